@@ -11,8 +11,11 @@ denoises its own clip with a full weight replica; there is no collective inside 
 start/stop barriers and the max-over-ranks reduction of the elapsed time.  value = N * steps / max-rank time (weak
 scaling: per-GPU work is fixed).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel family, measured live with hipEvents on the launch
-stream) and `cpu_baseline` (the CPU oracle timed on a bounded sample, N = 1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and reports them (`value`,
+`ms_per_step`); `--dump-outputs DIR` then writes the last timed step's x_{t-1} and pred_x0 as DIR/<name>.npy (float32).
+`--full` adds everything else, after the timed region: the VAE decode behind `clips_per_min`, `roofline` (dominant
+kernel family, measured with hipEvents on the launch stream), the child runs (`at_tolerance`, `other_configs`,
+`training_step`) and `cpu_baseline` (the CPU oracle timed on a bounded sample, N = 1 only).
 """
 import argparse
 import contextlib
@@ -36,6 +39,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--resolution", default="1024", choices=["1024", "512"])
     ap.add_argument("--batch", type=int, default=1, help="clips per GPU per step (reference driver uses 3 modalities)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the VAE decode "
+                         "(clips_per_min), the per-family roofline, the child runs and the CPU baseline; the --no-* switches "
+                         "below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (x_prev, pred_x0) to DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full"],
                     help="sample: one oracle forward at MDM512's spatial size on a 4-frame clip (3.15 TFLOP, tens of seconds); "
@@ -159,7 +168,7 @@ def child_bench(args, what, flags=(), env_extra=None, steps=4, warmup=1):
     child's own roofline record rides along.  Children run no children, no CPU baseline and no decode."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--batch", str(args.batch),
-           "--no-cpu-baseline", "--no-decode", "--no-children", "--profile-steps", "1", *flags]
+           "--full", "--no-cpu-baseline", "--no-decode", "--no-children", "--profile-steps", "1", *flags]
     if args.no_graph:
         cmd.append("--no-graph")
     env = dict(os.environ, **(env_extra or {}))
@@ -272,15 +281,38 @@ def make_workload(args, device, rank, dist):
               fs=inp["fs"], sparse_x=inp["sparse_x"], class_label=inp["class_label"], cfg_img=None,
               unconditional_conditioning_img_nonetext=None)
 
+    last = {}
+
     def run(n, x, start_index):
+        x0 = None
         for i in range(n):
             index = (start_index - i) % S
             ts = torch.full((args.batch,), int(sampler.ddim_timesteps[index]), device=device, dtype=torch.long)
-            x, _ = sampler.p_sample_ddim(x, inp["cond"], ts, index=index, **kw)
+            x, x0 = sampler.p_sample_ddim(x, inp["cond"], ts, index=index, **kw)
+        if n:
+            last.update(x_prev=x, pred_x0=x0)        # what a caller of p_sample_ddim received from the last step
         return x
 
     model.model.diffusion_model.use_hip_graph = not args.no_graph
-    return {"run": run, "x0": inp["x_T"], "S": S, "model": model, "inp": inp, "hip": hip}
+    return {"run": run, "x0": inp["x_T"], "S": S, "model": model, "inp": inp, "hip": hip, "outputs": lambda: dict(last)}
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """arrays {name: tensor} -> d/<name>.npy in float32.  Beyond DUMP_BYTES in all, each array is cut to a fixed seeded sample of
+    its flattened elements (the same indices in every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 4
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if total > DUMP_BYTES:
+            keep = max(1, t.numel() * DUMP_BYTES // total)
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(d, name + ".npy"), a.cpu().numpy())
 
 
 def main():
@@ -298,7 +330,7 @@ def main():
     run, S, model, hip = wl["run"], wl["S"], wl["model"], wl["hip"]
     use_graph = not args.no_graph
     x = run(args.warmup, wl["x0"], S - 1)
-    profile = not args.no_profile and hip is not None
+    profile = args.full and not args.no_profile and hip is not None
     if profile and not use_graph:            # eager mode: the timed region itself is bracketed with hipEvents
         hip.prof_reset()
         hip.prof_enable((1 << len(hip.FAM_NAMES)) - 1)
@@ -312,12 +344,14 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = parallel.max_over_ranks(elapsed, dist, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl["outputs"]() if "outputs" in wl else {"x_prev": x})
     finite = bool(torch.isfinite(x).all().item())
 
     # One clip = 50 such steps + one AutoencoderKL decode of its 16 frames (outside the timed region; reported so that
     # clips/min is a measured figure, not steps/s divided by 50).
     decode_ms = None
-    if not args.no_decode and model is not None:
+    if args.full and not args.no_decode and model is not None:
         z = x[:1].contiguous()
         model.decode_first_stage(z)                      # warm-up: weight packing, allocator
         sync(device)
@@ -371,10 +405,11 @@ def main():
         # context-free prefix, 3.4 T; the sub-pixel upsample convs issue 4/9 of theirs), so this is a reference-equivalent rate
         "reference_equivalent_tflops_per_gpu": round(step_tflop * args.batch * args.steps / elapsed, 2),
         "reference_equivalent_frac_of_bf16_mfma_peak": round(step_tflop * args.batch * args.steps / elapsed / PEAK_TFLOPS_BF16, 4),
-        "clips_per_min": round(60.0 * world * args.batch / (50.0 * elapsed / args.steps + (decode_ms or 0.0) / 1000.0), 4),
-        "vae_decode_ms_per_clip": None if decode_ms is None else round(decode_ms, 2),
         "output_finite": finite,
     }
+    if args.full:
+        out["clips_per_min"] = round(60.0 * world * args.batch / (50.0 * elapsed / args.steps + (decode_ms or 0.0) / 1000.0), 4)
+        out["vae_decode_ms_per_clip"] = None if decode_ms is None else round(decode_ms, 2)
     if fams:
         total_ms = sum(f["ms"] for f in fams) or 1.0
         kernels = []
@@ -409,7 +444,7 @@ def main():
             out["roofline"]["frac_of_measured_peak"] = round(dom["achieved"] / MEASURED_MFMA_PEAK_TFLOPS, 4)
         out["kernels"] = kernels
         out["kernel_time_ms_per_step"] = round(total_ms / prof_steps, 3)
-    children = world == 1 and args.operand == "bf16" and not args.no_children and not os.environ.get("MUDG_ATTN_FP8")
+    children = args.full and world == 1 and args.operand == "bf16" and not args.no_children and not os.environ.get("MUDG_ATTN_FP8")
     if children and not args.no_at_tolerance:
         out["at_tolerance"] = at_tolerance(args)      # child process; this one idles meanwhile (288 GB hold both replicas)
         out["value_at_tolerance"] = out["at_tolerance"].get("value")      # steps/s of the mode that meets the stated 1e-3 tolerance
@@ -417,7 +452,7 @@ def main():
         out["other_configs"] = other_configs(args)
     if children and not args.no_training and args.batch == 1:
         out["training_step"] = training_step_record(args)
-    if world == 1 and not args.no_cpu_baseline and model is not None:
+    if args.full and world == 1 and not args.no_cpu_baseline and model is not None:
         try:
             out["cpu_baseline"] = cpu_baseline(model, wl["inp"], args.resolution, args.cpu_baseline)
         except Exception as e:          # the baseline is a report, never a reason to lose the GPU number

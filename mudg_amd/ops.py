@@ -531,6 +531,9 @@ def add_(y, x, alpha=1.0):
 
 def lincomb(x, y, ca, cb):
     """ca[b] * x[b] + cb[b] * y[b] for fp32 (B, ...) tensors and fp32 [B] device coefficient vectors."""
+    for t in (x, y, ca, cb):
+        if not t.is_cuda:           # the kernel would dereference host addresses
+            raise hip.MudgError(f"lincomb: expected tensors on the GPU, got {t.device}")
     x, y = x.float().contiguous(), y.float().contiguous()
     ca, cb = ca.float().contiguous(), cb.float().contiguous()
     out = torch.empty_like(x)

@@ -125,7 +125,9 @@ class ChildRuns:
         # The children's reference arithmetic is torch on the host: each child gets its share of the cores.  (Six children with the
         # default of one OpenMP thread per core each — 768 spinning threads on 128 cores — ran the variant block FORTY times slower
         # than one after the other: round-6 log, gpurun_out/r6/gpu_tests_1.txt.)
-        self.threads = max(2, (os.cpu_count() or 8) // self.workers)
+        # The cores to share are this process's allotment where OMP_NUM_THREADS sets one, not every core of the host.
+        budget = int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 8
+        self.threads = max(2, budget // self.workers)
 
     def submit(self, key, cmd, cwd, env, timeout, alone=False):
         """alone=True: nothing else starts before this child has finished — the first child of a module runs so, and leaves warm
