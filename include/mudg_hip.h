@@ -126,7 +126,7 @@ int mudg_gemm(const MudgGemmDesc* d, void* stream);
  * runs it (same-size 3x3 convs, temporal convs with korder 0 and plain GEMMs with N % 320 == 0 whose frames are
  * whole 288-row tiles: Hout * Wout, HW — for mode 0 the caller's hint in HW — a multiple of 288), or 160 where the 160 x 320-tile
  * kernel of the 16-bit builds does (round 6: the same problems when a frame is whole 160-row tiles but not whole 288-row ones and
- * has at least 640 rows — MDM512's 2560- and 640-pixel frames; plain GEMMs there from K = 640, or without a residual).  `stats` then holds
+ * has at least 640 rows — MDM512's 2560- and 640-pixel frames; plain GEMMs there from K = 1280).  `stats` then holds
  * fp32 [ceil(M / rows)][Nout][2], and the consumer (mudg_groupnorm_fused) is told the same height.  The answer depends on the
  * descriptor's geometry, strides and pointer alignment, never on M: a clip's results do not depend on the batch it travels in. */
 int mudg_gemm_stats_rows(const MudgGemmDesc* d);

@@ -1849,27 +1849,15 @@ extern "C" int mudg_attention(const MudgAttnDesc* dp, void* stream) {
 #if MUDG_PLANES > 1
     {
         constexpr int smem = 4 * PLANES * ATILE * (int)sizeof(h16);
-        static bool attr_done[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) MUDG_FAIL(MUDG_ELAUNCH, "mudg_attention: hipGetDevice");
-        if (!attr_done[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "mudg_attention: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_done[dev] = true;
-        }
+        if (const int rc = mudg_lds_opt_in<&attn_split_kernel<false>>(smem, "mudg_attention")) return rc;
+        if (const int rc = mudg_lds_opt_in<&attn_split_kernel<true>>(smem, "mudg_attention")) return rc;
         bool dma_ok = false;
 #if MUDG_PLANES == 2
         // the long self-attention on LDS-DMA staged tiles (whole key tiles inside the 2-GiB window of a buffer descriptor)
         dma_ok = wide && d.Nk % 64 == 0 && (int64_t)d.Nk * d.ldk * 2 < (1ll << 31) && (int64_t)64 * d.ldvt * 2 + (int64_t)d.Nk * 2 + d.ldvt < (1ll << 31);
         if (dma_ok) {
-            static bool attr2[64] = {};
-            if (!attr2[dev]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_split_dma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_DMA_SMEM);
-                if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_split_dma_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_DMA_SMEM);
-                if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "mudg_attention: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                attr2[dev] = true;
-            }
+            if (const int rc = mudg_lds_opt_in<&attn_split_dma_kernel<true>>(SPLIT_DMA_SMEM, "mudg_attention")) return rc;
+            if (const int rc = mudg_lds_opt_in<&attn_split_dma_kernel<false>>(SPLIT_DMA_SMEM, "mudg_attention")) return rc;
             if (d.q_prescaled) hipLaunchKernelGGL(attn_split_dma_kernel<true>, dim3((unsigned)total), dim3(256), SPLIT_DMA_SMEM, s, d, nqt, (int)total);
             else hipLaunchKernelGGL(attn_split_dma_kernel<false>, dim3((unsigned)total), dim3(256), SPLIT_DMA_SMEM, s, d, nqt, (int)total);
         }
@@ -1910,15 +1898,8 @@ extern "C" int mudg_attention(const MudgAttnDesc* dp, void* stream) {
         xq = xq > 8 ? 8 : xq;
         if (xv && xq >= 2 && d.Nk <= 2 * KB && (!d.K2 || d.Nk2 <= KB)) {
             constexpr int smem = 2 * XK_TILES * ATILE * (int)sizeof(h16);
-            static bool attr_done[64] = {};
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) MUDG_FAIL(MUDG_ELAUNCH, "mudg_attention: hipGetDevice");
-            if (!attr_done[dev]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-                if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-                if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "mudg_attention: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                attr_done[dev] = true;
-            }
+            if (const int rc = mudg_lds_opt_in<&xattn_kernel<false>>(smem, "mudg_attention")) return rc;
+            if (const int rc = mudg_lds_opt_in<&xattn_kernel<true>>(smem, "mudg_attention")) return rc;
             const int nqc = (nqt + xq - 1) / xq;
             const int64_t totx = (int64_t)nqc * d.F * d.heads;
             if (d.K2) hipLaunchKernelGGL(xattn_kernel<true>, dim3((unsigned)totx), dim3(256), smem, s, d, nqt, xq, nqc, (int)totx);

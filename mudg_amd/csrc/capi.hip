@@ -33,6 +33,24 @@ int mudg_variant(const char* name, int dflt) {
 }
 #endif
 
+int mudg_current_device() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return -1;
+    return dev;
+}
+
+int mudg_cu_count() {
+    static int cus[MAX_DEVICES] = {};
+    const int dev = mudg_current_device();
+    if (dev < 0) return 0;
+    if (!cus[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        cus[dev] = n;
+    }
+    return cus[dev];
+}
+
 int mudg_prof_begin(int fam, hipStream_t s) {
     if (!(g_mask & (1 << fam))) return -1;
     std::lock_guard<std::mutex> lk(g_mu);

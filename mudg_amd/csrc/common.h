@@ -176,7 +176,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // -DMUDG_DEBUG_VARIANTS (libmudg_hip_dbg.so, used by tests/test_gemm_variants_gpu.py and tools/); the shipped libraries
 // take the default — no environment variable changes which kernel they run.
 #ifdef MUDG_DEBUG_VARIANTS
-int mudg_variant(const char* name, int dflt);         // getenv("MUDG_" name), read at every call (call sites cache it)
+int mudg_variant(const char* name, int dflt);         // getenv("MUDG_" name), read at every call (some call sites cache it)
 #else
 static inline int mudg_variant(const char*, int dflt) { return dflt; }
 #endif
@@ -194,3 +194,22 @@ static inline int mudg_check_launch(const char* what) {
     return MUDG_OK;
 }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// Per-device host state (capi.hip) is kept in arrays of MAX_DEVICES: one process may drive several GPUs.
+constexpr int MAX_DEVICES = 64;
+int mudg_current_device();      // the current device, or -1 (none, or beyond MAX_DEVICES)
+int mudg_cu_count();            // compute units of the current device, or 0 when it cannot be asked (callers pick their fallback)
+// Lets Kernel take `bytes` of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize): set once per device and kernel, keyed by the
+// kernel itself.  MUDG_OK, or MUDG_ELAUNCH with the error text "<what>: ...".
+template <auto Kernel>
+int mudg_lds_opt_in(int bytes, const char* what) {
+    static bool done[MAX_DEVICES] = {};
+    const int dev = mudg_current_device();
+    if (dev < 0) MUDG_FAIL(MUDG_ELAUNCH, "%s: no current device", what);
+    if (!done[dev]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+        done[dev] = true;
+    }
+    return MUDG_OK;
+}

@@ -24,8 +24,6 @@
 #include <cmath>
 #include <type_traits>
 
-bool mudg_gemm_fast_ok(const MudgGemmDesc& d);
-
 namespace {
 
 
@@ -1052,20 +1050,10 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
     }
 }
 
-// Lazily created per-device state (a zero page, the Phi table, the kernels' LDS opt-in): keyed by the current device so
-// that one process may drive several GPUs.
-}  // namespace
-int mudg_current_device() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return -1;
-    return dev;
-}
-namespace {
-int current_device() { return mudg_current_device(); }
-
+// Lazily created per-device state (a zero page, the Phi table): keyed by the current device so that one process may drive several GPUs.
 const h16* zero_page() {
     static h16* page[MAX_DEVICES] = {};
-    const int dev = current_device();
+    const int dev = mudg_current_device();
     if (dev < 0) return nullptr;
     if (!page[dev]) {
         void* ptr = nullptr;
@@ -1080,12 +1068,10 @@ const h16* zero_page() {
 }  // namespace
 const float* mudg_phi_table(bool split_ok) {
     static float* tabs[MAX_DEVICES] = {};
-    static int mode = -1;
-    if (mode < 0) mode = mudg_variant("GELU_LUT", 1);
     // the split-operand builds evaluate erf (bf16x3: to 1.5e-7); bf16x3's 288 x 256 GEGLU tile asks for the table and interpolates it
     // to the same accuracy with a cubic (split_ok, wgemm.hip)
-    if (!mode || (PLANES > 1 && !(split_ok && PLANES == 2))) return nullptr;
-    const int dev = current_device();
+    if (!mudg_variant("GELU_LUT", 1) || (PLANES > 1 && !(split_ok && PLANES == 2))) return nullptr;
+    const int dev = mudg_current_device();
     if (dev < 0) return nullptr;
     float*& tab = tabs[dev];
     if (!tab) {
@@ -1102,26 +1088,60 @@ const float* mudg_phi_table(bool split_ok) {
     return tab;
 }
 namespace {
-const float* phi_table() { return mudg_phi_table(); }
 
 template <typename G, int MODE, bool FAST, bool SB = false>
 int launch(const MudgGemmDesc& d, int vflags, hipStream_t s) {
-    static bool attr_done[MAX_DEVICES] = {};
     const h16* zp = zero_page();
     if (!zp) MUDG_FAIL(MUDG_ELAUNCH, "gemm: could not allocate the zero page");
-    bool& attr_set = attr_done[current_device()];
     constexpr int smem = smem_main<G>(FAST, SB);
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<G, MODE, FAST, SB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem + PHI_BYTES);
-        if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (const int rc = mudg_lds_opt_in<&gemm_kernel<G, MODE, FAST, SB>>(smem + PHI_BYTES, "gemm")) return rc;
     const int tiles = ((d.M + G::BM - 1) / G::BM) * ((d.N + G::BN - 1) / G::BN);
     dim3 grid(tiles, 1, d.batch);
-    const float* phi = d.geglu ? phi_table() : nullptr;
+    const float* phi = d.geglu ? mudg_phi_table() : nullptr;
     hipLaunchKernelGGL((gemm_kernel<G, MODE, FAST, SB>), grid, dim3(G::NTH), smem + (phi ? PHI_BYTES : 0), s, d, vflags, zp, phi);
     return mudg_check_launch("mudg_gemm");
+}
+
+// ---- kernel selection ------------------------------------------------------------------------------------------------------------
+// The kernel-variant switches that select GEMM kernels (common.h, mudg_variant), all read here: at every call in the variant builds, so
+// that one process can compare kernels; folded to these defaults in the shipped libraries.  Their meanings: at the rules below.
+struct GemmSwitches {
+    int fast = mudg_variant("GEMM_FAST", 1), sb = mudg_variant("GEMM_SB", 1), persist = mudg_variant("GEMM_PERSIST", 1);
+    int wide = mudg_variant("GEMM_WIDE", 2), xshare = mudg_variant("CONV_XSHARE", 1);
+    int w288 = mudg_variant("GEMM_W288", 1), w288p = mudg_variant("GEMM_W288P", 1), w288q = mudg_variant("GEMM_W288Q", 0);
+    int h144 = mudg_variant("GEMM_H144", 1), h144pf = mudg_variant("GEMM_H144PF", 1);
+    int h144delay = mudg_variant("GEMM_H144DELAY", 0) | (mudg_variant("GEMM_H144ABL", 0) << 16) | (mudg_variant("GEMM_H144PRIO", 1) ? 0 : 1 << 20);
+    int w160 = mudg_variant("GEMM_W160", 1), w160defer = mudg_variant("GEMM_W160DEFER", 1);
+};
+
+// Whether the buffer-descriptor (FAST) kernels can run this problem.  Variant switch GEMM_FAST=0 forces the generic
+// address path (for A/B measurements and tests of both paths).
+bool fast_ok(const MudgGemmDesc& d, const GemmSwitches& sw) {
+    if (!sw.fast) return false;
+    const int cin = d.mode == 0 ? d.K : d.Cin;
+    if ((d.K & 63) || (cin & 63) || (d.csplit & 63)) return false;
+    if (d.mode == 1 && (d.upsample || d.Hout * d.Wout <= 0)) return false;
+    const int64_t ld = d.X2 && d.ldx2 > d.ldx ? d.ldx2 : d.ldx;
+    int64_t rel = 255, soff = (int64_t)cin * 2 + (PLANES > 1 ? ld * 2 : 0);
+    if (d.mode == 1) {
+        rel = (int64_t)(255 / (d.Hout * d.Wout) + 2) * d.Hin * d.Win;
+        soff += (int64_t)(2 * d.Win + 2) * ld * 2;
+    } else if (d.mode == 2) {
+        soff += (int64_t)2 * d.HW * ld * 2;
+        if (d.korder) rel = (int64_t)(d.T - 1) * d.HW + 8;      // TMAP: a tile's rows span all frames of a clip
+    }
+    const int64_t lim = (int64_t)1 << 31;
+    return rel * ld * 2 + 128 + soff + 16 < lim && (int64_t)(255 + (PLANES > 1)) * d.ldw * 2 + (int64_t)d.K * 2 + 144 < lim;
+}
+
+// Whether Y / R can be accessed in whole 16-byte pieces (VF_Y / VF_R).
+int access_flags(const MudgGemmDesc& d) {
+    int vflags = 0;
+    const int ybytes = d.out_fp32 == KIND_F32 ? 4 : 2;
+    if (aligned16(d.Y) && ((int64_t)d.ldy * ybytes) % (d.out_fp32 ? 16 : 16 * PLANES) == 0 && ((int64_t)d.sY * ybytes) % 16 == 0) vflags |= VF_Y;
+    const int rbytes = d.res_fp32 == KIND_F32 ? 4 : 2;
+    if (d.R && aligned16(d.R) && ((int64_t)d.ldr * rbytes) % (d.res_fp32 ? 16 : 16 * PLANES) == 0 && ((int64_t)d.sR * rbytes) % 16 == 0) vflags |= VF_R;
+    return vflags;
 }
 
 // Problems with at least three tiles per CU (eight for the 3x3 convs) go to the single-buffer / 4-workgroups-per-CU
@@ -1129,13 +1149,11 @@ int launch(const MudgGemmDesc& d, int vflags, hipStream_t s) {
 // double-buffered 2-per-CU kernel wins.
 // Variant switch GEMM_SB=0 disables it, =2 forces it for every FAST problem.  (bf16x3 build: the fused-piece kernel is the
 // only FAST kernel, see fused_planes.)
-bool use_single_buffer(const MudgGemmDesc& d) {
+bool use_single_buffer(const MudgGemmDesc& d, const GemmSwitches& sw) {
     if (fused_planes(true)) return true;
     if (d.Y8) return false;                   // the fused fp8 copy is compiled into the two-per-CU variant only
-    static int mode = -1;
-    if (mode < 0) mode = mudg_variant("GEMM_SB", 1);
-    if (mode == 0) return false;
-    if (mode == 2) return true;
+    if (sw.sb == 0) return false;
+    if (sw.sb == 2) return true;
     const int64_t tiles = (int64_t)((d.M + G128::BM - 1) / G128::BM) * ((d.N + G128::BN - 1) / G128::BN) * d.batch;
     // (3x3 convs whose dx taps share a staged tile — XSHARE, one-stage kernel only — switch at half the tile count: 18432 x 1280 x
     //  11520 551 -> 530 us, x 23040 1072 -> 1040; 4608 rows stay on the two-stage kernel, 170 against 224 us.  Both kernels add the
@@ -1145,16 +1163,6 @@ bool use_single_buffer(const MudgGemmDesc& d) {
     return tiles >= (d.mode == 1 ? (xs ? 1024 : 2048) : 768);
 }
 
-// Variant switch GEMM_PERSIST=0: the non-persistent 128 x 128 kernels (A/B measurements); 2 / 3 / 4: that many persistent
-// workgroups per CU for every problem.
-int persist_mode() {
-    static int mode = -1;
-    if (mode < 0) mode = mudg_variant("GEMM_PERSIST", 1);
-    return mode;
-}
-bool use_persistent() { return persist_mode() != 0; }
-// Workgroups per CU of the persistent kernel: one K-tile stage at 4 per CU where the one-tile-per-workgroup rule chose the
-// single-buffer variant, two stages at 2 per CU otherwise.
 // What the persistent kernel (pgemm.hip) takes, and where it is used.
 // Takes: whole 16-byte pieces everywhere (Nout % 8 == 0, aligned Y / R rows), a residual that may seed the accumulators (alpha 1),
 // a group bias constant over a 128-row tile, bias-only GEGLU, no plain activation; ragged widths, the Perceiver's GELU and odd
@@ -1170,28 +1178,29 @@ bool use_persistent() { return persist_mode() != 0; }
 //     these problems is the result stream slowing every fetch of a K loop that has one stage in flight per workgroup
 //     (DESIGN §6), which neither persistence nor the direct epilogue changes.
 // Variant switch GEMM_PERSIST: 0 = never, 1 = this rule, 2 / 3 / 4 = every eligible problem at that many workgroups per CU.
-bool persistent_ok(const MudgGemmDesc& d, int vflags) {
-    if (!use_persistent() || PLANES > 2) return false;
+bool persistent_ok(const MudgGemmDesc& d, int vflags, const GemmSwitches& sw) {
+    if (!sw.persist || PLANES > 2) return false;
     if (d.mode == 2 && d.korder) return false;            // slab-major temporal convs (TMAP): the one-tile kernels' row mapping and K walk
     if (d.act || !(vflags & VF_Y) || (d.R && !(vflags & VF_R))) return false;
     if ((d.geglu ? d.N / 2 : d.N) % 8 != 0) return false;
     if (d.geglu && (d.mode != 0 || d.R || d.gbias || d.stats)) return false;
     if (d.R && d.alpha != 1.f) return false;
     if (d.gbias && d.rows_per_group % 128 != 0) return false;
-    if (persist_mode() != 1 || d.geglu) return true;
+    if (sw.persist != 1 || d.geglu) return true;
     // The rule must not look at M: a residual enters the persistent kernel's sum first and the one-tile kernels' last, and a clip's
     // result may not depend on the batch it travels in (tests/test_fullsize_gpu.py).  N, K >= 1280 = the plain GEMMs of the
     // 1280-wide levels, whatever the number of clips.
     return d.mode == 0 && d.N >= 1280 && d.K >= 1280;
 }
-bool use_single_buffer(const MudgGemmDesc& d);
-int persistent_wgs(const MudgGemmDesc& d) {
-    const int m = persist_mode();
-    if (m >= 2 && m <= 4) return m;
-    return use_single_buffer(d) ? 4 : 2;
+// Workgroups per CU of the persistent kernel: one K-tile stage at 4 per CU where the one-tile-per-workgroup rule chose the
+// single-buffer variant, two stages at 2 per CU otherwise.
+int persistent_wgs(const MudgGemmDesc& d, const GemmSwitches& sw) {
+    int wgs = sw.persist >= 2 && sw.persist <= 4 ? sw.persist : (use_single_buffer(d, sw) ? 4 : 2);
+    const bool rs = d.R || d.stats;
+    if (fused_planes(true) || d.Y8 || rs) wgs = wgs > 2 ? (rs && !fused_planes(true) && !d.Y8 ? 3 : 2) : 2;   // 64-KiB stage / the fused fp8 copy / seeds and partials
+    return wgs;
 }
 
-#if MUDG_PLANES == 1
 // The wide tiles (G320 / G256, 16-bit builds, descriptor loader): 0 = the 128 x 128 kernels, 5 / 4 = NI of the wide tile.
 // Measured per shape on MI355X (tools/exp_tiles.py, profiles/r3/tiles_*.txt): with all 256 CUs holding one wide tile each the
 // main loop runs at 1280-1370 TFLOP/s against 980-1070 of the 128 x 128 kernels (long K), but a wide tile is alone on its CU —
@@ -1199,67 +1208,192 @@ int persistent_wgs(const MudgGemmDesc& d) {
 // only wins where K is long AND the rounds are full enough: the 3x3 convs with K >= 8000 at N = 320 (+ 6.7 %), parity at
 // K = 5760, and it loses on every plain / GEGLU GEMM of the UNet (K <= 5120: - 15 ... - 55 %).  The rule below is that measurement.
 // Variant switch GEMM_WIDE=0 disables them, =1 forces them wherever the columns fit (tests run every epilogue that way).
-int use_wide(const MudgGemmDesc& d) {
-    static int mode = -1;
-    if (mode < 0) mode = mudg_variant("GEMM_WIDE", 2);
-    if (mode == 0) return 0;
+int use_wide(const MudgGemmDesc& d, const GemmSwitches& sw) {
+    if (sw.wide == 0) return 0;
     if (d.Y8) return 0;                       // the fused fp8 copy lives in the 128 x 128 kernels' epilogue
     int ni = 0;
     if (d.geglu) ni = (d.N % 256 == 0) ? 4 : 0;
     else if (d.N % 320 == 0) ni = 5;
     else if (d.N % 256 == 0) ni = 4;
     if (!ni) return 0;
-    if (mode == 1) return ni;
+    if (sw.wide == 1) return ni;
     const int64_t tiles = (int64_t)((d.M + 255) / 256) * (d.N / (64 * ni)) * d.batch;
     const int64_t rounds = (tiles + 255) / 256;
     if (d.mode != 1 || d.geglu || d.K < 8000) return 0;
     if (tiles < 4 * 256 || tiles * 10 < rounds * 256 * 9) return 0;        // >= 4 rounds, >= 90 % of the slots of the rounds used
     return ni;
 }
-#endif
 
-}  // namespace
-
-// Whether the buffer-descriptor (FAST) kernels can run this problem.  Variant switch GEMM_FAST=0 forces the generic
-// address path (for A/B measurements and tests of both paths).
-bool mudg_gemm_fast_ok(const MudgGemmDesc& d) {
-    static int en = -1;
-    if (en < 0) en = mudg_variant("GEMM_FAST", 1);
-    if (!en) return false;
+// The tile kernels of wgemm.hip (16-bit builds and bf16x3; the 160-row tile and the 288-row tile's other forms: 16-bit builds only).
+// What the 288- or the 160-row tile can run at all.
+bool wgemm_eligible(const MudgGemmDesc& d, int vflags, int bm) {
+    if (d.batch != 1 || d.act || d.Y8 || d.subpixel || (d.mode == 1 && d.upsample)) return false;
+    if (d.geglu ? (d.mode != 0 || d.N % 256 != 0 || d.R || d.gbias || d.stats) : d.N % 320 != 0) return false;
+    if (!(vflags & VF_Y) || (d.R && !(vflags & VF_R))) return false;
     const int cin = d.mode == 0 ? d.K : d.Cin;
     if ((d.K & 63) || (cin & 63) || (d.csplit & 63)) return false;
-    if (d.mode == 1 && d.upsample) return false;
+    if (d.mode == 1 && (d.stride != 1 || d.pad != 1 || d.Hin != d.Hout || d.Win != d.Wout || d.K != 9 * d.Cin)) return false;
+    if (d.mode == 2 && (d.korder || d.K != 3 * d.Cin)) return false;       // (korder 1 means tiles of 8 pixels x 16 frames to the 128 x 128 kernels)
+    if (d.gbias && (d.rows_per_group % bm != 0)) return false;             // one group per tile: the group bias rides in the column constants
+    if (d.R && d.alpha != 1.f) return false;                               // the residual seeds the accumulators (w_seed)
+    if ((d.ldy & 7) || (d.R && (d.ldr & 7))) return false;                 // 8-byte pieces of the unpaired fragment
+    // 32-bit reach of the descriptor offsets
     const int64_t ld = d.X2 && d.ldx2 > d.ldx ? d.ldx2 : d.ldx;
-    int64_t rel = 255, soff = (int64_t)cin * 2 + (PLANES > 1 ? ld * 2 : 0);
-    if (d.mode == 1) {
-        rel = (int64_t)(255 / (d.Hout * d.Wout) + 2) * d.Hin * d.Win;
-        soff += (int64_t)(2 * d.Win + 2) * ld * 2;
-    } else if (d.mode == 2) {
-        soff += (int64_t)2 * d.HW * ld * 2;
-        if (d.korder) rel = (int64_t)(d.T - 1) * d.HW + 8;      // TMAP: a tile's rows span all frames of a clip
-    }
+    int64_t rows = bm + 16 + (PLANES > 1);                                 // (the second piece of a row: ld / 2 elements further)
+    if (d.mode == 1) rows += 2 * (int64_t)d.Win + 2;
+    if (d.mode == 2) rows += 2 * (int64_t)d.HW;
     const int64_t lim = (int64_t)1 << 31;
-    return rel * ld * 2 + 128 + soff + 16 < lim && (int64_t)(255 + (PLANES > 1)) * d.ldw * 2 + (int64_t)d.K * 2 + 144 < lim;
+    return rows * ld * 2 + (int64_t)cin * 2 + 256 < lim && (int64_t)(320 + 16 + (PLANES > 1)) * d.ldw * 2 + (int64_t)d.K * 2 + 256 < lim;
 }
 
-// Whether Y / R can be accessed in whole 16-byte pieces (VF_Y / VF_R).
-static int access_flags(const MudgGemmDesc& d) {
-    int vflags = 0;
-    const int ybytes = d.out_fp32 == KIND_F32 ? 4 : 2;
-    if (aligned16(d.Y) && ((int64_t)d.ldy * ybytes) % (d.out_fp32 ? 16 : 16 * PLANES) == 0 && ((int64_t)d.sY * ybytes) % 16 == 0) vflags |= VF_Y;
-    const int rbytes = d.res_fp32 == KIND_F32 ? 4 : 2;
-    if (d.R && aligned16(d.R) && ((int64_t)d.ldr * rbytes) % (d.res_fp32 ? 16 : 16 * PLANES) == 0 && ((int64_t)d.sR * rbytes) % 16 == 0) vflags |= VF_R;
-    return vflags;
+// The half-height GEGLU kernel (hgeglu_kernel).  Variant switch GEMM_H144: 0 = never, 1 = the rule, 2 = every GEGLU problem the 288 x 256
+// tile is eligible for (the callers have checked wgemm_eligible: mode 0, N % 256 == 0, K % 64 == 0, 16-byte Y pieces, no residual / group
+// bias / partials).  Same bits as the kernels it replaces, so the rule may look at M.
+// Variant switch GEMM_H144PF (measurements): 0 = the plain loop (every k half starts with its own fragment reads), 1 = the prefetching loop.
+bool half_height_ok(const MudgGemmDesc& d, const GemmSwitches& sw) {
+    if (!sw.h144 || !d.geglu) return false;
+    if (sw.h144 == 2) return true;
+    // Measured (MI355X; profiles/r6/h144*.txt, bench_h144_off / _rule.json): per launch x 0.90 ... 1.08 of the persistent 288 x 256 form in
+    // isolated timings (+ 3 ... 7 % at K = 320 on the level-0 rows and where the eight-wave tile has less than a round of tiles, - 5 ...
+    // - 10 % from K = 512: 92 instead of 136 FLOP per staged byte), and INSIDE the step — the same library, the same box, the rule "where
+    // it won in isolation" against never — 122.39 against 121.53 ms: the rocprofv3 trace of that step has its level-0 launches at 710 us
+    // where the persistent form's were 681.  The rule is therefore: never.  The kernel stays, tested (tests/test_gemm_variants_gpu.py
+    // runs the parity suites with it forced, test_half_height_geglu_kernel_is_bit_identical...), as the measured answer to "two
+    // workgroups per CU" (DESIGN §3.2).
+    return false;
+}
+
+// The persistent form (wgemm_pkernel): whole tiles, at least two K-tiles, more tiles than CUs.  Same bits as the one-tile form, so M may
+// decide.  Measured (same box, tools/exp_w288.py with MUDG_GEMM_W288P = 0 / 2, profiles/r5/w288_persistent.txt): GEGLU + 2 ... + 9 % (its
+// epilogue is the longest and fetches nothing); plain GEMMs - 7 ... + 6 % with no pattern worth a rule — a residual's fetches queue
+// behind the next tile's staged pieces, and what persistence saves per tile (launch, first-fetch latency) is small beside what bounds
+// the short-K problems (the epilogue's own traffic).  Variant switch GEMM_W288P: 0 = never, 1 = GEGLU only (the rule), 2 = every
+// problem the kernel can run.
+// Returns its grid (one workgroup per CU, whole XCDs), or 0 for the one-tile form.
+int w288_persistent_grid(const MudgGemmDesc& d, const GemmSwitches& sw) {
+    if (!sw.w288p || (sw.w288p == 1 && !d.geglu) || d.mode != 0 || d.R || d.M % WBM != 0 || d.K < 2 * BK) return 0;
+    {   // the whole problem behind one descriptor per operand: rows ride in 32-bit scalar offsets
+        const int64_t ld = d.X2 && d.ldx2 > d.ldx ? d.ldx2 : d.ldx, lim = (int64_t)1 << 31;
+        if (((int64_t)d.M + 16) * ld * 2 + (int64_t)d.K * 2 + 256 >= lim || ((int64_t)d.N + 16) * d.ldw * 2 + (int64_t)d.K * 2 + 256 >= lim) return 0;
+    }
+    const int n = mudg_cu_count();
+    if (n <= 0) return 0;                                    // no current device
+    const int cus = (n < 8 ? 8 : n) & ~7;                    // whole XCDs' worth of workgroups
+    const int tiles = (d.M / WBM) * (d.N / (d.geglu ? 256 : 320));
+    return tiles > cus ? cus : 0;
+}
+
+// Where the 288-row tile is used.  The rule never looks at M (see wgemm.hip's header): `S`, the rows of one frame (mode 0: the caller's hint
+// in d.HW), must be whole tiles — then every frame batch of the benchmarked resolution fills whole rounds of the 256 CUs.
+// Variant switch GEMM_W288 (debug-variants build; read at every call so that one process can compare kernels): 0 = never, 1 = the rule
+// below, 2 = every eligible problem.
+bool wgemm288_ok(const MudgGemmDesc& d, int vflags, const GemmSwitches& sw) {
+    if (!sw.w288 || !wgemm_eligible(d, vflags, WBM)) return false;
+    if (sw.w288 == 2) return true;
+    if (PLANES == 1 && d.geglu && half_height_ok(d, sw)) return true;         // (same bits as every other GEGLU kernel: no frame geometry needed)
+    const int S = d.mode == 1 ? d.Hout * d.Wout : d.HW;
+    if (S <= 0 || S % WBM != 0) return false;
+    // Measured per shape against the 128 x 128 kernels (tools/exp_w288.py, profiles/r5/w288_shapes.txt; MI355X, frames of whole tiles):
+    // 3x3 convs + 20 ... + 40 %, temporal convs + 19 ... + 28 %; plain GEMMs + 16 ... + 37 % from K = 1280, + 1 ... + 26 % at K = 320 / 640
+    // (N <= K: every projection of the UNet; - 1 ... - 3 % for N = 2 ... 3 K with a residual, which the UNet does not have); GEGLU below.
+    // bf16x3 (same tool with MUDG_OPERAND=bf16x3, profiles/r5/w288_x3_shapes.txt; the 128 x 128 side is the fused-piece kernel, one-tile or
+    // persistent as gemm.hip selects): 3x3 convs + 27 ... + 44 %, temporal convs + 22 ... + 27 %, GEGLU + 11 ... + 13 %, plain GEMMs + 11 ...
+    // + 42 % down to K = 320: three times the MFMAs per staged byte and per epilogue — every problem whose frames are whole tiles.
+    if (d.mode != 0 || PLANES == 2) return true;
+    // GEGLU (bit-identical to the persistent 128 x 128 kernel it replaces, so M may decide): + 7 ... + 16 % in the persistent form (more
+    // tiles than CUs) at every K; the one-tile form + 11 % at K = 1280, - 1 % at K = 640, - 5 ... - 12 % at K = 320.  Since round 6 the
+    // two-workgroup half-height kernel (hgeglu_kernel) runs GEGLU wherever its rule says so (half_height_ok).
+    if (d.geglu && d.K < 640) return w288_persistent_grid(d, sw) > 0;
+    return true;
+}
+
+// The 160-row tile (wq_kernel<..., 5>): frames of whole 160-row tiles that are not whole 288-row tiles.  Variant switch GEMM_W160: 0 = never,
+// 1 = the rule, 2 = every eligible problem (as GEMM_W288 = 2; the 288-row tile's own rule is asked first).
+bool w160_ok(const MudgGemmDesc& d, int vflags, const GemmSwitches& sw) {
+    if (!sw.w160 || !wgemm_eligible(d, vflags, QBM)) return false;
+    if (sw.w160 == 2) return true;
+    const int S = d.mode == 1 ? d.Hout * d.Wout : d.HW;
+    if (S <= 0 || S % QBM != 0) return false;
+    // Measured per shape against the 128 x 128 kernels, twice.  In isolation (tools/exp_w160.py, profiles/r6/w160_shapes.txt; MI355X, MDM512's
+    // frame batches, every operand hot in the 256-MiB Infinity Cache after the first repeat): 3x3 convs + 28 ... + 45 %, temporal convs + 14 ...
+    // + 27 % at 2560- and 640-pixel frames; plain GEMMs + 13 ... + 35 % from K = 640 with N <= K, + 0 ... + 9 % for N = 2 ... 3 K, at K = 320
+    // + 7 ... + 14 % without and - 2 ... - 3 % with a residual; GEGLU - 9 ... - 22 % against the persistent 128 x 128 kernel.  And INSIDE
+    // the step (tools/shape_profile.py 512 with GEMM_W160 = 0 / 1 / 2, profiles/r6/shapes_m512_w160_*.md), where a kernel's operands come
+    // from HBM or from its producer: convs + 12 ... + 27 %, temporal convs + 5 ... + 14 %, plain GEMMs + 11 ... + 16 % at K >= 1280 — and
+    // - 3 ... - 13 % at K = 320 / 640, where the one workgroup of a CU waits for its first k half alone while the 128 x 128 kernels have
+    // four workgroups per CU to cover for each other (the isolated timing hides it: its operands never leave the cache).  The rule follows
+    // the step.  One workgroup per CU wants a frame batch to bring enough tiles: the 160-pixel level (32 frames = 32 tile rows x 4 ... 8
+    // columns: half the CUs) stays on the 128 x 128 kernels (- 20 ... - 45 % there).  Never M: S, K, the mode.
+    if (S < 640 || d.geglu) return false;
+    if (d.mode != 0) return true;
+    return d.K >= 1280;
 }
 
 // The defaults mudg_gemm gives a caller's descriptor before any kernel-selection rule reads it: batch < 1 -> 1, no second source ->
 // csplit = the whole channel axis, alpha == 0 (a zero-initialised C struct) -> 1.  ONE place, so that every query about "which kernel
 // will run this" (mudg_gemm_stats_rows) sees exactly the descriptor mudg_gemm dispatches on.
-static void normalise_desc(MudgGemmDesc& d) {
+void normalise_desc(MudgGemmDesc& d) {
     if (d.batch < 1) d.batch = 1;
     if (!d.X2) d.csplit = d.mode == 0 ? d.K : d.Cin;
     if (d.alpha == 0.f) d.alpha = 1.f;
 }
+
+// THE kernel choice of mudg_gemm, for a normalised descriptor: which kernel runs the problem and everything its launch needs.  A pure function
+// of the descriptor, the variant switches and the CU count: it launches nothing and does not fail.  mudg_gemm launches what it names,
+// mudg_gemm_stats_rows reports its `rows`.  Precedence: the 288-row tile, the 160-row tile, then — on the descriptor loader — the wide
+// tiles, the persistent kernel, the single-buffer and the double-buffer kernel; the generic 128 x 128 kernel for everything else.
+GemmPlan gemm_plan(const MudgGemmDesc& d) {
+    const GemmSwitches sw;
+    GemmPlan p{};
+    p.vflags = access_flags(d);
+    // TMAP / TSHARE (see gemm_kernel): slab-major temporal convs on the descriptor loader; else the generic loader walks the slab-major K axis
+    // over plain 128-row tiles
+    if (d.mode == 2 && d.korder && fast_ok(d, sw)) p.vflags |= VF_TM;
+    // XSHARE (see gemm_kernel): same-size stride-1 3x3 convs with the slab-major K order.  Variant switch CONV_XSHARE=0: off.
+    if (sw.xshare && d.mode == 1 && d.korder && !d.subpixel && !d.upsample && d.stride == 1 && d.pad == 1 && d.Hin == d.Hout && d.Win == d.Wout &&
+        d.K == 9 * d.Cin && (d.Cin & 63) == 0)
+        p.vflags |= VF_XS;
+    p.rows = 128;
+    if (PLANES <= 2 && wgemm288_ok(d, p.vflags, sw)) {
+        p.rows = WBM;
+        // The 288-row tile on the loop of the 160-row one (wq_kernel<..., 9>), variant builds only.  Variant switch GEMM_W288Q: 0 = never (the
+        // rule: wgemm_kernel's six-phase loop), 2 = every one-tile problem of the 288-row tile (GEGLU included).  Measured per shape against the
+        // six-phase loop (tools/exp_w288.py q, profiles/r6/w288q_shapes.txt): 3x3 convs x 0.96 ... 1.04, temporal convs x 1.00 ... 1.02, plain
+        // GEMMs x 0.85 ... 1.07, GEGLU (one-tile against the persistent six-phase form) x 0.90 ... 0.98 — the same bits and no gain: two
+        // different schedules of the same 45 MFMAs, 14 fragment reads and 38 DMA pieces per k half end at the same 1300 - 1430 TFLOP/s.
+        if (PLANES == 1 && sw.w288p != 2 && sw.w288q == 2) {
+            p.kernel = GK_W288Q;
+        } else if (PLANES == 1 && d.geglu && half_height_ok(d, sw)) {
+            p.kernel = GK_H144;
+            p.pf = sw.h144pf != 0;
+            p.delay = sw.h144delay;
+        } else if (PLANES == 1 && (p.grid = w288_persistent_grid(d, sw)) > 0) {
+            p.kernel = GK_W288P;
+        } else {
+            p.kernel = GK_W288;
+        }
+    } else if (PLANES == 1 && w160_ok(d, p.vflags, sw)) {
+        p.rows = QBM;
+        p.kernel = GK_W160;
+        // a residual of 16-bit storage (the fp16 stream, an operand matrix) is deferred to the epilogue, an fp32 one seeds the accumulators.
+        // Variant switch GEMM_W160DEFER = 0: every residual seeds.
+        p.rs = !d.R ? 0 : ((d.res_fp32 != KIND_F32 && sw.w160defer) ? 2 : 1);
+    } else if (fast_ok(d, sw)) {
+        if (PLANES == 1 && (p.ni = use_wide(d, sw)) != 0) {
+            p.kernel = GK_WIDE;
+        } else if (persistent_ok(d, p.vflags, sw)) {
+            p.kernel = GK_PERSIST;
+            p.wgs = persistent_wgs(d, sw);
+        } else {
+            p.kernel = use_single_buffer(d, sw) ? GK_SINGLE : GK_DOUBLE;        // (bf16x3: always the single-stage fused-piece kernel)
+        }
+    } else {
+        p.kernel = GK_GENERIC;
+    }
+    return p;
+}
+
+}  // namespace
 
 // Height of the row blocks `stats` will be written in for this problem (mudg_hip.h): 288 / 160 where a tile kernel of wgemm.hip runs it, else 128.
 extern "C" int mudg_gemm_stats_rows(const MudgGemmDesc* dp) {
@@ -1267,8 +1401,7 @@ extern "C" int mudg_gemm_stats_rows(const MudgGemmDesc* dp) {
     MudgGemmDesc d = *dp;
     if (d.out_fp32 < 0 || d.out_fp32 > 2 || d.res_fp32 < 0 || d.res_fp32 > 2 || d.mode < 0 || d.mode > 2) return 128;
     normalise_desc(d);
-    const int rows = mudg_wgemm_rows(d, access_flags(d));
-    return rows ? rows : 128;
+    return gemm_plan(d).rows;
 }
 
 extern "C" int mudg_conv_subpixel_ok(const MudgGemmDesc* dp) {
@@ -1278,7 +1411,7 @@ extern "C" int mudg_conv_subpixel_ok(const MudgGemmDesc* dp) {
     if (d.X2 || d.R || d.gbias || d.stats || d.geglu || d.sX != 0 || d.sY != 0) return 0;
     if (d.Hout != d.Hin || d.Wout != d.Win || d.K != 4 * d.Cin || (d.Cin & 63)) return 0;
     d.csplit = d.Cin;
-    return mudg_gemm_fast_ok(d) ? 1 : 0;
+    return fast_ok(d, GemmSwitches{}) ? 1 : 0;
 }
 
 extern "C" int mudg_gemm(const MudgGemmDesc* dp, void* stream) {
@@ -1330,22 +1463,13 @@ extern "C" int mudg_gemm(const MudgGemmDesc* dp, void* stream) {
                      "mudg_gemm: Y8 needs S8, an operand-kind Y, N %% 32 == 0, no GEGLU / sub-pixel / batch, ldy8 %% 8 == 0");
     }
     MUDG_REQUIRE(d.out_fp32 >= 0 && d.out_fp32 <= 2 && d.res_fp32 >= 0 && d.res_fp32 <= 2, "mudg_gemm: out_fp32 / res_fp32 are 0 (operand), 1 (fp32) or 2 (fp16)");
-    int vflags = access_flags(d);
-
     if (d.mode == 2 && d.korder) {      // TMAP / TSHARE (see gemm_kernel): slab-major temporal convs are defined for 16-frame clips on the descriptor loader
         MUDG_REQUIRE(PLANES <= 2 && d.T == 16 && (d.HW & 7) == 0 && (d.Cin & 63) == 0 && d.K == 3 * d.Cin && !d.X2 && d.M == (d.M / (d.T * d.HW)) * d.T * d.HW,
                      "mudg_gemm: temporal conv with korder = 1 needs T = 16, HW %% 8 == 0, Cin %% 64 == 0, K = 3 Cin, one source, whole clips");
         // (the group-bias index of the epilogue is the LOGICAL row / rows_per_group: with the tile mapping that is the clip, nothing finer)
         MUDG_REQUIRE(!d.gbias || d.rows_per_group % (d.T * d.HW) == 0, "mudg_gemm: temporal conv with korder = 1 takes a group bias per clip(s) only");
-        if (mudg_gemm_fast_ok(d)) vflags |= VF_TM;      // else: the generic loader walks the slab-major K axis over plain 128-row tiles
     }
-    {   // XSHARE (see gemm_kernel): same-size stride-1 3x3 convs with the slab-major K order.  Variant switch CONV_XSHARE=0: off.
-        static int xs = -1;
-        if (xs < 0) xs = mudg_variant("CONV_XSHARE", 1);
-        if (xs && d.mode == 1 && d.korder && !d.subpixel && !d.upsample && d.stride == 1 && d.pad == 1 && d.Hin == d.Hout && d.Win == d.Wout &&
-            d.K == 9 * d.Cin && (d.Cin & 63) == 0)
-            vflags |= VF_XS;
-    }
+    const GemmPlan plan = gemm_plan(d);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int fam = d.mode == 0 ? MUDG_FAM_GEMM : (d.mode == 1 ? MUDG_FAM_CONV : MUDG_FAM_TCONV);
     const int slot = mudg_prof_begin(fam, s);
@@ -1353,27 +1477,20 @@ extern "C" int mudg_gemm(const MudgGemmDesc* dp, void* stream) {
     auto by_mode = [&](auto g, auto fast, auto sb) {
         using G = decltype(g);
         constexpr bool F = decltype(fast)::value, S = decltype(sb)::value;
-        return d.mode == 0 ? launch<G, 0, F, S>(d, vflags, s) : (d.mode == 1 ? launch<G, 1, F, S>(d, vflags, s) : launch<G, 2, F, S>(d, vflags, s));
+        const int vf = plan.vflags;
+        return d.mode == 0 ? launch<G, 0, F, S>(d, vf, s) : (d.mode == 1 ? launch<G, 1, F, S>(d, vf, s) : launch<G, 2, F, S>(d, vf, s));
     };
-    if (mudg_wgemm_ok(d, vflags)) {
-        rc = mudg_wgemm_launch(d, vflags, s);
-    } else if (mudg_gemm_fast_ok(d)) {
-#if MUDG_PLANES == 1
-        const int wide = use_wide(d);
-        if (wide) rc = wide == 5 ? by_mode(G320{}, std::true_type{}, std::false_type{}) : by_mode(G256{}, std::true_type{}, std::false_type{});
-        else
-#endif
-#if MUDG_PLANES <= 2
-        if (persistent_ok(d, vflags)) {
-            rc = mudg_pgemm_launch(d, vflags, persistent_wgs(d), s);
-        } else
-#endif
-        if (use_single_buffer(d)) rc = by_mode(G128{}, std::true_type{}, std::true_type{});
+    switch (plan.kernel) {
+    case GK_GENERIC: rc = by_mode(G128{}, std::false_type{}, std::false_type{}); break;
+    case GK_SINGLE: rc = by_mode(G128{}, std::true_type{}, std::true_type{}); break;
 #if MUDG_PLANES != 2
-        else rc = by_mode(G128{}, std::true_type{}, std::false_type{});
+    case GK_DOUBLE: rc = by_mode(G128{}, std::true_type{}, std::false_type{}); break;
 #endif
-    } else {
-        rc = by_mode(G128{}, std::false_type{}, std::false_type{});
+#if MUDG_PLANES == 1
+    case GK_WIDE: rc = plan.ni == 5 ? by_mode(G320{}, std::true_type{}, std::false_type{}) : by_mode(G256{}, std::true_type{}, std::false_type{}); break;
+#endif
+    case GK_PERSIST: rc = mudg_pgemm_launch(d, plan, s); break;
+    default: rc = mudg_wgemm_launch(d, plan, s); break;
     }
     const double flops = 2.0 * d.M * (double)d.N * d.K * d.batch;          // algorithmic (the split builds issue NSEG times as many)
     // algorithmic bytes at 16-bit storage: activations in (taps are re-reads of the same rows), weights, the result, and the

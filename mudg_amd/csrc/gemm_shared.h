@@ -1,5 +1,5 @@
 // gemm_shared.h — what the contraction kernels of gemm.hip and pgemm.hip have in common: K-tile geometry, the buffer-descriptor
-// helpers of the LDS-DMA loader, the GELU forms of the epilogues, and the host-side state both launchers use.
+// helpers of the LDS-DMA loader, the GELU forms of the epilogues, and the kernel plan (GemmPlan) that gemm.hip makes and the launchers take.
 #pragma once
 #include "common.h"
 
@@ -51,13 +51,34 @@ __device__ __forceinline__ float gelu_lut(float x, const float* __restrict__ T) 
 }
 
 
-// Host side (gemm.hip): lazily created per-device state and the kernel-selection rule shared by both launchers.
-constexpr int MAX_DEVICES = 64;
-int mudg_current_device();
+// Host side.  Tile heights of wgemm.hip: the 288-row tile (wgemm_kernel, wgemm_pkernel, wq_kernel<..., 9>) and the 160-row tile
+// (wq_kernel<..., 5>); what the GroupNorm partial blocks of a problem are cut to where one of them runs it.
+constexpr int WBM = 288, QBM = 160;
 const float* mudg_phi_table(bool split_ok = false);      // device Phi table, or nullptr (split-operand builds unless split_ok in bf16x3 / variant switch)
-// pgemm.hip: the persistent 128 x 128 kernel; wgs = workgroups per CU (4 | 3: one K-tile stage, 2: two)
-int mudg_pgemm_launch(const MudgGemmDesc& d, int vflags, int wgs, hipStream_t s);
-// wgemm.hip: the 288 x 320 eight-wave tile (16-bit builds); _ok = eligible AND selected by its M-independent rule
-bool mudg_wgemm_ok(const MudgGemmDesc& d, int vflags);
-int mudg_wgemm_rows(const MudgGemmDesc& d, int vflags);      // 288 | 160 (w160_kernel, 16-bit builds) | 0
-int mudg_wgemm_launch(const MudgGemmDesc& d, int vflags, hipStream_t s);
+
+// What mudg_gemm runs for a problem and every parameter of that launch: chosen once, by gemm_plan (gemm.hip).
+enum GemmKernel {
+    GK_GENERIC,          // gemm_kernel<G128, MODE, false, false>: the generic address path
+    GK_DOUBLE,           // gemm_kernel<G128, MODE, true, false>: descriptor loader, two K-tile stages
+    GK_SINGLE,           // gemm_kernel<G128, MODE, true, true>: one stage, four workgroups per CU (bf16x3: the fused-piece kernel)
+    GK_WIDE,             // gemm_kernel<G320 | G256, MODE, true, false> (16-bit builds)
+    GK_PERSIST,          // pgemm_kernel (pgemm.hip)
+    GK_W288,             // wgemm_kernel (wgemm.hip)
+    GK_W288P,            // wgemm_pkernel (16-bit builds)
+    GK_W288Q,            // wq_kernel<..., 9> (variant builds)
+    GK_H144,             // hgeglu_kernel (16-bit builds)
+    GK_W160,             // wq_kernel<..., 5> (16-bit builds)
+};
+struct GemmPlan {
+    GemmKernel kernel;
+    int vflags;          // VF_Y | VF_R | VF_TM | VF_XS
+    int rows;            // height of the GroupNorm partial blocks: 288 | 160 | 128
+    int ni;              // GK_WIDE: NI of the wide tile (5: 256 x 320, 4: 256 x 256)
+    int wgs;             // GK_PERSIST: workgroups per CU (4 | 3: one K-tile stage, 2: two)
+    int grid;            // GK_W288P: workgroups
+    int rs;              // GK_W160: the residual — 0 none, 1 seeds the accumulators, 2 deferred to the epilogue
+    bool pf;             // GK_H144: the prefetching K loop
+    int delay;           // GK_H144: the measurement knobs of hgeglu_kernel (variant switches GEMM_H144DELAY / ABL / PRIO)
+};
+int mudg_pgemm_launch(const MudgGemmDesc& d, const GemmPlan& plan, hipStream_t s);       // GK_PERSIST
+int mudg_wgemm_launch(const MudgGemmDesc& d, const GemmPlan& plan, hipStream_t s);       // GK_W288 ... GK_W160

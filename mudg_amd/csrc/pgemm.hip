@@ -581,33 +581,16 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
     }
 }
 
-int cu_count() {
-    static int cus[MAX_DEVICES] = {};
-    const int dev = mudg_current_device();
-    if (dev < 0) return 256;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return cus[dev];
-}
-
 // One workgroup per residency slot (WGS per CU), or one per tile when there are fewer tiles than slots.
 template <int MODE, bool GEGLU, int WGS, bool RS>
 int launch_p(const MudgGemmDesc& d, int vflags, hipStream_t s) {
-    static bool attr_done[MAX_DEVICES] = {};
-    const int dev = mudg_current_device();
-    if (dev < 0) MUDG_FAIL(MUDG_ELAUNCH, "gemm: no current device");
     constexpr int smem = pk_smem(WGS);
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pgemm_kernel<MODE, GEGLU, WGS, RS>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done[dev] = true;
-    }
+    if (const int rc = mudg_lds_opt_in<&pgemm_kernel<MODE, GEGLU, WGS, RS>>(smem, "gemm")) return rc;
     const int ntm = (d.M + 127) / 128, ntn = (d.N + 127) / 128;
     const int64_t total = (int64_t)ntm * ntn * d.batch;
     if (total >= ((int64_t)1 << 31)) MUDG_FAIL(MUDG_EINVAL, "gemm: %lld tiles", (long long)total);
-    const int64_t slots = (int64_t)cu_count() * (FUSEDP ? 2 : WGS);
+    const int cus = mudg_cu_count();
+    const int64_t slots = (int64_t)(cus > 0 ? cus : 256) * (FUSEDP ? 2 : WGS);
     const int grid = (int)(total < slots ? total : slots);
     const float* phi = GEGLU ? mudg_phi_table() : nullptr;
     hipLaunchKernelGGL((pgemm_kernel<MODE, GEGLU, WGS, RS>), dim3(grid), dim3(256), smem, s, d, vflags, phi, ntm, ntn);
@@ -622,15 +605,11 @@ int by_problem(const MudgGemmDesc& d, int vflags, hipStream_t s) {
 
 }  // namespace
 
-int mudg_pgemm_launch(const MudgGemmDesc& d, int vflags, int wgs, hipStream_t s) {
-    if (d.geglu && (d.mode != 0 || d.R || d.gbias || d.stats || d.act)) MUDG_FAIL(MUDG_EINVAL, "gemm: the persistent GEGLU kernel is bias-only");
-    if (d.R && (d.alpha != 1.f || d.act)) MUDG_FAIL(MUDG_EINVAL, "gemm: the persistent kernel seeds the accumulators with the residual (alpha 1, no activation)");
-    const bool rs = d.R || d.stats;
-    if (FUSEDP || d.Y8 || rs) wgs = wgs > 2 ? (rs && !FUSEDP && !d.Y8 ? 3 : 2) : 2;       // 64-KiB stage / the fused fp8 copy / seeds and partials
-    if (wgs >= 4) return by_problem<4, false>(d, vflags, s);
-    if (wgs == 3) return by_problem<3, true>(d, vflags, s);
-    return rs ? by_problem<2, true>(d, vflags, s) : by_problem<2, false>(d, vflags, s);
+int mudg_pgemm_launch(const MudgGemmDesc& d, const GemmPlan& plan, hipStream_t s) {
+    if (plan.wgs >= 4) return by_problem<4, false>(d, plan.vflags, s);
+    if (plan.wgs == 3) return by_problem<3, true>(d, plan.vflags, s);
+    return d.R || d.stats ? by_problem<2, true>(d, plan.vflags, s) : by_problem<2, false>(d, plan.vflags, s);
 }
 #else
-int mudg_pgemm_launch(const MudgGemmDesc&, int, int, hipStream_t) { MUDG_FAIL(MUDG_EINVAL, "gemm: no persistent kernel in this build"); }
+int mudg_pgemm_launch(const MudgGemmDesc&, const GemmPlan&, hipStream_t) { MUDG_FAIL(MUDG_EINVAL, "gemm: no persistent kernel in this build"); }
 #endif

@@ -41,7 +41,7 @@
 // 128 x 128 kernels' on every shape and epilogue the suite runs (tests/test_gemm_variants_gpu.py::
 // test_wide288_is_bit_identical_to_the_one_tile_kernels — an observation about v_mfma_f32_16x16x32 vs two v_mfma_f32_32x32x16 on gfx950,
 // asserted by that test, not a documented property of the instructions).  With a residual they are not — the sum is ((r + x w) + bias) here
-// and ((x w + bias) + r) there — and that alone is why the selection rule (mudg_wgemm_ok) never looks at M: a clip's result must not
+// and ((x w + bias) + r) there — and that alone is why the selection rule (gemm.hip, wgemm288_ok) never looks at M: a clip's result must not
 // depend on the batch it travels in, so whether a residual problem runs on this tile is decided by its per-frame geometry only.
 //
 // bf16x3 build (MUDG_PLANES = 2), same tile, same epilogue: a k half holds both bf16 pieces of both operands (x0, x1, w0, w1: 76 KiB),
@@ -64,7 +64,6 @@
 #if MUDG_PLANES <= 2
 namespace {
 
-constexpr int WBM = 288;
 constexpr int WNA = WBM / 16;                            // 16-row subtiles of the X operand tile
 constexpr int W_TAIL = 2 * 320 * 2 * 4;                  // epilogue hand-off of the GroupNorm partials between the two M halves (320-wide tile)
 constexpr int W_TAIL_GEGLU = (PHI_N + 4) * 8;            // the GEGLU tile (256 wide): the Phi table as (value, step to the next entry) pairs
@@ -164,7 +163,7 @@ template <int NREP> __device__ __forceinline__ int wave_single_col(int wc) { ret
 // in an epilogue that nothing overlaps on a CU holding one workgroup (the 294912 x 320 x 320 out-projection 178 -> 158 us, 73728 x 640 x 640
 // 102 -> 83, 18432 x 2560 x 1280 135 -> 121).  The
 // sum is ((r + x w) + bias) instead of ((x w + bias) + r): not the bits of the 128 x 128 one-tile kernels, so whether a problem with a
-// residual runs here never depends on M (mudg_wgemm_ok).
+// residual runs here never depends on M (gemm.hip, wgemm288_ok).
 template <int NREP, int NI>
 __device__ __forceinline__ void w_seed(const MudgGemmDesc& p, f32x4 (&acc)[NI][NREP], const int m0, const int n0, const int wr, const int wc, const int lane) {
     constexpr int NPAIR = NREP / 2;
@@ -1332,15 +1331,14 @@ __global__ __launch_bounds__(256, 2) void hgeglu_kernel(const MudgGemmDesc p, co
 //     fragments of k half h + 1  (5 W + 5 X reads into the other register set) | 25 MFMAs of k half h
 // Bits: the K order and the per-row arithmetic of every other contraction kernel; without a residual identical to the 128 x 128 kernels,
 // and with a 16-bit one too (it is added by the epilogue, after the bias: RS = 2 below); an fp32 residual seeds the accumulators as on the
-// 288-row tile — ((r + x w) + bias) — so the rule (mudg_wgemm_rows) looks at the frame geometry, never at M.
+// 288-row tile — ((r + x w) + bias) — so the rule (gemm.hip, w160_ok) looks at the frame geometry, never at M.
 // The same skeleton carries TWO tile heights (NI = 16-row fragments per wave and M half): NI = 5 — 160 rows, above — and, in the variant
-// builds only (GEMM_W288Q, a measurement: mudg_wgemm_launch), NI = 9 — 288 rows, the tile of wgemm_kernel on this loop: what took the 160-row
+// builds only (GEMM_W288Q, a measurement: gemm.hip, gemm_plan), NI = 9 — 288 rows, the tile of wgemm_kernel on this loop: what took the 160-row
 // loop from 1050 to 1290 TFLOP/s (fragment reads between the MFMAs, no branch in the steady state, one barrier per k half) applied to the
 // tile with 151 FLOP per staged byte — same bits, same speed as the six-phase loop (profiles/r6/w288q_shapes.txt).  At 180
 // accumulators there is no room for a second fragment set, so the fragments are refreshed IN PLACE: a row's X fragment is requested for
 // the next k half as soon as its five MFMAs are issued, a W fragment after its last use in the last row — each has at least five MFMAs
 // (plus the barrier and the DMA issue) to arrive.  Ring of FOUR k halves of 38 | 34 KiB (five pieces per wave).
-constexpr int QBM = 160;
 template <int NREP, int NI> struct QGeo {
     static constexpr int BM = 32 * NI;                   // 160 | 288
     static constexpr int NA = 2 * NI;                    // X subtiles of a k half
@@ -1705,124 +1703,12 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
 }
 #endif
 
-// Variant switch GEMM_W288 (debug-variants build; read at every call so that one process can compare kernels): 0 = never, 1 = the rule
-// below, 2 = every eligible problem.
-int variant() { return mudg_variant("GEMM_W288", 1); }
-
 }  // namespace
 
-#if MUDG_PLANES == 1
-static int persistent_grid(const MudgGemmDesc& d);
-// The half-height GEGLU kernel (hgeglu_kernel).  Variant switch GEMM_H144: 0 = never, 1 = the rule, 2 = every GEGLU problem the 288 x 256
-// tile is eligible for (the callers have checked wgemm_eligible: mode 0, N % 256 == 0, K % 64 == 0, 16-byte Y pieces, no residual / group
-// bias / partials).  Same bits as the kernels it replaces, so the rule may look at M.
-static bool half_height_ok(const MudgGemmDesc& d) {
-    const int hv = mudg_variant("GEMM_H144", 1);
-    if (!hv || !d.geglu) return false;
-    if (hv == 2) return true;
-    // Measured (MI355X; profiles/r6/h144*.txt, bench_h144_off / _rule.json): per launch x 0.90 ... 1.08 of the persistent 288 x 256 form in
-    // isolated timings (+ 3 ... 7 % at K = 320 on the level-0 rows and where the eight-wave tile has less than a round of tiles, - 5 ...
-    // - 10 % from K = 512: 92 instead of 136 FLOP per staged byte), and INSIDE the step — the same library, the same box, the rule "where
-    // it won in isolation" against never — 122.39 against 121.53 ms: the rocprofv3 trace of that step has its level-0 launches at 710 us
-    // where the persistent form's were 681.  The rule is therefore: never.  The kernel stays, tested (tests/test_gemm_variants_gpu.py
-    // runs the parity suites with it forced, test_half_height_geglu_kernel_is_bit_identical...), as the measured answer to "two
-    // workgroups per CU" (DESIGN §3.2).
-    return false;
-}
-#endif
-// What the kernel can run at all.
-static bool wgemm_eligible(const MudgGemmDesc& d, int vflags, int bm = WBM) {
-    if (d.batch != 1 || d.act || d.Y8 || d.subpixel || (d.mode == 1 && d.upsample)) return false;
-    if (d.geglu ? (d.mode != 0 || d.N % 256 != 0 || d.R || d.gbias || d.stats) : d.N % 320 != 0) return false;
-    if (!(vflags & VF_Y) || (d.R && !(vflags & VF_R))) return false;
-    const int cin = d.mode == 0 ? d.K : d.Cin;
-    if ((d.K & 63) || (cin & 63) || (d.csplit & 63)) return false;
-    if (d.mode == 1 && (d.stride != 1 || d.pad != 1 || d.Hin != d.Hout || d.Win != d.Wout || d.K != 9 * d.Cin)) return false;
-    if (d.mode == 2 && (d.korder || d.K != 3 * d.Cin)) return false;       // (korder 1 means tiles of 8 pixels x 16 frames to the callers: gemm.hip)
-    if (d.gbias && (d.rows_per_group % bm != 0)) return false;             // one group per tile: the group bias rides in the column constants
-    if (d.R && d.alpha != 1.f) return false;                               // the residual seeds the accumulators (w_seed)
-    if ((d.ldy & 7) || (d.R && (d.ldr & 7))) return false;                 // 8-byte pieces of the unpaired fragment
-    // 32-bit reach of the descriptor offsets
-    const int64_t ld = d.X2 && d.ldx2 > d.ldx ? d.ldx2 : d.ldx;
-    int64_t rows = bm + 16 + (PLANES > 1);                                 // (the second piece of a row: ld / 2 elements further)
-    if (d.mode == 1) rows += 2 * (int64_t)d.Win + 2;
-    if (d.mode == 2) rows += 2 * (int64_t)d.HW;
-    const int64_t lim = (int64_t)1 << 31;
-    return rows * ld * 2 + (int64_t)cin * 2 + 256 < lim && (int64_t)(320 + 16 + (PLANES > 1)) * d.ldw * 2 + (int64_t)d.K * 2 + 256 < lim;
-}
-
-// Where it is used.  The rule never looks at M (see the header): `S`, the rows of one frame (mode 0: the caller's hint in d.HW), must be
-// whole tiles — then every frame batch of the benchmarked resolution fills whole rounds of the 256 CUs.
-static bool wgemm288_ok(const MudgGemmDesc& d, int vflags) {
-    const int mode = variant();
-    if (!mode || !wgemm_eligible(d, vflags)) return false;
-    if (mode == 2) return true;
-#if MUDG_PLANES == 1
-    if (d.geglu && half_height_ok(d)) return true;         // (same bits as every other GEGLU kernel: no frame geometry needed)
-#endif
-    const int S = d.mode == 1 ? d.Hout * d.Wout : d.HW;
-    if (S <= 0 || S % WBM != 0) return false;
-    // Measured per shape against the 128 x 128 kernels (tools/exp_w288.py, profiles/r5/w288_shapes.txt; MI355X, frames of whole tiles):
-    // 3x3 convs + 20 ... + 40 %, temporal convs + 19 ... + 28 %; plain GEMMs + 16 ... + 37 % from K = 1280, + 1 ... + 26 % at K = 320 / 640
-    // (N <= K: every projection of the UNet; - 1 ... - 3 % for N = 2 ... 3 K with a residual, which the UNet does not have); GEGLU below.
-    // bf16x3 (same tool with MUDG_OPERAND=bf16x3, profiles/r5/w288_x3_shapes.txt; the 128 x 128 side is the fused-piece kernel, one-tile or
-    // persistent as gemm.hip selects): 3x3 convs + 27 ... + 44 %, temporal convs + 22 ... + 27 %, GEGLU + 11 ... + 13 %, plain GEMMs + 11 ...
-    // + 42 % down to K = 320: three times the MFMAs per staged byte and per epilogue — every problem whose frames are whole tiles.
-    if (d.mode != 0 || PLANES == 2) return true;
-#if MUDG_PLANES == 1
-    // GEGLU (bit-identical to the persistent 128 x 128 kernel it replaces, so M may decide): + 7 ... + 16 % in the persistent form (more
-    // tiles than CUs) at every K; the one-tile form + 11 % at K = 1280, - 1 % at K = 640, - 5 ... - 12 % at K = 320.  Since round 6 the
-    // two-workgroup half-height kernel (hgeglu_kernel) runs GEGLU wherever its rule says so (half_height_ok).
-    if (d.geglu && d.K < 640) return persistent_grid(d) > 0;
-#endif
-    return true;
-}
-
-#if MUDG_PLANES == 1
-// The 160-row tile (w160_kernel): frames of whole 160-row tiles that are not whole 288-row tiles.  Variant switch GEMM_W160: 0 = never,
-// 1 = the rule, 2 = every eligible problem (as GEMM_W288 = 2; the 288-row tile's own rule is asked first).
-static bool w160_ok(const MudgGemmDesc& d, int vflags) {
-    const int mode = mudg_variant("GEMM_W160", 1);
-    if (!mode || !wgemm_eligible(d, vflags, QBM)) return false;
-    if (mode == 2) return true;
-    const int S = d.mode == 1 ? d.Hout * d.Wout : d.HW;
-    if (S <= 0 || S % QBM != 0) return false;
-    // Measured per shape against the 128 x 128 kernels, twice.  In isolation (tools/exp_w160.py, profiles/r6/w160_shapes.txt; MI355X, MDM512's
-    // frame batches, every operand hot in the 256-MiB Infinity Cache after the first repeat): 3x3 convs + 28 ... + 45 %, temporal convs + 14 ...
-    // + 27 % at 2560- and 640-pixel frames; plain GEMMs + 13 ... + 35 % from K = 640 with N <= K, + 0 ... + 9 % for N = 2 ... 3 K, at K = 320
-    // + 7 ... + 14 % without and - 2 ... - 3 % with a residual; GEGLU - 9 ... - 22 % against the persistent 128 x 128 kernel.  And INSIDE
-    // the step (tools/shape_profile.py 512 with GEMM_W160 = 0 / 1 / 2, profiles/r6/shapes_m512_w160_*.md), where a kernel's operands come
-    // from HBM or from its producer: convs + 12 ... + 27 %, temporal convs + 5 ... + 14 %, plain GEMMs + 11 ... + 16 % at K >= 1280 — and
-    // - 3 ... - 13 % at K = 320 / 640, where the one workgroup of a CU waits for its first k half alone while the 128 x 128 kernels have
-    // four workgroups per CU to cover for each other (the isolated timing hides it: its operands never leave the cache).  The rule follows
-    // the step.  One workgroup per CU wants a frame batch to bring enough tiles: the 160-pixel level (32 frames = 32 tile rows x 4 ... 8
-    // columns: half the CUs) stays on the 128 x 128 kernels (- 20 ... - 45 % there).  Never M: S, K, the mode.
-    if (S < 640 || d.geglu) return false;
-    if (d.mode != 0) return true;
-    return d.K >= 1280;
-}
-#endif
-// Height of the tile that will run the problem: 288, 160 or 0 (none of the kernels of this file).
-int mudg_wgemm_rows(const MudgGemmDesc& d, int vflags) {
-    if (wgemm288_ok(d, vflags)) return WBM;
-#if MUDG_PLANES == 1
-    if (w160_ok(d, vflags)) return QBM;
-#endif
-    return 0;
-}
-bool mudg_wgemm_ok(const MudgGemmDesc& d, int vflags) { return mudg_wgemm_rows(d, vflags) != 0; }
-
 template <int MODE, int NREP, bool GEGLU>
-static int wgemm_launch_one(const MudgGemmDesc& d, int vflags, hipStream_t s, int slot) {
-    static bool attr_done[MAX_DEVICES][4] = {};
-    const int dev = mudg_current_device();
-    if (dev < 0) MUDG_FAIL(MUDG_ELAUNCH, "gemm: no current device");
+static int wgemm_launch_one(const MudgGemmDesc& d, int vflags, hipStream_t s) {
     using G = WGeo<NREP>;
-    if (!attr_done[dev][slot]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgemm_kernel<MODE, NREP, GEGLU>), hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM);
-        if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done[dev][slot] = true;
-    }
+    if (const int rc = mudg_lds_opt_in<&wgemm_kernel<MODE, NREP, GEGLU>>(G::SMEM, "gemm")) return rc;
     const int tiles = ((d.M + WBM - 1) / WBM) * (d.N / G::BN);
     const float* phi = GEGLU ? mudg_phi_table(PLANES == 2) : nullptr;
     hipLaunchKernelGGL((wgemm_kernel<MODE, NREP, GEGLU>), dim3(tiles), dim3(512), G::SMEM, s, d, vflags, phi);
@@ -1830,72 +1716,23 @@ static int wgemm_launch_one(const MudgGemmDesc& d, int vflags, hipStream_t s, in
 }
 
 #if MUDG_PLANES == 1
-// The persistent form (wgemm_pkernel): whole tiles, at least two K-tiles, more tiles than CUs.  Same bits as the one-tile form, so M may
-// decide.  Measured (same box, tools/exp_w288.py with MUDG_GEMM_W288P = 0 / 2, profiles/r5/w288_persistent.txt): GEGLU + 2 ... + 9 % (its
-// epilogue is the longest and fetches nothing); plain GEMMs - 7 ... + 6 % with no pattern worth a rule — a residual's fetches queue
-// behind the next tile's staged pieces, and what persistence saves per tile (launch, first-fetch latency) is small beside what bounds
-// the short-K problems (the epilogue's own traffic).  Variant switch GEMM_W288P: 0 = never, 1 = GEGLU only (the rule), 2 = every
-// problem the kernel can run.
 template <int NREP, bool GEGLU>
-static int wgemm_launch_persistent(const MudgGemmDesc& d, int vflags, hipStream_t s, int slot, int grid) {
-    static bool attr_done[MAX_DEVICES][2] = {};
-    const int dev = mudg_current_device();
+static int wgemm_launch_persistent(const MudgGemmDesc& d, int vflags, hipStream_t s, int grid) {
     using G = WGeo<NREP>;
-    if (!attr_done[dev][slot]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgemm_pkernel<NREP, GEGLU>), hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM);
-        if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done[dev][slot] = true;
-    }
+    if (const int rc = mudg_lds_opt_in<&wgemm_pkernel<NREP, GEGLU>>(G::SMEM, "gemm")) return rc;
     const int tiles = (d.M / WBM) * (d.N / G::BN);
     const float* phi = GEGLU ? mudg_phi_table(PLANES == 2) : nullptr;
     hipLaunchKernelGGL((wgemm_pkernel<NREP, GEGLU>), dim3(grid), dim3(512), G::SMEM, s, d, vflags, phi, tiles);
     return mudg_check_launch("mudg_gemm");
 }
-static int persistent_grid(const MudgGemmDesc& d) {
-    static int cus[MAX_DEVICES] = {};
-    const int pv = mudg_variant("GEMM_W288P", 1);
-    if (!pv || (pv == 1 && !d.geglu) || d.mode != 0 || d.R || d.M % WBM != 0 || d.K < 2 * BK) return 0;
-    {   // the whole problem behind one descriptor per operand: rows ride in 32-bit scalar offsets
-        const int64_t ld = d.X2 && d.ldx2 > d.ldx ? d.ldx2 : d.ldx, lim = (int64_t)1 << 31;
-        if (((int64_t)d.M + 16) * ld * 2 + (int64_t)d.K * 2 + 256 >= lim || ((int64_t)d.N + 16) * d.ldw * 2 + (int64_t)d.K * 2 + 256 >= lim) return 0;
-    }
-    const int dev = mudg_current_device();
-    if (dev < 0) return 0;
-    if (!cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 8;
-        cus[dev] = n & ~7;                                   // whole XCDs' worth of workgroups
-    }
-    const int tiles = (d.M / WBM) * (d.N / (d.geglu ? 256 : 320));
-    return tiles > cus[dev] ? cus[dev] : 0;
-}
-#endif
 
-#if MUDG_PLANES == 1
 template <bool PF>
-static int hgeglu_launch_one(const MudgGemmDesc& d, int vflags, hipStream_t s) {
-    static bool attr_done[MAX_DEVICES] = {};
-    const int dev = mudg_current_device();
-    if (dev < 0) MUDG_FAIL(MUDG_ELAUNCH, "gemm: no current device");
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hgeglu_kernel<PF>), hipFuncAttributeMaxDynamicSharedMemorySize, H_SMEM);
-        if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done[dev] = true;
-    }
+static int hgeglu_launch(const MudgGemmDesc& d, int vflags, int delay, hipStream_t s) {
+    if (const int rc = mudg_lds_opt_in<&hgeglu_kernel<PF>>(H_SMEM, "gemm")) return rc;
     const int tiles = ((d.M + 16 * H_NA - 1) / (16 * H_NA)) * (d.N / 256);
-    static int cus[MAX_DEVICES] = {};
-    if (!cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-        cus[dev] = n;
-    }
-    const int delay = mudg_variant("GEMM_H144DELAY", 0) | (mudg_variant("GEMM_H144ABL", 0) << 16) | (mudg_variant("GEMM_H144PRIO", 1) ? 0 : 1 << 20);
-    hipLaunchKernelGGL(hgeglu_kernel<PF>, dim3(tiles), dim3(256), H_SMEM, s, d, vflags, mudg_phi_table(false), 2 * cus[dev], delay);
+    const int cus = mudg_cu_count();
+    hipLaunchKernelGGL(hgeglu_kernel<PF>, dim3(tiles), dim3(256), H_SMEM, s, d, vflags, mudg_phi_table(false), 2 * (cus < 8 ? 256 : cus), delay);
     return mudg_check_launch("mudg_gemm");
-}
-// Variant switch GEMM_H144PF (measurements): 0 = the plain loop (every k half starts with its own fragment reads), 1 = the prefetching loop.
-static int hgeglu_launch(const MudgGemmDesc& d, int vflags, hipStream_t s) {
-    return mudg_variant("GEMM_H144PF", 1) ? hgeglu_launch_one<true>(d, vflags, s) : hgeglu_launch_one<false>(d, vflags, s);
 }
 #endif
 
@@ -1908,59 +1745,53 @@ extern "C" int mudg_debug_set_stamps(void* buf) {
 
 #if MUDG_PLANES == 1
 template <int MODE, int NREP, bool GEGLU, int RS, int NI>
-static int wq_launch_one(const MudgGemmDesc& d, int vflags, hipStream_t s, int slot) {
-    static bool attr_done[MAX_DEVICES][20] = {};
-    const int dev = mudg_current_device();
-    if (dev < 0) MUDG_FAIL(MUDG_ELAUNCH, "gemm: no current device");
+static int wq_launch_one(const MudgGemmDesc& d, int vflags, hipStream_t s) {
     using G = QGeo<NREP, NI>;
-    if (!attr_done[dev][slot]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wq_kernel<MODE, NREP, GEGLU, RS, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM);
-        if (e != hipSuccess) MUDG_FAIL(MUDG_ELAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_done[dev][slot] = true;
-    }
+    if (const int rc = mudg_lds_opt_in<&wq_kernel<MODE, NREP, GEGLU, RS, NI>>(G::SMEM, "gemm")) return rc;
     const int tiles = ((d.M + G::BM - 1) / G::BM) * (d.N / G::BN);
     const float* phi = GEGLU ? mudg_phi_table(false) : nullptr;
     hipLaunchKernelGGL((wq_kernel<MODE, NREP, GEGLU, RS, NI>), dim3(tiles), dim3(512), G::SMEM, s, d, vflags, phi);
     return mudg_check_launch("mudg_gemm");
 }
+
+// The 160-row tile for each mode and residual form (GemmPlan::rs).
+template <int RS>
+static int w160_launch(const MudgGemmDesc& d, int vflags, hipStream_t s) {
+    if (d.mode == 0) return wq_launch_one<0, 5, false, RS, 5>(d, vflags, s);
+    if (d.mode == 1) return wq_launch_one<1, 5, false, RS, 5>(d, vflags, s);
+    return wq_launch_one<2, 5, false, RS, 5>(d, vflags, s);
+}
 #endif
 
-int mudg_wgemm_launch(const MudgGemmDesc& d, int vflags, hipStream_t s) {
+// The kernel gemm_plan (gemm.hip) chose, for the problem's GEGLU flag and mode.
+int mudg_wgemm_launch(const MudgGemmDesc& d, const GemmPlan& plan, hipStream_t s) {
+    const int vflags = plan.vflags;
+    switch (plan.kernel) {
+    case GK_W288:
+        if (d.geglu) return wgemm_launch_one<0, 4, true>(d, vflags, s);
+        if (d.mode == 0) return wgemm_launch_one<0, 5, false>(d, vflags, s);
+        if (d.mode == 1) return wgemm_launch_one<1, 5, false>(d, vflags, s);
+        return wgemm_launch_one<2, 5, false>(d, vflags, s);
 #if MUDG_PLANES == 1
-    const int rows = mudg_wgemm_rows(d, vflags);
-    if (rows == QBM) {
-        if (d.geglu) return wq_launch_one<0, 4, true, 0, 5>(d, vflags, s, 6);
-        // a residual of 16-bit storage (the fp16 stream, an operand matrix) is deferred to the epilogue, an fp32 one seeds the accumulators.
-        // Variant switch GEMM_W160DEFER = 0: every residual seeds.
-        const int rs = !d.R ? 0 : ((d.res_fp32 != KIND_F32 && mudg_variant("GEMM_W160DEFER", 1)) ? 2 : 1);
-        if (d.mode == 0) return rs == 0 ? wq_launch_one<0, 5, false, 0, 5>(d, vflags, s, 0) : (rs == 1 ? wq_launch_one<0, 5, false, 1, 5>(d, vflags, s, 1) : wq_launch_one<0, 5, false, 2, 5>(d, vflags, s, 14));
-        if (d.mode == 1) return rs == 0 ? wq_launch_one<1, 5, false, 0, 5>(d, vflags, s, 2) : (rs == 1 ? wq_launch_one<1, 5, false, 1, 5>(d, vflags, s, 3) : wq_launch_one<1, 5, false, 2, 5>(d, vflags, s, 15));
-        return rs == 0 ? wq_launch_one<2, 5, false, 0, 5>(d, vflags, s, 4) : (rs == 1 ? wq_launch_one<2, 5, false, 1, 5>(d, vflags, s, 5) : wq_launch_one<2, 5, false, 2, 5>(d, vflags, s, 16));
-    }
+    case GK_W288P:
+        return d.geglu ? wgemm_launch_persistent<4, true>(d, vflags, s, plan.grid) : wgemm_launch_persistent<5, false>(d, vflags, s, plan.grid);
+    case GK_H144:
+        return plan.pf ? hgeglu_launch<true>(d, vflags, plan.delay, s) : hgeglu_launch<false>(d, vflags, plan.delay, s);
+    case GK_W160:
+        if (d.geglu) return wq_launch_one<0, 4, true, 0, 5>(d, vflags, s);
+        return plan.rs == 0 ? w160_launch<0>(d, vflags, s) : (plan.rs == 1 ? w160_launch<1>(d, vflags, s) : w160_launch<2>(d, vflags, s));
 #ifdef MUDG_DEBUG_VARIANTS
-    // The 288-row tile on the loop of the 160-row one (wq_kernel<..., 9>), variant builds only.  Variant switch GEMM_W288Q: 0 = never (the
-    // rule: wgemm_kernel's six-phase loop), 2 = every one-tile problem of the 288-row tile (GEGLU included).  Measured per shape against the
-    // six-phase loop (tools/exp_w288.py q, profiles/r6/w288q_shapes.txt): 3x3 convs x 0.96 ... 1.04, temporal convs x 1.00 ... 1.02, plain
-    // GEMMs x 0.85 ... 1.07, GEGLU (one-tile against the persistent six-phase form) x 0.90 ... 0.98 — the same bits and no gain: two
-    // different schedules of the same 45 MFMAs, 14 fragment reads and 38 DMA pieces per k half end at the same 1300 - 1430 TFLOP/s.
-    if (mudg_variant("GEMM_W288P", 1) != 2 && mudg_variant("GEMM_W288Q", 0) == 2) {
-        if (d.geglu) return wq_launch_one<0, 4, true, 0, 9>(d, vflags, s, 13);
-        if (d.mode == 0) return d.R ? wq_launch_one<0, 5, false, 1, 9>(d, vflags, s, 7) : wq_launch_one<0, 5, false, 0, 9>(d, vflags, s, 8);
-        if (d.mode == 1) return d.R ? wq_launch_one<1, 5, false, 1, 9>(d, vflags, s, 9) : wq_launch_one<1, 5, false, 0, 9>(d, vflags, s, 10);
-        return d.R ? wq_launch_one<2, 5, false, 1, 9>(d, vflags, s, 11) : wq_launch_one<2, 5, false, 0, 9>(d, vflags, s, 12);
+    case GK_W288Q:
+        if (d.geglu) return wq_launch_one<0, 4, true, 0, 9>(d, vflags, s);
+        if (d.mode == 0) return d.R ? wq_launch_one<0, 5, false, 1, 9>(d, vflags, s) : wq_launch_one<0, 5, false, 0, 9>(d, vflags, s);
+        if (d.mode == 1) return d.R ? wq_launch_one<1, 5, false, 1, 9>(d, vflags, s) : wq_launch_one<1, 5, false, 0, 9>(d, vflags, s);
+        return d.R ? wq_launch_one<2, 5, false, 1, 9>(d, vflags, s) : wq_launch_one<2, 5, false, 0, 9>(d, vflags, s);
+#endif
+#endif
+    default:
+        MUDG_FAIL(MUDG_EINVAL, "gemm: kernel %d is not in this build", (int)plan.kernel);
     }
-#endif
-    if (d.geglu && half_height_ok(d)) return hgeglu_launch(d, vflags, s);
-    if (const int grid = persistent_grid(d))
-        return d.geglu ? wgemm_launch_persistent<4, true>(d, vflags, s, 1, grid) : wgemm_launch_persistent<5, false>(d, vflags, s, 0, grid);
-#endif
-    if (d.geglu) return wgemm_launch_one<0, 4, true>(d, vflags, s, 3);
-    if (d.mode == 0) return wgemm_launch_one<0, 5, false>(d, vflags, s, 0);
-    if (d.mode == 1) return wgemm_launch_one<1, 5, false>(d, vflags, s, 1);
-    return wgemm_launch_one<2, 5, false>(d, vflags, s, 2);
 }
 #else
-bool mudg_wgemm_ok(const MudgGemmDesc&, int) { return false; }
-int mudg_wgemm_rows(const MudgGemmDesc&, int) { return 0; }
-int mudg_wgemm_launch(const MudgGemmDesc&, int, hipStream_t) { MUDG_FAIL(MUDG_EINVAL, "gemm: no 288 x 320 kernel in this build"); }
+int mudg_wgemm_launch(const MudgGemmDesc&, const GemmPlan&, hipStream_t) { MUDG_FAIL(MUDG_EINVAL, "gemm: no 288 x 320 kernel in this build"); }
 #endif

@@ -954,7 +954,7 @@ def test_wide288_is_bit_identical_to_the_one_tile_kernels(cuda):
             assert torch.equal(a, b) and torch.equal(getattr(a, ops.GN_ATTR, torch.zeros(1)), getattr(b, ops.GN_ATTR, torch.zeros(1)))
 
 
-# ---------------------------------------------------------------------------------------------- the 160 x 320 tile (csrc/wgemm.hip: w160_kernel)
+# ---------------------------------------------------------------------------------------------- the 160 x 320 tile (csrc/wgemm.hip: wq_kernel<..., 5>)
 def _w160_build():
     return _hip.planes() == 1            # 16-bit builds only
 

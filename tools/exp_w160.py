@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The 160-row tile kernel (csrc/wgemm.hip: w160_kernel) against the 128 x 128 kernels on the same inputs: parity of results and GroupNorm
+"""The 160-row tile kernel (csrc/wgemm.hip: wq_kernel<..., 5>) against the 128 x 128 kernels on the same inputs: parity of results and GroupNorm
 partials on small problems of every mode / epilogue, then per-shape timings of the MDM512 shapes (BASELINE configs[1]) with either kernel.
     MUDG_DEBUG_VARIANTS=1 python tools/exp_w160.py [parity|time|all]"""
 import os, sys

@@ -40,7 +40,7 @@ ap.add_argument("--launches", type=int, default=2000, help="tile launches to rea
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--repeat", type=int, default=3)
 ap.add_argument("--no-poison", action="store_true")
-ap.add_argument("--tile", type=int, default=288, choices=(288, 160), help="288: wgemm_kernel / wgemm_pkernel; 160: w160_kernel (16-bit builds)")
+ap.add_argument("--tile", type=int, default=288, choices=(288, 160), help="288: wgemm_kernel / wgemm_pkernel; 160: wq_kernel<..., 5> (16-bit builds)")
 args = ap.parse_args()
 
 CANARY = 0x5A5B
