@@ -285,6 +285,22 @@ int mudg_ddim_step(const float* x, const float* e_c, const float* e_u, const flo
 int mudg_gaussian_sample(const float* moments, const float* noise, float* out, int N, int C, int HW, float scale,
                          void* stream);
 
+/* ------------------------------------------------------------------ training from a data batch (ddpm3d.py:1064-1149)
+ * posterior_assemble: the posterior samples of the three VAE encodes of get_batch_input in one launch, written in the layout
+ *   the UNet takes.  mom_* (B*T, 2C, HW) fp32 moments of the dense / sparse colour / sparse depth frames, frame n = b*T + t;
+ *   noise_* (B*T, C, HW), all three or none (NULL = posterior mode); the arithmetic of mudg_gaussian_sample, bit for bit:
+ *   z (B, C, T, HW) = sample(mom_x);  c_concat (B, 2C, T, HW) = [sample(mom_sparse) | sample(mom_depth)] along the channels.
+ * cond_dropout: classifier-free-guidance dropout from the device vector r (B uniform draws), thresholds p, p2 = 2p, p3 = 3p
+ *   rounded to fp32 by the caller:  prompt_out (B, LD) = r < p2 ? null_prompt (LD) : cond_emb (B, LD);
+ *   img_out (B, C, HW) = (1 - (r >= p)(r < p3)) * img, img read at img + b*img_bstride + c*img_cstride (floats): the key frame
+ *   of a (B, C, T, HW) clip is read in place. */
+int mudg_posterior_assemble(const float* mom_x, const float* mom_sparse, const float* mom_depth, const float* noise_x,
+                            const float* noise_sparse, const float* noise_depth, float* z, float* c_concat, int B, int T, int C,
+                            int64_t HW, float scale, void* stream);
+int mudg_cond_dropout(const float* r, float p, float p2, float p3, const float* cond_emb, const float* null_prompt,
+                      float* prompt_out, int B, int64_t LD, const float* img, int64_t img_bstride, int64_t img_cstride,
+                      float* img_out, int C, int64_t HW, void* stream);
+
 /* ------------------------------------------------------------------ post-processing of decoded frames
  * (virtual_render/eval_tools.py: byte / integer work, results bit-equal to the reference's)
  * frames_to_u8:     out[b][t][p][c] = (uint8) trunc((clamp(v[b][c][t][p], -1, 1) + 1) / 2 * 255)      eval_tools.py:22-27

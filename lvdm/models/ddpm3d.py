@@ -203,12 +203,24 @@ class DDPM(nn.Module):
         return step.AdamW(params, lr=getattr(self, "learning_rate", 1e-4))
 
     def training_step(self, batch, batch_idx=0):
-        """`batch` = dict(x_start=latents (B, 4, T, H, W), cond={c_crossattn, c_concat}, t=(B,) long, + apply_model kwargs):
-        the tensors the reference's shared_step / get_batch_input hand to p_losses (the Waymo data pipeline that makes them is
-        outside the hot path).  Returns the loss; call .backward() and the optimizer as Lightning would."""
+        """A batch that carries `x_start` = dict(x_start=latents (B, 4, T, H, W), cond={c_crossattn, c_concat}, t=(B,) long,
+        + apply_model kwargs) — the tensors the reference's shared_step / get_batch_input hand to p_losses — goes straight to
+        p_losses.  Any other batch is a DATA batch (pixels, caption, class label, frame rate) and takes the reference's own route
+        (ddpm3d.py:790-802): shared_step(batch, random_uncond=self.classifier_free_guidance).  Returns the loss; call .backward() and
+        the optimizer as Lightning would."""
+        if "x_start" not in batch:
+            loss, _ = self.shared_step(batch, random_uncond=getattr(self, "classifier_free_guidance", False))
+            return loss
         kw = {k: v for k, v in batch.items() if k not in ("x_start", "cond", "t", "noise")}
         loss, _ = self.p_losses(batch["x_start"], batch["cond"], batch["t"], noise=batch.get("noise"), **kw)
         return loss
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0):
+        """shared_step without a graph; returns the loss_dict (there are no EMA weights to evaluate a second time: use_ema is
+        rejected by the constructor)."""
+        _, loss_dict = self.shared_step(batch)
+        return loss_dict
 
     def forward(self, x, c, **kwargs):
         """The training entry (ddpm3d.py:711-715): draw one timestep per sample, apply the dynamic rescale of the latents when the
@@ -219,9 +231,9 @@ class DDPM(nn.Module):
             x = x * extract_into_tensor(self.scale_arr.to(x.device), t, x.shape)
         return self.p_losses(x, c, t, **kwargs)
 
-    def shared_step(self, batch, **kwargs):
-        raise NotImplementedError("get_batch_input (VAE-encoding Waymo items, CLIP towers, random conditioning dropout) is the data "
-                                  "pipeline of the reference, outside the hot path: call p_losses / training_step with latents")
+    def shared_step(self, batch, random_uncond=None, **kwargs):
+        raise NotImplementedError("shared_step from a data batch (VAE-encoding the frames, CLIP towers, random conditioning dropout) is "
+                                  "built for LatentVisualDiffusion only (get_batch_input): call p_losses / training_step with latents")
 
 
 class LatentDiffusion(DDPM):
@@ -375,3 +387,134 @@ class LatentVisualDiffusion(LatentDiffusion):
         self.image_proj_model = instantiate_from_config(image_proj_stage_config)
         if not image_proj_model_trainable:
             self.image_proj_model = self._freeze(self.image_proj_model)
+
+    # ---- training from a data batch (reference ddpm3d.py:1056-1149): everything under it already runs on HIP; this joins it
+    def _batch_keys(self, with_fs=True):
+        keys = [self.first_stage_key, "sparse_frames", "sparse_depth", "class_label", self.cond_stage_key]
+        if with_fs:
+            keys.append("frame_stride" if self.fps_condition_type == "fs" else "fps")
+        return keys
+
+    def _require_batch(self, batch, keys):
+        missing = [k for k in keys if k not in batch]
+        if missing:
+            raise NotImplementedError(f"the batch lacks the data entries {missing}: a data batch carries {self._batch_keys()} "
+                                      "(making them from Waymo items is the dataset's work, not built here); latents go to "
+                                      "p_losses / training_step(dict(x_start=..., cond=..., t=...))")
+
+    @staticmethod
+    def get_input(batch, k):
+        return batch[k].to(memory_format=torch.contiguous_format).float()
+
+    def _uncond_draw(self, n, device):
+        """The one random draw of the conditioning dropout (ddpm3d.py:1084): B uniforms made ON the device, where they stay."""
+        return torch.rand(n, device=device)
+
+    @torch.no_grad()
+    def _encode_streams(self, x, sparse_x, sparse_depth):
+        """The three encode_first_stage calls of get_batch_input as one: the frames of all streams go through the encoder as one
+        frame batch, the posterior noise is drawn on the CPU generator in the reference's order (dense, sparse colour, sparse depth;
+        frame by frame when perframe_ae), and one launch samples all three posteriors straight into z (B, 4, T, h, w) and
+        c_concat (B, 8, T, h, w) = [sparse_z | sparse_depth_z]."""
+        from mudg_amd import ops
+        from mudg_amd.engine import vae
+        if x.dim() != 5 or x.shape != sparse_x.shape or x.shape != sparse_depth.shape:
+            raise ValueError(f"get_batch_input: the three streams must be (B, 3, T, H, W) clips of one shape, got {tuple(x.shape)}, "
+                             f"{tuple(sparse_x.shape)}, {tuple(sparse_depth.shape)}")
+        b, t = x.shape[0], x.shape[2]
+        moments = vae.encode_moments(self.first_stage_model, [x, sparse_x, sparse_depth])
+        n, c2, hh, ww = moments[0].shape
+        if self.perframe_ae:
+            noise = torch.cat([torch.randn((1, c2 // 2, hh, ww)) for _ in range(3 * n)], 0)
+        else:
+            noise = torch.cat([torch.randn((n, c2 // 2, hh, ww)) for _ in range(3)], 0)
+        # the one host-to-device transfer of get_batch_input: from page-locked memory and asynchronous, so the host does not wait
+        noise = noise.reshape(3, n, c2 // 2, hh, ww).pin_memory().to(x.device, non_blocking=True)
+        return ops.posterior_assemble(*moments, noise, b, t, float(self.scale_factor))
+
+    @torch.no_grad()
+    def _cond_dropout(self, random_num, cond_emb, null_prompt, sparse_x, frame):
+        """prompt_mask / input_mask of ddpm3d.py:1087-1100 applied in one launch: (prompt rows, the image the tower sees)."""
+        from mudg_amd import ops
+        return ops.cond_dropout(random_num, self.uncond_prob, cond_emb.detach(), null_prompt, sparse_x, frame)
+
+    def get_batch_input(self, batch, random_uncond, return_first_stage_outputs=False, return_original_cond=False,
+                        return_fs=False, return_cond_frame=False, return_original_input=False, return_sparse_input=False,
+                        return_class_label=False, **kwargs):
+        """A data batch -> [z, sparse_z, cond, (xrec), (cond_input), (fs), (cond_frame), (x), (sparse_x), (class_label)] as the
+        reference's method of the same name.  With random_uncond the text / both / the key-frame image are dropped for
+        r < p / p <= r < 2p / 2p <= r < 3p (p = uncond_prob); the draw and the masks never leave the device.  `sparse_z` is the
+        view c_concat[:, :4] of the assembled conditioning."""
+        self._require_batch(batch, self._batch_keys(with_fs=return_fs))
+        x = self.get_input(batch, self.first_stage_key)
+        sparse_x = self.get_input(batch, "sparse_frames")
+        class_label = self.get_input(batch, "class_label")
+        sparse_depth = self.get_input(batch, "sparse_depth")
+        if self.encoder_type != "2d":
+            raise NotImplementedError("encoder_type '3d' is not on the MuDG path")
+
+        z, latent_cond = self._encode_streams(x, sparse_x, sparse_depth)
+        sparse_z = latent_cond[:, :z.shape[1]]
+
+        cond_input = batch[self.cond_stage_key]
+        with torch.set_grad_enabled(torch.is_grad_enabled() and self.cond_stage_trainable):
+            if isinstance(cond_input, (dict, list)):
+                cond_emb = self.get_learned_conditioning(cond_input)
+            else:
+                cond_emb = self.get_learned_conditioning(cond_input.to(self.device))
+            null_prompt = self.get_learned_conditioning([""])
+        if random_uncond:
+            random_num = self._uncond_draw(x.size(0), x.device)
+        else:
+            random_num = torch.ones(x.size(0), device=x.device)         # nothing dropped: full text and image conditioning
+
+        cond_frame_index = 0
+        if self.rand_cond_frame:
+            assert self.rand_cond_frame is False, "random condition frame is not supported"
+        prompt_imb, img = self._cond_dropout(random_num, cond_emb, null_prompt, sparse_x, cond_frame_index)
+        with torch.no_grad():
+            img_emb = self.embedder(img)                                    # b l c
+        with torch.set_grad_enabled(torch.is_grad_enabled() and self.image_proj_model_trainable):
+            img_emb = self.image_proj_model(img_emb)
+
+        cond = {}
+        if self.model.conditioning_key == "hybrid":
+            if self.interp_mode:
+                # starting frame + (L - 2 empty frames) + ending frame
+                img_cat_cond = torch.zeros_like(z)
+                img_cat_cond[:, :, 0] = z[:, :, 0]
+                img_cat_cond[:, :, -1] = z[:, :, -1]
+            else:
+                img_cat_cond = latent_cond
+            cond["c_concat"] = [img_cat_cond]                               # b c t h w
+        cond["c_crossattn"] = [torch.cat([prompt_imb, img_emb], dim=1)]     # along the sequence
+
+        out = [z, sparse_z, cond]
+        if return_first_stage_outputs:
+            out.append(self.decode_first_stage(z))
+        if return_original_cond:
+            out.append(cond_input)
+        if return_fs:
+            out.append(self.get_input(batch, "frame_stride" if self.fps_condition_type == "fs" else "fps"))
+        if return_cond_frame:
+            out.append(x[:, :, cond_frame_index, ...].unsqueeze(2))
+        if return_original_input:
+            out.append(x)
+        if return_sparse_input:
+            out.append(sparse_x)
+        if return_class_label:
+            out.append(class_label)
+        return out
+
+    def shared_step(self, batch, random_uncond=None, **kwargs):
+        """ddpm3d.py:1056-1062: get_batch_input, then forward() (random t, dynamic rescale, p_losses) with fs / sparse_x /
+        class_label among the keyword arguments.  random_uncond None = self.classifier_free_guidance.  Returns (loss, loss_dict)."""
+        if random_uncond is None:
+            random_uncond = self.classifier_free_guidance
+        x, sparse_x, c, fs, class_label = self.get_batch_input(batch, random_uncond=random_uncond, return_fs=True,
+                                                               return_class_label=True)
+        kwargs.update({"fs": fs.long()})
+        kwargs.update({"sparse_x": sparse_x})
+        kwargs.update({"class_label": class_label})
+        return self(x, c, **kwargs)
+

@@ -111,27 +111,59 @@ def encoder_rows(enc, x, frames, h, w):
     return _conv3x3(enc.conv_out, x, frames, h, w), h, w
 
 
+def _load_frames(x, a, b, rows, hw):
+    """Frames [a, b) of one stream into the first (b - a) * hw rows of `rows`.  A (N, 3, H, W) stream is a batch of one-frame
+    clips; a (B, 3, T, H, W) stream is read in place, frame b T + t, one frame window per clip (no permuted copy of the pixels)."""
+    if x.dim() == 4:
+        ops.ncthw_to_rows(x[a:b].unsqueeze(2), rows, 0)
+        return
+    t = x.shape[2]
+    done = 0
+    while a < b:
+        clip, t0 = divmod(a, t)
+        nt = min(t - t0, b - a)
+        ops.ncthw_to_rows(x[clip:clip + 1], rows[done * hw:(done + nt) * hw], 0, t0=t0, frames=nt)
+        a, done = a + nt, done + nt
+
+
 @torch.no_grad()
 def encode_moments(ae, x, max_frames=8):
     """AutoencoderKL.encode up to the posterior parameters: x (N, 3, H, W) -> moments (N, 2*embed, H/8, W/8) fp32
-    (encoder + 1x1 quant_conv).  Frames are independent and processed in batches."""
-    x = _check(x).contiguous()
-    n, c, h, w = x.shape
+    (encoder + 1x1 quant_conv).  Frames are independent and processed in batches of `max_frames`.
+
+    `x` may also be a list of streams — each (N_i, 3, H, W) or (B, 3, T, H, W), same frame size — which are encoded as ONE frame
+    batch (stream after stream, a 5-D stream in (b t) order) and returned as a list of per-stream moments (contiguous slices of one
+    buffer).  The three streams of a training batch take this door: a batch of frames may then span two streams, where stream by
+    stream each would end on a partial one."""
+    streams = list(x) if isinstance(x, (list, tuple)) else [x]
+    streams = [_check(v).contiguous() for v in streams]
+    counts = [v.shape[0] * (v.shape[2] if v.dim() == 5 else 1) for v in streams]
+    c, (h, w) = streams[0].shape[1], streams[0].shape[-2:]
+    if any(v.shape[1] != c or tuple(v.shape[-2:]) != (h, w) or v.device != streams[0].device for v in streams):
+        raise ValueError("encode_moments: every stream must have the same channels, frame size and device")
+    first = [sum(counts[:i]) for i in range(len(counts) + 1)]              # first global frame of each stream
+    n = first[-1]
     cin = (c + 7) // 8 * 8
     qc = ae.quant_conv
     out = None
     for n0 in range(0, n, max_frames):
         nb = min(max_frames, n - n0)
-        rows = ops.empty_rows(nb * h * w, cin, ops.H16(), x.device)
-        ops.ncthw_to_rows(x[n0:n0 + nb].unsqueeze(2), rows, 0)
+        rows = ops.empty_rows(nb * h * w, cin, ops.H16(), streams[0].device)
+        for i, v in enumerate(streams):
+            a, b = max(n0, first[i]), min(n0 + nb, first[i + 1])
+            if a < b:
+                _load_frames(v, a - first[i], b - first[i], rows[(a - n0) * h * w:], h * w)
         if cin > c:
             ops.zero_channels(rows, c, cin)
         y, hh, ww = encoder_rows(ae.encoder, rows, nb, h, w)
         mom = ops.gemm(y, pk.linear(qc), bias=pk.f32(qc, "bias"), out_fp32=True)
         if out is None:
-            out = torch.empty((n, mom.shape[1], 1, hh, ww), dtype=torch.float32, device=x.device)
+            out = torch.empty((n, mom.shape[1], 1, hh, ww), dtype=torch.float32, device=mom.device)
         ops.rows_to_ncthw(mom, (nb, mom.shape[1], 1, hh, ww), out=out[n0:n0 + nb])
-    return out[:, :, 0]
+    out = out[:, :, 0]
+    if isinstance(x, (list, tuple)):
+        return [out[first[i]:first[i + 1]] for i in range(len(streams))]
+    return out
 
 
 def _check(z):

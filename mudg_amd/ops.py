@@ -555,6 +555,54 @@ def gaussian_sample(moments, noise=None, scale=1.0):
     return out
 
 
+def _dense_f32(name, t, shape=None):
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise hip.MudgError(f"{name}: expected a contiguous fp32 tensor on the GPU" + (f" of shape {tuple(shape)}" if shape else "")
+                            + f", got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def posterior_assemble(mom_x, mom_sparse, mom_depth, noise, b, t, scale=1.0):
+    """The three posterior samples of get_batch_input in one launch, in the UNet's layout: moments (b t, 2C, h, w) fp32 of the
+    dense / sparse colour / sparse depth frames, `noise` (3, b t, C, h, w) on the device (stream order dense, sparse, depth) or
+    None (posterior mode) -> z (b, C, t, h, w), c_concat (b, 2C, t, h, w) = [sparse | depth] along the channels.  The value
+    arithmetic is gaussian_sample's."""
+    n, c2, h, w = mom_x.shape
+    c = c2 // 2
+    if n != b * t:
+        raise hip.MudgError(f"posterior_assemble: {n} frames are not {b} clips of {t}")
+    for m in (mom_x, mom_sparse, mom_depth):
+        _dense_f32("posterior_assemble: moments", m, (n, c2, h, w))
+    if noise is not None:
+        _dense_f32("posterior_assemble: noise", noise, (3, n, c, h, w))
+    z = torch.empty((b, c, t, h, w), dtype=torch.float32, device=mom_x.device)
+    cc = torch.empty((b, 2 * c, t, h, w), dtype=torch.float32, device=mom_x.device)
+    nz = [None] * 3 if noise is None else [noise[i].data_ptr() for i in range(3)]
+    hip.check(hip.lib().mudg_posterior_assemble(mom_x.data_ptr(), mom_sparse.data_ptr(), mom_depth.data_ptr(), *nz, z.data_ptr(),
+                                                cc.data_ptr(), b, t, c, h * w, float(scale), _stream()), "mudg_posterior_assemble")
+    return z, cc
+
+
+def cond_dropout(r, p, cond_emb, null_prompt, clip, frame=0):
+    """Conditioning dropout of get_batch_input from the device vector r (b,): prompt rows (b, L, D) <- null_prompt (1, L, D)
+    where r < 2p; image (b, C, H, W) = (1 - (r >= p)(r < 3p)) * clip[:, :, frame], read in place from the (b, C, T, H, W) clip
+    (which is not modified).  One launch; r never leaves the device."""
+    b, ch, t, h, w = clip.shape
+    _dense_f32("cond_dropout: clip", clip)
+    _dense_f32("cond_dropout: r", r, (b,))
+    cond_emb = _dense_f32("cond_dropout: prompt embedding", cond_emb.float().contiguous())
+    null_prompt = _dense_f32("cond_dropout: null prompt", null_prompt.float().contiguous(), (1,) + tuple(cond_emb.shape[1:]))
+    if cond_emb.shape[0] != b or not 0 <= frame < t:
+        raise hip.MudgError(f"cond_dropout: {cond_emb.shape[0]} prompts / frame {frame} for a clip batch {tuple(clip.shape)}")
+    prompt = torch.empty_like(cond_emb)
+    img = torch.empty((b, ch, h, w), dtype=torch.float32, device=clip.device)
+    p = float(p)
+    hip.check(hip.lib().mudg_cond_dropout(r.data_ptr(), p, 2 * p, 3 * p, cond_emb.data_ptr(), null_prompt.data_ptr(), prompt.data_ptr(),
+                                          b, cond_emb[0].numel(), clip.data_ptr() + 4 * frame * h * w, clip.stride(0), clip.stride(1),
+                                          img.data_ptr(), ch, h * w, _stream()), "mudg_cond_dropout")
+    return prompt, img
+
+
 def ddim_step(x, e_c, e_u, noise, coef, e_m=None):
     """Fused DDIM update on fp32 latents (B, ...). coef = 8 to 10 host floats, see mudg_ddim_step; e_m = the
     image-only-conditioned pass of the three-way guidance (coef[8] = cfg_img); coef[9] = 1 for eps-predicting models."""

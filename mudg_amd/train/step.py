@@ -293,14 +293,23 @@ class GradientAllReducer:
         self._hooks = []
 
 
-def training_step(model, x_start, cond, t, optimizer, reducer=None, noise=None, clipper=None, **kwargs):
+def training_step(model, x_start, cond=None, t=None, optimizer=None, reducer=None, noise=None, clipper=None, **kwargs):
     """One optimisation step as the reference's trainer runs it: zero_grad -> p_losses -> backward -> (gradient all-reduce) ->
-    (gradient-norm clipping) -> AdamW.  Returns (loss, loss_dict); with a clipper, loss_dict["grad_norm"] is the device scalar."""
+    (gradient-norm clipping) -> AdamW.  Returns (loss, loss_dict); with a clipper, loss_dict["grad_norm"] is the device scalar.
+    `x_start` may instead be a DATA batch (a dict of pixels, caption, class label, frame rate: LatentVisualDiffusion.get_batch_input);
+    the loss then comes from model.shared_step(batch, random_uncond=model.classifier_free_guidance), `cond` and `t` stay None."""
+    if optimizer is None:
+        raise TypeError("training_step needs the optimizer")
     if reducer is not None:
         reducer.zero_grad()                               # one fill per bucket; the gradients stay views into the buckets
     else:
         optimizer.zero_grad(set_to_none=False)            # (multi-tensor fill; the clipper's and AdamW's pointer tables stay valid)
-    loss, info = p_losses(model, x_start, cond, t, noise=noise, **kwargs)
+    if isinstance(x_start, dict):
+        if cond is not None or t is not None or noise is not None:
+            raise TypeError("training_step: a data batch brings its own conditioning; the timesteps and the noise are drawn in forward()")
+        loss, info = model.shared_step(x_start, random_uncond=model.classifier_free_guidance, **kwargs)
+    else:
+        loss, info = p_losses(model, x_start, cond, t, noise=noise, **kwargs)
     loss.backward()
     if reducer is not None:
         reducer()

@@ -6,11 +6,99 @@ config.yaml): the stages' temporal transformers frozen (temporal_frozen), the gr
 reference's per-GPU batch of 4 clips (config.yaml:113-135), `acc2` = its accumulate_grad_batches 2 (two micro-batches per
 optimiser step).  All parameters trainable and no clipping otherwise (the heavier step).  FLOP accounting: 3 x the forward per
 clip, whatever is frozen.  After the timed steps one more step runs with the contraction families bracketed by hipEvents
-(forward GEMMs / convs / attention and the input-gradient GEMMs that run on the same kernels): the `roofline` of the json."""
+(forward GEMMs / convs / attention and the input-gradient GEMMs that run on the same kernels): the `roofline` of the json.
+
+`python tools/train_bench.py --from-pixels [512 1024] [json]`: one step from a PIXEL batch per resolution (B = 1: 3 streams x 16 frames through
+the VAE encoder, conditioning dropout, Resampler, then the step above).  Reports get_batch_input's milliseconds (five repeats after a
+warm-up call) next to the same work written with three encode_first_stage calls + torch.cat / torch.where — what a caller could write
+before get_batch_input existed — timed the same way in the same process, and get_batch_input's share of the whole step.  The CLIP towers
+are outside this package: device-resident stand-ins of the towers' output shapes take their place and cost nothing."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from mudg_amd import configs, factory
+
+RESAMPLER_MDM = {"target": "lvdm.modules.encoders.resampler.Resampler",          # the image_proj_stage_config of the MDM training configs
+                 "params": dict(dim=1024, depth=4, dim_head=64, heads=12, num_queries=16, embedding_dim=1280, output_dim=1024, ff_mult=4, video_length=16)}
+PIXELS = {"512": (320, 512), "1024": (576, 1024)}
+
+
+class _Tower(torch.nn.Module):
+    """A stand-in for a frozen CLIP tower: fixed tokens of the tower's output shape, already on the device."""
+
+    def __init__(self, rows, null=None):
+        super().__init__()
+        self.rows, self.null = rows, null
+
+    def encode(self, prompts):
+        return self.null if list(prompts) == [""] else self.rows
+
+    def forward(self, x):
+        return self.rows
+
+
+def _timed(fn, repeats=5):
+    fn()                                                    # warm-up: packed weights, kernel plans, allocator
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def from_pixels(res, dev):
+    model = factory.build_synthetic_model(res, dev, seed=123, overrides={"image_proj_stage_config": RESAMPLER_MDM, "first_stage_key": "dense_frames",
+                                                                         "uncond_prob": 0.05}).train()
+    g = torch.Generator(device=dev).manual_seed(7)
+    rn = lambda *s: torch.randn(*s, generator=g, device=dev)
+    model.cond_stage_model = _Tower(rn(1, 77, 1024), rn(1, 77, 1024))
+    model.embedder = _Tower(rn(1, 257, 1280))
+    h, w = PIXELS[res]
+    clip = lambda: rn(1, 3, 16, h, w).clamp(-1, 1)
+    batch = {"dense_frames": clip(), "sparse_frames": clip(), "sparse_depth": clip(), "class_label": torch.tensor([[500]], device=dev),
+             "caption": ["a street"], "fps": torch.tensor([10], device=dev)}
+    p = model.uncond_prob
+
+    def by_hand():                                          # the same work without get_batch_input: three encodes, cat, where
+        z = model.encode_first_stage(batch["dense_frames"])
+        sparse_z, depth_z = model.encode_first_stage(batch["sparse_frames"]), model.encode_first_stage(batch["sparse_depth"])
+        cat = torch.cat([sparse_z, depth_z], 1)
+        r = torch.rand(1, device=dev)
+        emb, null = model.get_learned_conditioning(batch["caption"]), model.get_learned_conditioning([""])
+        prompt = torch.where((r < 2 * p)[:, None, None], null, emb)
+        keep = 1 - ((r >= p).float() * (r < 3 * p).float())[:, None, None, None]
+        with torch.no_grad():
+            tokens = model.embedder(keep * batch["sparse_frames"][:, :, 0])
+        return z, cat, torch.cat([prompt, model.image_proj_model(tokens)], 1)
+
+    hand = _timed(by_hand)
+    new = _timed(lambda: model.get_batch_input(batch, random_uncond=True, return_fs=True, return_class_label=True))
+    model.learning_rate = 1e-5
+    opt = model.configure_optimizers()
+
+    def one_step():
+        opt.zero_grad(set_to_none=False)
+        model.training_step(batch).backward()
+        opt.step()
+
+    step_ms = _timed(one_step, repeats=3)
+    med = lambda v: sorted(v)[len(v) // 2]
+    return {"workload": f"MDM{res} training step from a pixel batch: get_batch_input (3 x 16 frames of {h} x {w}) -> p_losses -> backward -> AdamW, B = 1",
+            "get_batch_input_ms": [round(v, 2) for v in new], "by_hand_ms": [round(v, 2) for v in hand],
+            "get_batch_input_ms_median": round(med(new), 2), "by_hand_ms_median": round(med(hand), 2),
+            "by_hand_spread_ms": round(max(hand) - min(hand), 2), "step_ms": [round(v, 1) for v in step_ms],
+            "share_of_step": round(med(new) / med(step_ms), 4),
+            "by_hand": "three encode_first_stage calls + torch.cat / torch.where + the same towers and Resampler, same process, timed first"}
+
+
+if "--from-pixels" in sys.argv:
+    import json
+    for r_ in [a for a in sys.argv[1:] if a in PIXELS] or ["512", "1024"]:
+        print(json.dumps(from_pixels(r_, torch.device("cuda:0"))), flush=True)
+        torch.cuda.empty_cache()
+    sys.exit(0)
 
 res = sys.argv[1] if len(sys.argv) > 1 else "512"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
