@@ -309,6 +309,11 @@ int mudg_cond_dropout(const float* r, float p, float p2, float p3, const float* 
  *                   first minimum wins) and the image recoloured with the palette                       eval_tools.py:309-347 */
 int mudg_frames_to_u8(const float* video, uint8_t* out, int B, int C, int T, int64_t HW, void* stream);
 int mudg_depth_from_u8(const uint8_t* frames, float* depth, int64_t pixels, void* stream);
+/* The frame sheet of a logged entry (utils/save_video.py:62-136): video (N, C, T, H, W) fp32, C = 1 or 3 -> out (T, N H, W, 3) uint8,
+ * the samples stacked along the height (make_grid(nrow=1, padding=0)), one channel repeated to three; clamp != 0: clamp to [-1, 1]
+ * first (prepare_to_log); rescale != 0: (x + 1) / 2; then * 255 and truncation, in the reference's fp32 order: byte-equal.  An
+ * image entry (N, C, H, W) -> (N H, W, 3) is the call with T = 1. */
+int mudg_log_sheet(const float* video, uint8_t* out, int N, int C, int T, int H, int W, int clamp, int rescale, void* stream);
 int mudg_semantic_nearest(const uint8_t* img, uint8_t* vis, int64_t* labels, int64_t hw, void* stream);
 
 /* ------------------------------------------------------------------ training step
@@ -414,6 +419,17 @@ int mudg_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr
  * (p, g, m, v addresses, count <= mudg_clip_chunk()) covering every parameter; bit-identical to mudg_adamw per element. */
 int mudg_adamw_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                      void* stream);
+/* The averaged weights (lvdm/ema.py, ddpm3d.py:188-201, 398-409), same table scheme (rows of int64, count <= mudg_clip_chunk(), one
+ * workgroup per row; 16-byte accesses where every address of the row is 16-byte aligned).
+ * ema_multi, rows (shadow, param, count): shadow = shadow - one_minus_decay * (shadow - param), every operation rounded on its own
+ *   (bit-equal to LitEma.forward on the CPU).
+ * adamw_ema_multi, rows (p, g, m, v, shadow, count): mudg_adamw_multi's update and ema_multi's of the same element in one pass;
+ *   p, m, v bit-identical to mudg_adamw_multi, shadow bit-identical to mudg_adamw_multi followed by mudg_ema_multi.
+ * swap_multi, rows (a, b, count): a and b change places (ema_scope: one swap on entry, one on exit; no third copy). */
+int mudg_adamw_ema_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                         float one_minus_decay, void* stream);
+int mudg_ema_multi(const int64_t* table, int nchunks, float one_minus_decay, void* stream);
+int mudg_swap_multi(const int64_t* table, int nchunks, void* stream);
 /* torch.nn.utils.clip_grad_norm_ over many fp32 tensors with no host round trip (the reference's trainer: gradient_clip_val 0.5,
  * norm).  table: device int64 [nchunks][2] = (address, count <= mudg_clip_chunk()) covering every gradient; partial: fp64 [nchunks]
  * scratch; out: float [2] = (total 2-norm, clip coefficient min(1, max_norm / (norm + 1e-6))); the gradients are scaled in place. */

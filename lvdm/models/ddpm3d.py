@@ -5,9 +5,12 @@ What the denoising path needs from the reference's Lightning classes, without Li
 DiffusionWrapper.forward 1309-1324), the v-parameterisation helpers (239-251), first-stage decode (646-671) and the
 constructor surface of LatentVisualDiffusion (1033-1055) so MuDG's YAML configs instantiate it unchanged and its
 checkpoints load with the same key prefixes (model.diffusion_model.*, first_stage_model.*, image_proj_model.*).
-The training step (p_losses, configure_optimizers, training_step) is delegated to mudg_amd.train; the
-Lightning loop, logging and the data pipeline around it are not built.
+The training step (p_losses, configure_optimizers, training_step) is delegated to mudg_amd.train.  What the
+reference's loop does around a step is here too, without Lightning: the averaged weights (use_ema: lvdm/ema.py, ema_scope,
+on_train_batch_end, the *_ema entries of validation_step) and log_images / sample_log (1186-1265, 996-1005), which
+main/callbacks.py's ImageLogger calls.  The Lightning loop itself and the data pipeline are not built.
 """
+from contextlib import contextmanager
 from functools import partial
 
 import numpy as np
@@ -30,6 +33,28 @@ def _cfg_get(cfg, key, fallback=None):
         except (KeyError, TypeError):
             return fallback
     return getattr(cfg, key, fallback)
+
+
+def _make_grid(tensor, nrow=8, padding=2, pad_value=0.0):
+    """torchvision.utils.make_grid for a batch (N, C, H, W) with its defaults (no normalisation): cell k at row k // nrow, column
+    k % nrow, top-left corner (row (H + padding) + padding, column (W + padding) + padding) of a (C, rows (H + padding) + padding,
+    columns (W + padding) + padding) canvas filled with pad_value; a one-channel batch is repeated to three channels, a batch of
+    one image is returned as that image.  (torchvision is not a dependency of this package.)"""
+    if tensor.dim() != 4:
+        raise ValueError(f"_make_grid lays out a (N, C, H, W) batch, got {tuple(tensor.shape)}")
+    if tensor.shape[1] == 1:
+        tensor = torch.cat((tensor, tensor, tensor), 1)
+    if tensor.shape[0] == 1:
+        return tensor.squeeze(0)
+    nmaps = tensor.shape[0]
+    xmaps = min(nrow, nmaps)
+    ymaps = -(-nmaps // xmaps)
+    height, width = tensor.shape[2] + padding, tensor.shape[3] + padding
+    grid = tensor.new_full((tensor.shape[1], height * ymaps + padding, width * xmaps + padding), pad_value)
+    for k in range(nmaps):
+        y, x = divmod(k, xmaps)
+        grid[:, y * height + padding:(y + 1) * height, x * width + padding:(x + 1) * width] = tensor[k]
+    return grid
 
 
 class DiffusionWrapper(nn.Module):
@@ -68,8 +93,6 @@ class DDPM(nn.Module):
                  learn_logvar=False, logvar_init=0., rescale_betas_zero_snr=False):
         super().__init__()
         assert parameterization in ["eps", "x0", "v"], 'currently only supporting "eps" and "x0" and "v"'
-        if use_ema:
-            raise NotImplementedError("EMA weights (use_ema) are disabled in every MuDG config and not implemented")
         self.parameterization = parameterization
         self.cond_stage_model = None
         self.clip_denoised, self.log_every_t = clip_denoised, log_every_t
@@ -78,7 +101,10 @@ class DDPM(nn.Module):
         self.image_size = [image_size, image_size] if isinstance(image_size, int) else image_size
         self.use_positional_encodings = use_positional_encodings
         self.model = DiffusionWrapper(unet_config, conditioning_key)
-        self.use_ema = False
+        self.use_ema = bool(use_ema)
+        if self.use_ema:
+            from lvdm.ema import LitEma
+            self.model_ema = LitEma(self.model)
         self.rescale_betas_zero_snr = rescale_betas_zero_snr
         self.v_posterior, self.original_elbo_weight, self.l_simple_weight = v_posterior, original_elbo_weight, l_simple_weight
         if monitor is not None:
@@ -151,6 +177,27 @@ class DDPM(nn.Module):
         lvlb[0] = lvlb[1]
         self.register_buffer("lvlb_weights", f32(lvlb), persistent=False)
 
+    @contextmanager
+    def ema_scope(self, context=None):
+        """Inside the scope the network runs on the averaged weights (ddpm3d.py:188-201).  Here: one in-place exchange of weights and
+        shadows on entry and one on exit (LitEma.swap) instead of the reference's store / copy_to / restore — the training weights
+        come back bit for bit and no third copy of the parameters is held; while the scope is open the shadow buffers hold the
+        training weights.  The exchange bumps the version counters of the parameters, so packed operand weights, captured graphs
+        and cached contexts follow.  Without use_ema: nothing happens."""
+        if self.use_ema:
+            self.model_ema.swap(self.model)
+        try:
+            yield None
+        finally:
+            if self.use_ema:
+                self.model_ema.swap(self.model)
+
+    def on_train_batch_end(self, *args, **kwargs):
+        """ddpm3d.py:407-409: one update of the averaged weights (a loop that hands model_ema to mudg_amd.train.step.training_step
+        has had it inside the optimiser's launch already and does not call this)."""
+        if self.use_ema:
+            self.model_ema(self.model)
+
     def init_from_ckpt(self, path, ignore_keys=list(), only_model=False):
         sd = torch.load(path, map_location="cpu")
         sd = sd.get("state_dict", sd)
@@ -217,10 +264,14 @@ class DDPM(nn.Module):
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):
-        """shared_step without a graph; returns the loss_dict (there are no EMA weights to evaluate a second time: use_ema is
-        rejected by the constructor)."""
+        """shared_step without a graph; returns the loss_dict.  With use_ema the batch is evaluated a second time under ema_scope()
+        and those entries join the dictionary with '_ema' appended to their keys (ddpm3d.py:398-405, which logs both)."""
         _, loss_dict = self.shared_step(batch)
-        return loss_dict
+        if not self.use_ema:
+            return loss_dict
+        with self.ema_scope():
+            _, loss_dict_ema = self.shared_step(batch)
+        return dict(loss_dict, **{key + "_ema": loss_dict_ema[key] for key in loss_dict_ema})
 
     def forward(self, x, c, **kwargs):
         """The training entry (ddpm3d.py:711-715): draw one timestep per sample, apply the dynamic rescale of the latents when the
@@ -365,6 +416,31 @@ class LatentDiffusion(DDPM):
 
     differentiable_decode_first_stage = decode_first_stage
 
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
+        """ddpm3d.py:996-1005: a DDIM run of `ddim_steps` steps over (channels, temporal_length, *image_size) latents; every other
+        keyword argument goes to DDIMSampler.sample.  Returns (samples, intermediates)."""
+        if not ddim:
+            raise NotImplementedError("sample_log(ddim=False): the ancestral sampler is not on the MuDG path; pass ddim_steps")
+        from lvdm.models.samplers.ddim import DDIMSampler
+        shape = (self.channels, self.temporal_length, *self.image_size)
+        return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+
+    @torch.no_grad()
+    def _get_denoise_row_from_list(self, samples, desc=""):
+        """ddpm3d.py:804-827: decode every recorded latent and lay the results out as torchvision's make_grid does with its default
+        padding: images (n, b, c, h, w) one row per sample, n columns; videos (n, b, c, t, h, w) one row per (sample, recorded
+        step), t columns."""
+        rows = torch.stack([self.decode_first_stage(zd.to(self.device)) for zd in samples])
+        if rows.dim() == 5:
+            n = rows.shape[0]
+            return _make_grid(rows.permute(1, 0, 2, 3, 4).flatten(0, 1), nrow=n)
+        if rows.dim() == 6:
+            t = rows.shape[3]
+            cells = rows.permute(1, 0, 3, 2, 4, 5).flatten(0, 2)          # (b n t) c h w
+            return _make_grid(cells, nrow=t)
+        raise ValueError(f"decoded latents of {rows.dim() - 1} dimensions")
+
     def apply_model(self, x_noisy, t, cond, **kwargs):
         if not isinstance(cond, dict):
             cond = {("c_concat" if self.model.conditioning_key == "concat" else "c_crossattn"):
@@ -505,6 +581,52 @@ class LatentVisualDiffusion(LatentDiffusion):
         if return_class_label:
             out.append(class_label)
         return out
+
+    @torch.no_grad()
+    def log_images(self, batch, sample=True, ddim_steps=50, ddim_eta=1., plot_denoise_rows=False, unconditional_guidance_scale=1.0,
+                   mask=None, **kwargs):
+        """What the training loop's ImageLogger logs (ddpm3d.py:1186-1265), for the FIRST sample of the batch: `image_condition` (its
+        key frame), `reconst` (decode of its encoded clip), `condition` (caption + "_fs=<frame rate>"), and with `sample` the
+        decoded `samples` of a DDIM run from the batch's conditioning under ema_scope() — guided against the unconditional branch
+        (null prompt by uncond_type, the all-zero image through embedder and image_proj_model, c_concat shared) when
+        unconditional_guidance_scale != 1 — plus, with plot_denoise_rows, `denoise_row` (the recorded pred_x0 list decoded and laid
+        out by _get_denoise_row_from_list).  x0=z, fs and class_label ride to the sampler among the keyword arguments; so does
+        everything else the caller passes (x_T=..., and split=..., which the UNet ignores), as in the reference.
+        One stated difference: the one-sample cut is made on a shallow copy, the caller's batch is not modified."""
+        sampled_img_num = 1
+        batch = {key: (value if key == "tasks" else value[:sampled_img_num]) for key, value in batch.items()}
+        use_ddim = ddim_steps is not None
+        log = dict()
+        z, sparse_z, c, xrec, xc, fs, cond_x, sparse, class_label = self.get_batch_input(
+            batch, random_uncond=False, return_first_stage_outputs=True, return_original_cond=True, return_fs=True,
+            return_cond_frame=True, return_sparse_input=True, return_class_label=True)
+        n = xrec.shape[0]
+        log["image_condition"] = cond_x
+        log["reconst"] = xrec
+        log["condition"] = [content + "_fs=" + str(rate) for content, rate in zip(xc, fs.tolist())]
+        kwargs.update({"fs": fs.long()})
+        kwargs.update({"class_label": class_label})
+        if not sample:
+            return log
+        uc = None
+        if unconditional_guidance_scale != 1.0:
+            c_emb, c_cat = (c["c_crossattn"][0], c["c_concat"][0] if "c_concat" in c else None) if isinstance(c, dict) else (c, None)
+            if self.uncond_type == "empty_seq":
+                uc_prompt = self.get_learned_conditioning(n * [""])
+            elif self.uncond_type == "zero_embed":
+                uc_prompt = torch.zeros_like(c_emb)
+            uc_img = self.image_proj_model(self.embedder(torch.zeros_like(xrec[:, :, 0])))      # the all-zero image: b c h w -> b l c
+            uc = torch.cat([uc_prompt, uc_img], dim=1)
+            if isinstance(c, dict):                      # hybrid: the latents the UNet reads beside x are those of the conditional pass
+                uc = {"c_concat": [c_cat], "c_crossattn": [uc]}
+        with self.ema_scope("Plotting"):
+            samples, z_denoise_row = self.sample_log(cond=c, batch_size=n, ddim=use_ddim, ddim_steps=ddim_steps, eta=ddim_eta,
+                                                     unconditional_guidance_scale=unconditional_guidance_scale,
+                                                     unconditional_conditioning=uc, x0=z, **kwargs)
+        log["samples"] = self.decode_first_stage(samples)
+        if plot_denoise_rows:
+            log["denoise_row"] = self._get_denoise_row_from_list(z_denoise_row["pred_x0"])
+        return log
 
     def shared_step(self, batch, random_uncond=None, **kwargs):
         """ddpm3d.py:1056-1062: get_batch_input, then forward() (random t, dynamic rescale, p_losses) with fs / sparse_x /

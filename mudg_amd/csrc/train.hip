@@ -565,6 +565,129 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------- averaged weights
+// The exponential moving average of the weights (lvdm/ema.py LitEma.forward) and the weight exchange of ema_scope
+// (ddpm3d.py:188-201), over MANY tensors in one launch with the chunk-table scheme of adamw_multi_kernel.  Pure streaming:
+// a chunk is walked in pieces of 256 x 16 bytes per operand, MT_U pieces at a time, every load of the pieces issued before the
+// first use (the updates are in place, so the compiler may not move a load above a store by itself); a chunk whose addresses are
+// not all 16-byte aligned (a view into a flat bucket) and the last count % 4 values take the scalar loop.
+//   shadow <- shadow - one_minus_decay * (shadow - param), each operation rounded on its own: the bits of the reference on the CPU
+constexpr int MT_U = 2;
+// The addresses come out of the table as integers: typed as global memory, so that the accesses are global_* and not flat_* ones.
+typedef __attribute__((address_space(1))) float gfloat;
+typedef __attribute__((address_space(1))) f32x4 gf32x4;
+__device__ __forceinline__ float ema_elem(float s, float p, float omd) { return __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, p))); }
+
+__global__ __launch_bounds__(256) void ema_multi_kernel(const int64_t* __restrict__ table, float omd) {
+    const int64_t* row = table + 3 * (int64_t)blockIdx.x;
+    gfloat* s = reinterpret_cast<gfloat*>(row[0]);
+    const gfloat* p = reinterpret_cast<const gfloat*>(row[1]);
+    const int n = (int)row[2];
+    int done = 0;
+    if (((row[0] | row[1]) & 15) == 0) {
+        gf32x4* s4 = reinterpret_cast<gf32x4*>(s);
+        const gf32x4* p4 = reinterpret_cast<const gf32x4*>(p);
+        const int n4 = n >> 2;
+        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
+            f32x4 a[MT_U] = {}, b[MT_U] = {};
+#pragma unroll
+            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) { a[u] = s4[i0 + 256 * u]; b[u] = p4[i0 + 256 * u]; }
+#pragma unroll
+            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a[u][e] = ema_elem(a[u][e], b[u][e], omd);
+                s4[i0 + 256 * u] = a[u];
+            }
+        }
+        done = n4 << 2;
+    }
+    for (int i = done + threadIdx.x; i < n; i += 256) s[i] = ema_elem(s[i], p[i], omd);
+}
+
+// rows (a, b, count): the two tensors change places; nothing else is held.
+__global__ __launch_bounds__(256) void swap_multi_kernel(const int64_t* __restrict__ table) {
+    const int64_t* row = table + 3 * (int64_t)blockIdx.x;
+    gfloat* a = reinterpret_cast<gfloat*>(row[0]);
+    gfloat* b = reinterpret_cast<gfloat*>(row[1]);
+    const int n = (int)row[2];
+    int done = 0;
+    if (((row[0] | row[1]) & 15) == 0) {
+        gf32x4* a4 = reinterpret_cast<gf32x4*>(a);
+        gf32x4* b4 = reinterpret_cast<gf32x4*>(b);
+        const int n4 = n >> 2;
+        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
+            f32x4 x[MT_U] = {}, y[MT_U] = {};
+#pragma unroll
+            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) { x[u] = a4[i0 + 256 * u]; y[u] = b4[i0 + 256 * u]; }
+#pragma unroll
+            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) { a4[i0 + 256 * u] = y[u]; b4[i0 + 256 * u] = x[u]; }
+        }
+        done = n4 << 2;
+    }
+    for (int i = done + threadIdx.x; i < n; i += 256) { const float x = a[i], y = b[i]; a[i] = y; b[i] = x; }
+}
+
+// adamw_multi_kernel's update and the average of the same element in one pass, rows (p, g, m, v, shadow, count): the average reads
+// the new parameter value out of the register it was just computed in — one read and one write of the shadow on top of the AdamW
+// traffic, no second read of the parameter.  The AdamW expressions are those of adamw_multi_kernel, term for term.
+__device__ __forceinline__ void adamw_ema_elem(float& p, float g, float& m, float& v, float& s, float b1, float b2, float eps, float bc2,
+                                               float step, float decay, float omd) {
+    const float gi = g;
+    const float pi = p * decay;
+    const float mi = b1 * m + (1.0f - b1) * gi;
+    const float vi = b2 * v + (1.0f - b2) * gi * gi;
+    m = mi; v = vi;
+    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+    p = pi - step * (mi / denom);
+    s = ema_elem(s, p, omd);
+}
+
+__global__ __launch_bounds__(256) void adamw_ema_multi_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2, float eps,
+                                                               float wd, float bc1, float bc2, float omd) {
+    const int64_t* row = table + 6 * (int64_t)blockIdx.x;
+    gfloat* p = reinterpret_cast<gfloat*>(row[0]);
+    const gfloat* g = reinterpret_cast<const gfloat*>(row[1]);
+    gfloat* m = reinterpret_cast<gfloat*>(row[2]);
+    gfloat* v = reinterpret_cast<gfloat*>(row[3]);
+    gfloat* s = reinterpret_cast<gfloat*>(row[4]);
+    const int n = (int)row[5];
+    const float step = lr / bc1, decay = 1.0f - lr * wd;
+    int done = 0;
+    if (((row[0] | row[1] | row[2] | row[3] | row[4]) & 15) == 0) {
+        gf32x4* p4 = reinterpret_cast<gf32x4*>(p);
+        const gf32x4* g4 = reinterpret_cast<const gf32x4*>(g);
+        gf32x4* m4 = reinterpret_cast<gf32x4*>(m);
+        gf32x4* v4 = reinterpret_cast<gf32x4*>(v);
+        gf32x4* s4 = reinterpret_cast<gf32x4*>(s);
+        const int n4 = n >> 2;
+        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
+            f32x4 pp[MT_U] = {}, gg[MT_U] = {}, mm[MT_U] = {}, vv[MT_U] = {}, ss[MT_U] = {};
+#pragma unroll
+            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
+                const int i = i0 + 256 * u;
+                pp[u] = p4[i]; gg[u] = g4[i]; mm[u] = m4[i]; vv[u] = v4[i]; ss[u] = s4[i];
+            }
+#pragma unroll
+            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
+                const int i = i0 + 256 * u;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float pe = pp[u][e], me = mm[u][e], ve = vv[u][e], se = ss[u][e];
+                    adamw_ema_elem(pe, gg[u][e], me, ve, se, b1, b2, eps, bc2, step, decay, omd);
+                    pp[u][e] = pe; mm[u][e] = me; vv[u][e] = ve; ss[u][e] = se;
+                }
+                p4[i] = pp[u]; m4[i] = mm[u]; v4[i] = vv[u]; s4[i] = ss[u];
+            }
+        }
+        done = n4 << 2;
+    }
+    for (int i = done + threadIdx.x; i < n; i += 256) {
+        float pe = p[i], me = m[i], ve = v[i], se = s[i];
+        adamw_ema_elem(pe, g[i], me, ve, se, b1, b2, eps, bc2, step, decay, omd);
+        p[i] = pe; m[i] = me; v[i] = ve; s[i] = se;
+    }
+}
+
 // Global gradient norm and clipping over many tensors without a host round trip (torch.nn.utils.clip_grad_norm_ semantics: the
 // reference's trainer clips to norm 0.5).  `table` lists chunks of at most CLIP_CHUNK fp32 values as (address, count) pairs; one
 // workgroup sums the squares of a chunk in fp64 (fixed order), one workgroup then folds the chunk sums in order and writes
@@ -856,6 +979,29 @@ int mudg_adamw_multi(const int64_t* table, int nchunks, float lr, float beta1, f
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, lr, beta1, beta2, eps,
                        weight_decay, bc1, bc2);
     return mudg_check_launch("mudg_adamw_multi");
+}
+
+int mudg_adamw_ema_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                         float one_minus_decay, void* stream) {
+    MUDG_REQUIRE(table && nchunks > 0 && step > 0, "mudg_adamw_ema_multi: bad arguments");
+    MUDG_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "mudg_adamw_ema_multi: one_minus_decay=%g outside [0, 1]", (double)one_minus_decay);
+    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+    hipLaunchKernelGGL(adamw_ema_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, lr, beta1, beta2,
+                       eps, weight_decay, bc1, bc2, one_minus_decay);
+    return mudg_check_launch("mudg_adamw_ema_multi");
+}
+
+int mudg_ema_multi(const int64_t* table, int nchunks, float one_minus_decay, void* stream) {
+    MUDG_REQUIRE(table && nchunks > 0, "mudg_ema_multi: bad arguments");
+    MUDG_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "mudg_ema_multi: one_minus_decay=%g outside [0, 1]", (double)one_minus_decay);
+    hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, one_minus_decay);
+    return mudg_check_launch("mudg_ema_multi");
+}
+
+int mudg_swap_multi(const int64_t* table, int nchunks, void* stream) {
+    MUDG_REQUIRE(table && nchunks > 0, "mudg_swap_multi: bad arguments");
+    hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table);
+    return mudg_check_launch("mudg_swap_multi");
 }
 
 int mudg_clip_chunk(void) { return CLIP_CHUNK; }

@@ -144,6 +144,7 @@ SIGNATURES = {
     "mudg_lincomb": (_I, [_P, _P, _P, _P, _P, _I, _L, _P]),
     "mudg_ddim_ws_doubles": (_L, [_I]),
     "mudg_frames_to_u8": (_I, [_P, _P, _I, _I, _I, _L, _P]),
+    "mudg_log_sheet": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mudg_depth_from_u8": (_I, [_P, _P, _L, _P]),
     "mudg_semantic_nearest": (_I, [_P, _P, _P, _L, _P]),
     "mudg_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_float), _P, _P]),
@@ -171,6 +172,9 @@ SIGNATURES = {
     "mudg_dilate2x": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "mudg_adamw": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P]),
     "mudg_adamw_multi": (_I, [_P, _I, _F, _F, _F, _F, _F, _I, _P]),
+    "mudg_adamw_ema_multi": (_I, [_P, _I, _F, _F, _F, _F, _F, _I, _F, _P]),
+    "mudg_ema_multi": (_I, [_P, _I, _F, _P]),
+    "mudg_swap_multi": (_I, [_P, _I, _P]),
     "mudg_clip_chunk": (_I, []),
     "mudg_clip_grad_norm": (_I, [_P, _I, _P, _F, _P, _P]),
     "mudg_gelu": (_I, [_P, _P, _P, _L, _P]),

@@ -633,6 +633,24 @@ def frames_to_uint8(video):
     return out
 
 
+def log_sheet(value, clamp=True, rescale=True):
+    """The uint8 frame sheet of a logged entry (utils/save_video.py:62-136): a video (n, c, t, h, w) -> (t, n*h, w, 3), an image
+    batch (n, c, h, w) -> (n*h, w, 3); c = 1 or 3, the samples stacked along the height, one channel repeated to three.  clamp: to
+    [-1, 1] first (prepare_to_log); rescale: (x + 1) / 2; then * 255 and truncation — byte-equal to the reference's expressions."""
+    if value.dim() not in (4, 5) or not value.is_cuda:
+        raise hip.MudgError(f"log_sheet: expected a cuda (n, c, t, h, w) or (n, c, h, w) tensor, got {tuple(value.shape)} on {value.device}")
+    v = value.detach().to(torch.float32).contiguous()
+    n, c = v.shape[:2]
+    t = v.shape[2] if v.dim() == 5 else 1
+    h, w = v.shape[-2:]
+    if c not in (1, 3):
+        raise hip.MudgError(f"log_sheet: {c} channels (grayscale or rgb entries only)")
+    out = torch.empty((t, n * h, w, 3), dtype=torch.uint8, device=v.device)
+    hip.check(hip.lib().mudg_log_sheet(v.data_ptr(), out.data_ptr(), n, c, t, h, w, int(bool(clamp)), int(bool(rescale)), _stream()),
+              "mudg_log_sheet")
+    return out if v.dim() == 5 else out[0]
+
+
 def depth_from_uint8(frames):
     """(..., h, w, 3) uint8 -> (..., 1, h, w) float32 in [0, 1]: channel mean / 255 (eval_tools.py:71)."""
     if frames.dtype != torch.uint8 or frames.shape[-1] != 3 or not frames.is_cuda:

@@ -275,6 +275,35 @@ def adamw_multi_(table, nchunks, *, lr, betas, eps, weight_decay, step):
     hip.check(hip.lib().mudg_adamw_multi(table.data_ptr(), nchunks, lr, betas[0], betas[1], eps, weight_decay, step, _s()), "mudg_adamw_multi")
 
 
+def chunk_table(groups):
+    """The device table of the multi-tensor kernels: `groups` is a list of tuples of same-sized contiguous fp32 tensors (one tuple
+    per row family, e.g. (shadow, parameter)); every tuple is cut into chunks of mudg_clip_chunk() values, one int64 row
+    (address of each tensor's chunk..., count) per chunk.  Returns (table, chunk count)."""
+    chunk = hip.lib().mudg_clip_chunk()
+    rows = []
+    for tensors in groups:
+        n = tensors[0].numel()
+        base = [t.data_ptr() for t in tensors]
+        rows.extend((*(a + 4 * off for a in base), min(chunk, n - off)) for off in range(0, n, chunk))
+    return torch.tensor(rows, dtype=torch.int64).to(groups[0][0].device), len(rows)
+
+
+def adamw_ema_multi_(table, nchunks, *, lr, betas, eps, weight_decay, step, one_minus_decay):
+    """adamw_multi_ and ema_multi_ of the same elements in one launch (table rows: p, g, m, v, shadow, count)."""
+    hip.check(hip.lib().mudg_adamw_ema_multi(table.data_ptr(), nchunks, lr, betas[0], betas[1], eps, weight_decay, step, one_minus_decay, _s()),
+              "mudg_adamw_ema_multi")
+
+
+def ema_multi_(table, nchunks, one_minus_decay):
+    """shadow <- shadow - one_minus_decay * (shadow - param) over every tensor listed in `table` (rows: shadow, param, count)."""
+    hip.check(hip.lib().mudg_ema_multi(table.data_ptr(), nchunks, one_minus_decay, _s()), "mudg_ema_multi")
+
+
+def swap_multi_(table, nchunks):
+    """The two tensors of every row (a, b, count) change places."""
+    hip.check(hip.lib().mudg_swap_multi(table.data_ptr(), nchunks, _s()), "mudg_swap_multi")
+
+
 def adamw_(p, g, m, v, *, lr, betas, eps, weight_decay, step):
     """One torch.optim.AdamW step on flat fp32 buffers, in place."""
     for t in (p, g, m, v):

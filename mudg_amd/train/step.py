@@ -55,11 +55,34 @@ class AdamW(torch.optim.Optimizer):
     of (parameter, gradient, moment, moment, count) chunks; the table is rebuilt only when a tensor moved), instead of one launch
     per tensor — 1520 for the UNet.  After the update every parameter's autograd version counter is bumped: the kernel writes
     through raw pointers, and the inference side (packed operand weights, captured hipGraphs, cached K / V^T of a prepared
-    context) recognises changed weights by (data_ptr, _version)."""
+    context) recognises changed weights by (data_ptr, _version).
+
+    step(ema=LitEma): the averaged weights are updated in the SAME launch (mudg_adamw_ema_multi: the average reads the new value out
+    of the register it was computed in — one read and one write of the shadow on top of the AdamW traffic).  `num_updates` advances
+    once per step; parameters the average does not track take the plain launch, tracked parameters the optimiser did not step
+    (no gradient) get their shadow moved by mudg_ema_multi: after the call every shadow has had exactly LitEma.forward's update.
+    The average names its parameters by identity (those of the model it was built on): an optimiser that holds none of them is an
+    error, not a silent plain step."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._tables = {}                                 # group index -> (key, device table, chunk count)
+        self._ema_tables = {}                             # group index -> (key, fused table, count, plain table, count)
+
+    def _table_ema(self, gi, ps, shadows):
+        """Two tables for a group stepped with an average: rows (p, g, m, v, shadow, count) for the tracked parameters and the
+        rows of _table for the rest (either may be empty: None)."""
+        key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
+                     p.numel(), shadows[id(p)].data_ptr() if id(p) in shadows else 0) for p in ps)
+        hit = self._ema_tables.get(gi)
+        if hit is not None and hit[0] == key:
+            return hit[1:]
+        cols = lambda p: (p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"])
+        fused = [cols(p) + (shadows[id(p)],) for p in ps if id(p) in shadows]
+        plain = [cols(p) for p in ps if id(p) not in shadows]
+        hit = (key,) + (K.chunk_table(fused) if fused else (None, 0)) + (K.chunk_table(plain) if plain else (None, 0))
+        self._ema_tables[gi] = hit
+        return hit[1:]
 
     def _table(self, gi, ps):
         from .. import hip
@@ -81,8 +104,14 @@ class AdamW(torch.optim.Optimizer):
         return table, len(rows)
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, ema=None):
         loss = None
+        shadows, omd, averaged = None, None, set()
+        if ema is not None:
+            shadows = ema.shadow_map()
+            if shadows and not any(id(p) in shadows for group in self.param_groups for p in group["params"]):
+                raise RuntimeError("AdamW.step(ema=...): none of the optimiser's parameters is tracked by this average — it was built "
+                                   "on another model instance")
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
@@ -102,7 +131,22 @@ class AdamW(torch.optim.Optimizer):
                 st["step"] += 1
                 steps.add(st["step"])
             hyper = dict(lr=group["lr"], betas=group["betas"], eps=group["eps"], weight_decay=group["weight_decay"])
-            if len(steps) == 1:
+            if ema is not None and len(steps) == 1:
+                tracked = [p for p in ps if id(p) in shadows]
+                if tracked:
+                    ema._check([(p, shadows[id(p)]) for p in tracked])
+                fused, nf, plain, npl = self._table_ema(gi, ps, shadows)
+                step = steps.pop()
+                if omd is None:                           # after every check that can raise: a failed step leaves num_updates alone
+                    omd = ema.begin_update()
+                if nf:
+                    K.adamw_ema_multi_(fused, nf, step=step, one_minus_decay=omd, **hyper)
+                if npl:
+                    K.adamw_multi_(plain, npl, step=step, **hyper)
+                for p in tracked:
+                    averaged.add(id(p))
+                    torch.autograd.graph.increment_version(shadows[id(p)])
+            elif len(steps) == 1:
                 table, n = self._table(gi, ps)
                 K.adamw_multi_(table, n, step=steps.pop(), **hyper)
             else:                                         # parameters that joined the group at different times: one launch each
@@ -111,6 +155,10 @@ class AdamW(torch.optim.Optimizer):
                     K.adamw_(p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], step=st["step"], **hyper)
             for p in ps:
                 torch.autograd.graph.increment_version(p)
+        if ema is not None:                               # tracked parameters no fused launch covered: the average alone
+            if omd is None:
+                omd = ema.begin_update()
+            ema.update([(p, s) for p, s in ema.pairs() if id(p) not in averaged], omd)
         return loss
 
 
@@ -293,11 +341,13 @@ class GradientAllReducer:
         self._hooks = []
 
 
-def training_step(model, x_start, cond=None, t=None, optimizer=None, reducer=None, noise=None, clipper=None, **kwargs):
+def training_step(model, x_start, cond=None, t=None, optimizer=None, reducer=None, noise=None, clipper=None, ema=None, **kwargs):
     """One optimisation step as the reference's trainer runs it: zero_grad -> p_losses -> backward -> (gradient all-reduce) ->
     (gradient-norm clipping) -> AdamW.  Returns (loss, loss_dict); with a clipper, loss_dict["grad_norm"] is the device scalar.
     `x_start` may instead be a DATA batch (a dict of pixels, caption, class label, frame rate: LatentVisualDiffusion.get_batch_input);
-    the loss then comes from model.shared_step(batch, random_uncond=model.classifier_free_guidance), `cond` and `t` stay None."""
+    the loss then comes from model.shared_step(batch, random_uncond=model.classifier_free_guidance), `cond` and `t` stay None.
+    `ema` (a lvdm.ema.LitEma, e.g. model.model_ema): the averaged weights are updated inside the optimiser's launch — what
+    on_train_batch_end() does in a loop that does not pass it; pass it OR call on_train_batch_end(), not both."""
     if optimizer is None:
         raise TypeError("training_step needs the optimizer")
     if reducer is not None:
@@ -317,5 +367,8 @@ def training_step(model, x_start, cond=None, t=None, optimizer=None, reducer=Non
         stat = clipper()
         if stat is not None:
             info = dict(info, grad_norm=stat[0])
-    optimizer.step()
+    if ema is not None:
+        optimizer.step(ema=ema)
+    else:
+        optimizer.step()
     return loss.detach(), info

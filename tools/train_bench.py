@@ -8,6 +8,15 @@ optimiser step).  All parameters trainable and no clipping otherwise (the heavie
 clip, whatever is frozen.  After the timed steps one more step runs with the contraction families bracketed by hipEvents
 (forward GEMMs / convs / attention and the input-gradient GEMMs that run on the same kernels): the `roofline` of the json.
 
+`--ema` (anywhere after the step count): after the plain steps the same number of steps runs with the averaged weights
+(lvdm.ema.LitEma over the UNet) updated inside the optimiser's launch (AdamW.step(ema=...): mudg_adamw_ema_multi), reported next to
+the plain step of the same run, together with the achieved TB/s of mudg_ema_multi (3 x 4 bytes per parameter) and mudg_swap_multi
+(4 x 4 bytes per parameter) on their own (the launches on their prebuilt tables, 20 repeats between two events).
+
+`python tools/train_bench.py --log-images [512|1024]`: one LatentVisualDiffusion.log_images call from a pixel batch (B = 1, 50 DDIM
+steps, guidance 7.5, the towers' stand-ins of --from-pixels) in seconds, after a 2-step warm-up call, next to 100 sampler steps of the
+same model in the same process (two 50-step sample_log runs on the conditioning log_images built).
+
 `python tools/train_bench.py --from-pixels [512 1024] [json]`: one step from a PIXEL batch per resolution (B = 1: 3 streams x 16 frames through
 the VAE encoder, conditioning dropout, Resampler, then the step above).  Reports get_batch_input's milliseconds (five repeats after a
 warm-up call) next to the same work written with three encode_first_stage calls + torch.cat / torch.where — what a caller could write
@@ -93,6 +102,49 @@ def from_pixels(res, dev):
             "by_hand": "three encode_first_stage calls + torch.cat / torch.where + the same towers and Resampler, same process, timed first"}
 
 
+def log_images_bench(res, dev):
+    model = factory.build_synthetic_model(res, dev, seed=123, overrides={"image_proj_stage_config": RESAMPLER_MDM, "first_stage_key": "dense_frames",
+                                                                         "uncond_prob": 0.05}).eval()
+    g = torch.Generator(device=dev).manual_seed(7)
+    rn = lambda *s: torch.randn(*s, generator=g, device=dev)
+    model.cond_stage_model = _Tower(rn(1, 77, 1024), rn(1, 77, 1024))
+    model.embedder = _Tower(rn(1, 257, 1280))
+    h, w = PIXELS[res]
+    clip = lambda: rn(1, 3, 16, h, w).clamp(-1, 1)
+    batch = {"dense_frames": clip(), "sparse_frames": clip(), "sparse_depth": clip(), "class_label": torch.tensor([[500]], device=dev),
+             "caption": ["a street"], "fps": torch.tensor([10], device=dev)}
+    kw = dict(ddim_eta=0.0, unconditional_guidance_scale=7.5)
+
+    def timed(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    model.log_images(batch, ddim_steps=2, **kw)              # warm-up: packed weights, kernel plans, allocator
+    calls = [timed(lambda: model.log_images(batch, ddim_steps=50, **kw)) for _ in range(3)]
+    # the sampler alone on the same conditioning: 2 x 50 guided steps
+    z, _, c, fs, label = model.get_batch_input(batch, random_uncond=False, return_fs=True, return_class_label=True)
+    zero = torch.zeros_like(batch["dense_frames"][:, :, 0])
+    uc = {"c_concat": c["c_concat"], "c_crossattn": [torch.cat([model.get_learned_conditioning([""]), model.image_proj_model(model.embedder(zero))], 1)]}
+    run = lambda: model.sample_log(cond=c, batch_size=1, ddim=True, ddim_steps=50, eta=0.0, unconditional_guidance_scale=7.5,
+                                   unconditional_conditioning=uc, fs=fs.long(), class_label=label)
+    run()
+    hundred = timed(lambda: (run(), run()))
+    t_in = timed(lambda: model.get_batch_input(batch, random_uncond=False, return_first_stage_outputs=True))
+    return {"workload": f"MDM{res} log_images: one sample, 50 DDIM steps, guidance 7.5, eta 0, from a pixel batch (3 x 16 frames of {h} x {w})",
+            "log_images_s": [round(v, 3) for v in calls], "sampler_100_steps_s": round(hundred, 3),
+            "get_batch_input_with_reconst_s": round(t_in, 3),
+            "note": "log_images = get_batch_input (3 encodes + the decode of reconst) + 50 guided steps + the decode of samples"}
+
+
+if "--log-images" in sys.argv:
+    import json
+    with torch.no_grad():
+        for r_ in [a for a in sys.argv[1:] if a in PIXELS] or ["512"]:
+            print(json.dumps(log_images_bench(r_, torch.device("cuda:0"))), flush=True)
+    sys.exit(0)
+
 if "--from-pixels" in sys.argv:
     import json
     for r_ in [a for a in sys.argv[1:] if a in PIXELS] or ["512", "1024"]:
@@ -126,13 +178,18 @@ clip = step.GradientClipper([p for g in opt.param_groups for p in g["params"]], 
 batch = dict(x_start=inp["x_T"], cond=inp["cond"], t=torch.tensor([500, 120, 870, 333][:B], device=dev), class_label=inp["class_label"], fs=inp["fs"])
 torch.cuda.reset_peak_memory_stats()
 times, losses = [], []
+EMA = "--ema" in sys.argv[3:]
+ema = None                                   # set for the second block of steps
 def one_step():
     opt.zero_grad(set_to_none=False)         # multi-tensor fill; gradient tensors (and the pointer tables built on them) persist
     for _ in range(ACC):
         loss = model.training_step(batch)
         (loss / ACC).backward()
     norm = clip() if clip is not None else None
-    opt.step()
+    if ema is not None:
+        opt.step(ema=ema)
+    else:
+        opt.step()
     return loss, norm
 
 
@@ -143,6 +200,40 @@ for i in range(steps + 1):
     times.append(time.perf_counter() - t0)
     losses.append(float(loss.detach()))
     print(f"step {i}: loss {losses[-1]:.5f}  {times[-1]:.2f} s" + (f"  grad norm {float(norm[0]):.3f}" if norm is not None else ""), flush=True)
+ema_report = None
+if EMA:
+    from lvdm.ema import LitEma
+    ema = LitEma(model.model).to(dev)
+    ema_times = []
+    for i in range(steps + 1):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        loss, norm = one_step()
+        torch.cuda.synchronize()
+        ema_times.append(time.perf_counter() - t0)
+        print(f"step {i} (fused average): loss {float(loss.detach()):.5f}  {ema_times[-1]:.2f} s", flush=True)
+    from mudg_amd.train import kernels as K_
+    pairs_ = ema.pairs()
+    nparam = sum(s_.numel() for _, s_ in pairs_)
+    tab_e, n_e = ema._table(("ema", len(pairs_)), pairs_)          # the kernels alone, on their prebuilt tables: no host work per call
+    tab_s, n_s = ema._table(("swap", len(pairs_)), pairs_)
+    def _tbs(fn, bytes_per_param, reps=20):
+        fn(); torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record(); torch.cuda.synchronize()
+        ms = a.elapsed_time(b) / reps
+        return round(ms, 3), round(bytes_per_param * nparam / (ms / 1e3) / 1e12, 2)
+    keep = [p.detach().clone() for p in model.model.parameters()]
+    ema_ms, ema_tbs = _tbs(lambda: K_.ema_multi_(tab_e, n_e, 1e-4), 12)
+    swap_ms, swap_tbs = _tbs(lambda: (K_.swap_multi_(tab_s, n_s), K_.swap_multi_(tab_s, n_s)), 32)        # an even count: the weights end where they were
+    assert all(torch.equal(a_, b_) for a_, b_ in zip(keep, model.model.parameters()))
+    del keep
+    ema_report = {"s_per_step_plain": round(min(times[1:]), 4), "s_per_step_fused_average": round(min(ema_times[1:]), 4), "averaged_parameters": nparam,
+                  "ema_multi_ms": ema_ms, "ema_multi_tb_per_s": ema_tbs, "swap_multi_ms": round(swap_ms / 2, 3), "swap_multi_tb_per_s": swap_tbs}
+    print("averaged weights:", ema_report, flush=True)
+    ema = None
 from mudg_amd import hip
 hip.prof_reset(); hip.prof_enable((1 << len(hip.FAM_NAMES)) - 1)
 one_step()
@@ -162,7 +253,7 @@ if "json" in sys.argv[3:]:
     print(json.dumps({"workload": f"MDM{res} training step: p_losses -> backward -> AdamW, full 1.44 B-parameter UNet, B = {B}, 16 frames"
                                   + (f", {ACC} micro-batches per optimiser step" if ACC > 1 else ""),
                       "s_per_step": round(best, 4), "steps": steps, "tflops_per_s": round(fl / best, 1), "tflop_per_step": round(fl, 1),
-                      "flop_accounting": "3 x the forward per clip", "batch": B, "accumulate": ACC, "roofline": roof, "checkpointing": ckpt, "stage2_settings": stage2,
+                      "flop_accounting": "3 x the forward per clip", "batch": B, "accumulate": ACC, "roofline": roof, "checkpointing": ckpt, "stage2_settings": stage2, **({"averaged_weights": ema_report} if ema_report else {}),
                       "peak_memory_gib": round(torch.cuda.max_memory_allocated() / 2**30, 1), "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)]}))
     sys.exit(0)
 print(f"MDM{res} training step (B = {B}" + (f" x {ACC} micro-batches" if ACC > 1 else "") + f", 16 frames, checkpointing {'on' if ckpt else 'off'}{', stage-2 settings' if stage2 else ''}): {best:.2f} s = {fl / best:.1f} TFLOP/s of the "
