@@ -316,6 +316,31 @@ int mudg_depth_from_u8(const uint8_t* frames, float* depth, int64_t pixels, void
 int mudg_log_sheet(const float* video, uint8_t* out, int N, int C, int T, int H, int W, int clamp, int rescale, void* stream);
 int mudg_semantic_nearest(const uint8_t* img, uint8_t* vis, int64_t* labels, int64_t hw, void* stream);
 
+/* ------------------------------------------------------------------ sparse conditions: point splat at virtual poses
+ * (data_process/tools/generate_sparse.py:116-223 asks this of OpenGL point sprites; DESIGN.md §12 states the raster rule.)
+ * A cloud is n points of 16 bytes: x, y, z fp32 and the colour in the fourth word (r | g << 8 | b << 16).
+ * splat_points: every point is projected with each of `poses` matrices (mats[pose][nmat][12] fp32, the top three rows of
+ *   w2c (@ transform_obj), row-major; ids == NULL: nmat = 1, else matrix ids[point] of the pose), culled unless
+ *   znear < zc < zfar, and every pixel (row j, column i) with u - s/2 <= i + 0.5 < u + s/2 (likewise v, j), s = point_size,
+ *   takes the unsigned 64-bit minimum of (bits(zc) << 32 | point index) in keys[pose][H][W], which the caller set to all ones
+ *   before the first call (splat_resolve leaves it so).  flags: MUDG_SPLAT_NO_EARLY_REJECT issues the atomic without
+ *   looking at the pixel first (measurements).  stats (or NULL): two counters, covered pixels and issued atomics, added to.
+ * splat_resolve: keys -> depth (zc of the winner, 0 where nothing landed) and colour (the winner's fourth word, 0 likewise)
+ *   over `pixels` = poses * H * W pixels; every key is set to all ones again.  `points` is the cloud the keys index.
+ * splat_compose: mask = 13 x 13 box dilation (= three 5 x 5 ones) of all(obj rgb > 0), outside the image unset; colour and
+ *   depth are the object's under the mask and the background's elsewhere (obj_* == NULL: the background); then
+ *   sparse_frames[pose][c][t][y][x] = (rgb / 255 - 0.5) * 2 and sparse_depth[pose][c][t][y][x] = (clamp(depth, 0, 100) / 100 - 0.5) * 2,
+ *   c = 0..2, tensors (3, T, H, W) per pose, pose_stride elements apart.  rgb_out (poses, H, W, 3) uint8, depth_out
+ *   (poses, H, W) fp32 and mask_out (poses, H, W) uint8 are optional (NULL). */
+#define MUDG_SPLAT_NO_EARLY_REJECT 1
+int mudg_splat_points(const void* points, const int32_t* ids, int64_t n, const float* mats, int poses, int nmat,
+                      uint64_t* keys, int H, int W, float fx, float fy, float cx, float cy, float znear, float zfar,
+                      float point_size, int flags, uint64_t* stats, void* stream);
+int mudg_splat_resolve(uint64_t* keys, const void* points, int64_t n, float* depth, uint32_t* colour, int64_t pixels, void* stream);
+int mudg_splat_compose(const uint32_t* bg_colour, const float* bg_depth, const uint32_t* obj_colour, const float* obj_depth,
+                       float* sparse_frames, float* sparse_depth, int64_t pose_stride, int poses, int T, int t, int H, int W,
+                       uint8_t* rgb_out, float* depth_out, uint8_t* mask_out, void* stream);
+
 /* ------------------------------------------------------------------ training step
  * Reference: lvdm/models/ddpm3d.py:741-802 (p_losses), :1267-1300 (configure_optimizers -> torch.optim.AdamW),
  * main/utils_train.py:126-137 (data-parallel strategy).  The contractions of the backward pass (dX = dY W, dW = dY^T X,

@@ -147,6 +147,9 @@ SIGNATURES = {
     "mudg_log_sheet": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mudg_depth_from_u8": (_I, [_P, _P, _L, _P]),
     "mudg_semantic_nearest": (_I, [_P, _P, _P, _L, _P]),
+    "mudg_splat_points": (_I, [_P, _P, _L, _P, _I, _I, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P]),
+    "mudg_splat_resolve": (_I, [_P, _P, _L, _P, _P, _L, _P]),
+    "mudg_splat_compose": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mudg_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_float), _P, _P]),
     "mudg_gaussian_sample": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "mudg_posterior_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _F, _P]),

@@ -672,3 +672,78 @@ def semantic_nearest(img):
     hip.check(hip.lib().mudg_semantic_nearest(x.data_ptr(), vis.data_ptr(), lab.data_ptr(), x.shape[1] * x.shape[2], _stream()),
               "mudg_semantic_nearest")
     return vis, lab
+
+
+# ------------------------------------------------------------------------------------------------ sparse conditions (point splat)
+def _splat_tensor(name, t, dtype, shape=None):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise hip.MudgError(f"{name}: expected a contiguous {dtype} tensor on the GPU" + (f" of shape {tuple(shape)}" if shape else "") + f", got {got}")
+    return t
+
+
+def splat_keys(poses, h, w, device):
+    """An empty key image (poses, h, w): all ones, which is how splat_resolve leaves it."""
+    return torch.full((poses, h, w), -1, dtype=torch.int64, device=device)
+
+
+def splat_points(points, mats, keys, intr, point_size, *, ids=None, znear=1e-4, zfar=200.0, early_reject=True, stats=None):
+    """Draw a packed cloud (n, 4) int32 — x, y, z fp32 bits and r | g << 8 | b << 16 — into keys (poses, h, w) int64 with the
+    matrices mats (poses, nmat, 12) fp32 (ids (n,) int32 choose among nmat > 1) and intr = (fx, fy, cx, cy): per covered pixel the
+    unsigned minimum of (bits(zc) << 32 | index).  DESIGN.md §12 states the rule.  stats: a (2,) int64 counter pair (tools)."""
+    _splat_tensor("splat_points: points", points, torch.int32)
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
+        raise hip.MudgError(f"splat_points: expected packed points (n > 0, 4), got {tuple(points.shape)}")
+    _splat_tensor("splat_points: mats", mats, torch.float32)
+    _splat_tensor("splat_points: keys", keys, torch.int64)
+    if mats.dim() != 3 or mats.shape[2] != 12 or keys.dim() != 3 or keys.shape[0] != mats.shape[0]:
+        raise hip.MudgError(f"splat_points: matrices {tuple(mats.shape)} do not go with a key image {tuple(keys.shape)}")
+    n, (poses, nmat) = points.shape[0], mats.shape[:2]
+    if ids is not None:
+        _splat_tensor("splat_points: ids", ids, torch.int32, (n,))
+    if stats is not None:
+        _splat_tensor("splat_points: stats", stats, torch.int64, (2,))
+    fx, fy, cx, cy = (float(v) for v in intr)
+    hip.check(hip.lib().mudg_splat_points(points.data_ptr(), _ptr(ids), n, mats.data_ptr(), poses, nmat, keys.data_ptr(), keys.shape[1], keys.shape[2],
+                                          fx, fy, cx, cy, float(znear), float(zfar), float(point_size), 0 if early_reject else 1,
+                                          _ptr(stats), _stream()), "mudg_splat_points")
+    return keys
+
+
+def splat_resolve(keys, points):
+    """keys (poses, h, w) -> (depth fp32, colour int32 = r | g << 8 | b << 16) of the winners, zero where nothing landed; the key image
+    is empty again afterwards."""
+    _splat_tensor("splat_resolve: keys", keys, torch.int64)
+    _splat_tensor("splat_resolve: points", points, torch.int32)
+    depth = torch.empty(keys.shape, dtype=torch.float32, device=keys.device)
+    colour = torch.empty(keys.shape, dtype=torch.int32, device=keys.device)
+    hip.check(hip.lib().mudg_splat_resolve(keys.data_ptr(), points.data_ptr(), points.shape[0], depth.data_ptr(), colour.data_ptr(), keys.numel(),
+                                           _stream()), "mudg_splat_resolve")
+    return depth, colour
+
+
+def splat_compose(bg, obj, sparse_frames, sparse_depth, t, *, images=False):
+    """bg / obj = (depth, colour) pairs of splat_resolve (obj None: no object layer); writes frame t of sparse_frames and sparse_depth
+    (poses, 3, T, h, w) fp32.  images: also returns (rgb (poses, h, w, 3) uint8, depth (poses, h, w) fp32, mask (poses, h, w) uint8)."""
+    bg_d, bg_c = bg
+    poses, h, w = bg_d.shape
+    _splat_tensor("splat_compose: background depth", bg_d, torch.float32)
+    _splat_tensor("splat_compose: background colour", bg_c, torch.int32, (poses, h, w))
+    ob_d = ob_c = None
+    if obj is not None:
+        ob_d = _splat_tensor("splat_compose: object depth", obj[0], torch.float32, (poses, h, w))
+        ob_c = _splat_tensor("splat_compose: object colour", obj[1], torch.int32, (poses, h, w))
+    _splat_tensor("splat_compose: sparse_frames", sparse_frames, torch.float32)
+    _splat_tensor("splat_compose: sparse_depth", sparse_depth, torch.float32, sparse_frames.shape)
+    if sparse_frames.dim() != 5 or sparse_frames.shape[0] != poses or sparse_frames.shape[1] != 3 or tuple(sparse_frames.shape[3:]) != (h, w):
+        raise hip.MudgError(f"splat_compose: conditions {tuple(sparse_frames.shape)} for {poses} poses of {h} x {w}")
+    T = sparse_frames.shape[2]
+    rgb = depth = mask = None
+    if images:
+        rgb = torch.empty((poses, h, w, 3), dtype=torch.uint8, device=bg_d.device)
+        depth = torch.empty((poses, h, w), dtype=torch.float32, device=bg_d.device)
+        mask = torch.empty((poses, h, w), dtype=torch.uint8, device=bg_d.device)
+    hip.check(hip.lib().mudg_splat_compose(bg_c.data_ptr(), bg_d.data_ptr(), _ptr(ob_c), _ptr(ob_d), sparse_frames.data_ptr(), sparse_depth.data_ptr(),
+                                           3 * T * h * w, poses, T, int(t), h, w, _ptr(rgb), _ptr(depth), _ptr(mask), _stream()),
+              "mudg_splat_compose")
+    return (rgb, depth, mask) if images else None

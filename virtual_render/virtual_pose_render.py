@@ -108,3 +108,36 @@ def synthesize_windows(model, windows, noise_shape, video_length=16, **synthesis
             if int(win["class_label"][nn, 0]) == 0:                        # the colour stream re-feeds itself
                 carry = samples[nn, 0, :, half:video_length].to(sparse.device)      # (c, half, h, w)
     return results
+
+
+def render_windows(scene, dense_frames, pose, video_length=16):
+    """Yields the window dicts `synthesize_windows` consumes, with the sparse conditions rendered on the GPU from the scene's point
+    clouds (mudg_amd/render.py) instead of read from pre-rendered files.
+
+    scene: mudg_amd.render.Scene (background cloud, objects, intrinsics, per-frame c2w, native size).  dense_frames:
+    (3, c, frames, h, w) in [-1, 1], the colour / depth / semantic dense streams of the whole clip; decoding camera files is host I/O
+    and stays with the caller; (h, w) is the size rendered at.  pose: 0, 1 or 2 — the original camera or the reference's virtual pose 1
+    (2 m to the left) or 2 (2 m to the right), its move_id — or a (4, 4) camera-from-virtual-camera matrix applied to every frame's
+    c2w.  As in the reference's loaders (virtual_render/data_tools.py:40, 61, 153, 212) the three streams carry the same sparse
+    colour and sparse depth, class labels 0, 500 and 1, and sparse frame 0 of every stream is that stream's dense frame 0; windows
+    advance by video_length // 2 (virtual_pose_render.py:246 there)."""
+    import numpy as np
+    from mudg_amd import render
+    c2w = np.asarray(scene.c2w, dtype=np.float64)
+    frames = c2w.shape[0]
+    if dense_frames.dim() != 5 or dense_frames.shape[0] != 3 or dense_frames.shape[2] != frames:
+        raise ValueError(f"render_windows: dense_frames {tuple(dense_frames.shape)} for three streams of {frames} frames")
+    if np.ndim(pose) == 0:
+        cams = np.stack([render.virtual_poses(c, with_ori_pose=True)[int(pose)] for c in c2w])
+    else:
+        cams = c2w @ np.asarray(pose, dtype=np.float64)
+    intr = np.broadcast_to(np.asarray(scene.intr, dtype=np.float64), (frames, 3, 3))
+    labels = torch.tensor(render.CLASS_LABELS, dtype=torch.long)[:, None]
+    for start in range(0, frames - video_length + 1, max(video_length // 2, 1)):
+        sel = slice(start, start + video_length)
+        cond = render.render_conditions(scene.background, scene.objects, intr[sel], c2w[sel], scene.hw_native, dense_frames.shape[-2:],
+                                        poses=cams[sel, None], frame_ids=range(start, start + video_length))
+        dense = dense_frames[:, :, sel]
+        sparse = cond["sparse_frames"].repeat(3, 1, 1, 1, 1)
+        sparse[:, :, 0] = dense[:, :, 0].to(sparse.device)
+        yield {"sparse": sparse, "dense": dense, "sparse_depth": cond["sparse_depth"].repeat(3, 1, 1, 1, 1), "class_label": labels}
