@@ -7,7 +7,9 @@ flash-attention kernels (32 / 64 queries per wave) forced, the LDS-table GroupNo
 (the defaults are the register-table kernel and the MFMA kernel), the 3x3 convs without the shared activation stage of their dx taps, the 288 x 320 tile forced for every problem it can run (and, in
 that child, its bit-identity with the 128 x 128 kernels: test_wide288_is_bit_identical_to_the_one_tile_kernels), the two-workgroup
 144 x 256 GEGLU kernel of round 6 forced for every GEGLU problem (both K-loop forms) and switched off, the 160 x 320 tile of round 6 forced
-for every problem it can run (test_wide160_is_bit_identical_to_the_one_tile_kernels runs in the children)."""
+for every problem it can run (test_wide160_is_bit_identical_to_the_one_tile_kernels runs in the children).  The attention dispatcher's A/B
+switches (MUDG_ATTN_Q, and MUDG_ATTN_DMA=0 / MUDG_ATTN_LEAN=0 / MUDG_ATTN_X=0: the register-staged 64-query kernel on whole key tiles, the
+classic softmax on prescaled Q, the one-tile kernel on many-tile cross-attention) run tests/test_attention_kernels_gpu.py."""
 import os
 import subprocess
 import sys
@@ -44,6 +46,9 @@ VARIANTS = [
 # (short K, GEGLU on the 288 x 256 tile, ragged M — the rule sends none of those to it), and switched off (every conv / temporal conv
 # on the fused-piece 128 x 128 kernels), under the mode-agnostic kernel suite and the UNet parity tests.
 VARIANTS_X3 = [{"MUDG_GEMM_W288": "2"}, {"MUDG_GEMM_W288": "0"}]
+# The attention dispatcher's own switches: these children run the per-kernel attention file only
+VARIANTS_ATTN = [{"MUDG_ATTN_DMA": "0"}, {"MUDG_ATTN_LEAN": "0"}, {"MUDG_ATTN_X": "0"}]
+ATTN_FILE = "tests/test_attention_kernels_gpu.py"
 _name = lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items())
 
 
@@ -54,8 +59,11 @@ def children():
     runs = ChildRuns(workers=4)
     for i, env in enumerate(VARIANTS):
         runs.submit(_name(env), [sys.executable, "-m", "pytest", "tests/test_kernels_gpu.py", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py",
-                                 "-m", "gpu", "-q", "-k", SELECT, "-p", "no:cacheprovider"],
+                                 *([ATTN_FILE] if "MUDG_ATTN_Q" in env else []), "-m", "gpu", "-q", "-k", SELECT, "-p", "no:cacheprovider"],
                     ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", **env), 900, alone=(i == 0))
+    for env in VARIANTS_ATTN:
+        runs.submit(_name(env), [sys.executable, "-m", "pytest", ATTN_FILE, "-m", "gpu", "-q", "-p", "no:cacheprovider"],
+                    ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", **env), 900)
     for env in VARIANTS_X3:
         runs.submit("x3:" + _name(env), [sys.executable, "-m", "pytest", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py", "-m", "gpu", "-q",
                                          "-p", "no:cacheprovider"],
@@ -65,7 +73,7 @@ def children():
     runs.shutdown()
 
 
-@pytest.mark.parametrize("env", VARIANTS, ids=_name)
+@pytest.mark.parametrize("env", VARIANTS + VARIANTS_ATTN, ids=_name)
 def test_kernel_parity_under_variant(cuda, env, request):
     if os.environ.get("MUDG_DEBUG_VARIANTS") == "1":
         pytest.skip("already running under a variant switch")

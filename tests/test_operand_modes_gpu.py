@@ -484,7 +484,8 @@ def test_cross_attention_with_resident_key_tiles_walks_many_query_tiles(cuda):
     assert torch.equal(value(sub2), value(both)[:nq]) and torch.equal(value(sub1), value(one)[:nq])
 
 
-@pytest.mark.skipif(_hip.planes() > 1, reason="the lean softmax belongs to the 16-bit builds' long self-attention kernel")
+@pytest.mark.skipif(_hip.planes() > 2, reason="bf16x6 has no lean softmax: its one attention kernel runs the classic loop, which "
+                                              "tests/test_attention_kernels_gpu.py holds to prescaled Q")
 @pytest.mark.parametrize("spread", [1.0, 4.0, 12.0])
 def test_attention_lean_softmax_with_prescaled_q(cuda, spread):
     """q_prescaled: Q carries scale * log2(e), the kernel exponentiates Q K^T directly with the first tile's row maximum
