@@ -23,17 +23,15 @@
 //
 // mudg_temporal_attention: T <= 32 keys per pixel — a bandwidth problem.  One wave per (pixel, head), fp32 VALU
 //   dot products with K/V of that pixel in LDS; no MFMA.
-#include "common.h"
+// The steps the flash kernels below share — work-item numbering, tile loads with the ragged tail, the softmax steps, the
+// padded-tile flash step, the epilogues, the DMA geometry — are written once in attn_shared.h (xcd_work_item: common.h).
+#include "attn_shared.h"
 #include <cstdlib>
-#include <type_traits>
 
 namespace {
 
-constexpr int QB = 128;     // query rows per workgroup
-constexpr int KB = 64;      // keys per tile
-constexpr int ALD = 72;     // LDS row stride in h16 (64 + 8 pad -> 144 B)
-constexpr int ATILE = 64 * ALD;
-
+#if MUDG_PLANES == 1
+// ------------------------------------------------------------------------------------------------ 16-bit builds
 // TWO: a second key / value set (p.K2 / p.Vt2: the image tokens) with its own softmax follows the first; the two
 // normalised results are summed in registers and stored once.
 template <bool TWO>
@@ -44,206 +42,54 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const MudgAttnDesc p, cons
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
 
-    // XCD-aware numbering: hardware places block b on XCD b % 8; give each XCD a contiguous range of work items.
-    int w;
-    {
-        const int q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    const int w = xcd_work_item(total);
     const int pair = w / nqt, qt = w - pair * nqt;
     const int f = pair / p.heads, h = pair - f * p.heads;
     const h16* Qp = reinterpret_cast<const h16*>(p.Q) + (int64_t)f * p.Nq * p.ldq + h * 64;
     h16* Op = reinterpret_cast<h16*>(p.O) + (int64_t)f * p.Nq * p.ldo + h * 64;
-    // the key / value set being walked (set 0, then set 1 when TWO)
-    const h16* Kp = reinterpret_cast<const h16*>(p.K) + (int64_t)(f / p.kv_div) * p.Nk * p.ldk + h * 64;
-    const h16* Vp = reinterpret_cast<const h16*>(p.Vt) + (int64_t)(f / p.kv_div) * p.svt + (int64_t)(h * 64) * p.ldvt;
-    int Nk = p.Nk, ldk = p.ldk, ldvt = p.ldvt;
 
     const int q = qt * QB + wave * 32 + l31;
     const bool qok = q < p.Nq;
 
-    h16x8 qf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-        qf[ks] = as_h16x8(qok ? ld16(Qp + (int64_t)q * p.ldq + ks * 16 + hi * 8) : zero16());
+    h16x8 qf[1][4];
+    load_q_frags(qf[0], Qp, q, p.ldq, 0, qok, hi);
 
     const int lrow = tid >> 3, kc = tid & 7;   // staging: rows lrow, lrow+32; 16-byte chunk kc
-    u32x4 kr[2], vr[2];
-    auto load_tiles = [&](int kt) {
-        const int j0 = kt * KB;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = lrow + 32 * i;
-            const int j = j0 + row;                       // key index for the K tile row
-            kr[i] = (j < Nk) ? ld16(Kp + (int64_t)j * ldk + kc * 8) : zero16();
-            const int jc = j0 + kc * 8;                   // first key of this V^T chunk (row = head-dim index)
-            u32x4 v = zero16();
-            if (jc < Nk) {
-                v = ld16(Vp + (int64_t)row * ldvt + jc);
-                if (jc + 8 > Nk) {                       // ragged tail: keys >= Nk must contribute exactly 0
-                    h16x8 hv = as_h16x8(v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) if (jc + e >= Nk) hv[e] = (h16)0.f;
-                    v = as_u32x4(hv);
-                }
-            }
-            vr[i] = v;
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            st16(&Ks[buf * ATILE + (lrow + 32 * i) * ALD + kc * 8], kr[i]);
-            st16(&Vs[buf * ATILE + (lrow + 32 * i) * ALD + kc * 8], vr[i]);
-        }
-    };
+    u32x4 kr[1][2], vr[1][2];
 
     f32x16 o[2], res[TWO ? 2 : 1];
     const float c = p.q_prescaled ? 1.0f : p.scale * 1.4426950408889634f;   // scores are exponentiated in base 2
     float inv = 0.f;
 #pragma unroll
     for (int set = 0; set < (TWO ? 2 : 1); ++set) {
-    if (TWO && set == 1) {
-        Kp = reinterpret_cast<const h16*>(p.K2) + (int64_t)(f / p.kv_div2) * p.Nk2 * p.ldk2 + h * 64;
-        Vp = reinterpret_cast<const h16*>(p.Vt2) + (int64_t)(f / p.kv_div2) * p.svt2 + (int64_t)(h * 64) * p.ldvt2;
-        Nk = p.Nk2; ldk = p.ldk2; ldvt = p.ldvt2;
-    }
+        const KvSet kv = kv_set(p, f, h, set);   // the key / value set being walked
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
-    float m_run = -INFINITY, l_run = 0.f;
+        for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
+        float m_run = -INFINITY, l_run = 0.f;
 
-    const int nkt = (Nk + KB - 1) / KB;
-    load_tiles(0);
-    stage(0);
-    __syncthreads();
-
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1;
-        const bool more = kt + 1 < nkt;
-        if (more) load_tiles(kt + 1);
-
-        // ---- S^T = K Q^T for the two 32-key sub-tiles
-        f32x16 s[2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[sub][r] = 0.f;
-            const h16* kp = Ks + cur * ATILE + (sub * 32 + l31) * ALD + hi * 8;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + ks * 16);
-                s[sub] = MFMA_32x32x16(kf, qf[ks], s[sub]);
-            }
-        }
-        if (kt * KB + KB > Nk) {   // ragged last tile
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int j = kt * KB + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (j >= Nk) s[sub][r] = -INFINITY;
-                }
-        }
-
-        // ---- online softmax (per query row = per lane; halves exchange once)
-        float mx = s[0][0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[0][r]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // The running maximum only moves during the first few tiles; when no row of this wave raised it, alpha is
-        // exactly 1 and the 32-register rescale of O (and its exp) is skipped — bit-identical, not a threshold trick.
-        const bool grew = !__all(mx <= m_run);
-        const float m_new = grew ? fmaxf(m_run, mx) : m_run;
-        const float alpha = grew ? __builtin_amdgcn_exp2f((m_run - m_new) * c) : 1.0f;
-        const float mc = m_new * c;
-        m_run = m_new;
-        float ps = 0.f;
-        h16x8 pk[2][2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e = __builtin_amdgcn_exp2f(fmaf(s[sub][r], c, -mc));   // explicit: contraction is off globally
-                ps += e;
-                pk[sub][r >> 3][r & 7] = (h16)e;
-            }
-        l_run = l_run * alpha + ps;
-        if (grew) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
-        }
-
-        // ---- O^T += V^T P^T ; contraction slots follow the key order the score MFMA left in registers
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-            const h16* vp = Vs + cur * ATILE + (dt * 32 + l31) * ALD + 4 * hi;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    const int kk = sub * 32 + jj * 16;
-                    const h16x4 lo = *reinterpret_cast<const h16x4*>(vp + kk);
-                    const h16x4 up = *reinterpret_cast<const h16x4*>(vp + kk + 8);
-                    h16x8 vf;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = up[e]; }
-                    o[dt] = MFMA_32x32x16(vf, pk[sub][jj], o[dt]);
-                }
-        }
-
-        if (more) stage(cur ^ 1);
+        const int nkt = (kv.Nk + KB - 1) / KB;
+        load_kv_tile(kv, 0, lrow, kc, kr, vr);
+        stage_padded(Ks, Vs, lrow, kc, kr, vr);
         __syncthreads();
-    }
 
-    // ---- normalise this set's result
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    inv = 1.f / l_tot;
-    if (!TWO && p.Lse && qok && hi == 0)               // log2-sum-exp of the scaled scores: P = 2^(c s - L) (mudg_attention_bwd)
-        p.Lse[((int64_t)f * p.Nq + q) * p.heads + h] = m_run * c + __log2f(l_tot);
-    if (TWO) {
-        if (set == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { res[0][r] = o[0][r] * inv; res[1][r] = o[1][r] * inv; }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { o[0][r] = fmaf(o[0][r], inv, res[0][r]); o[1][r] = fmaf(o[1][r], inv, res[1][r]); }
-            inv = 1.f;
+        for (int kt = 0; kt < nkt; ++kt) {
+            const int cur = kt & 1;
+            const bool more = kt + 1 < nkt;
+            if (more) load_kv_tile(kv, kt + 1, lrow, kc, kr, vr);
+            FLASH_TILE(Ks + cur * ATILE, Vs + cur * ATILE, qf, kt, kv.Nk, c, m_run, l_run, o, l31, hi);
+            if (more) stage_padded(Ks + (cur ^ 1) * ATILE, Vs + (cur ^ 1) * ATILE, lrow, kc, kr, vr);
+            __syncthreads();
         }
+        inv = finish_set<TWO>(p, set, f, h, q, qok, hi, c, m_run, l_run, o, res);
     }
-    }   // sets
-    // ---- store: lane holds, for its query row, head-dim columns dt*32 + 8g + 4*hi + {0..3}
-    if (qok) {
-        h16* orow = Op + (int64_t)q * p.ldo;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                h16* dst = orow + dt * 32 + 8 * g + 4 * hi;
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = o[dt][4 * g + j] * inv;
-                if (p.accumulate) {
-                    Pack8 old; old.u = *reinterpret_cast<const u32x2*>(dst);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] += (float)old.h[j];
-                }
-                Pack8 nw;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) nw.h[j] = (h16)v[j];
-                *reinterpret_cast<u32x2*>(dst) = nw.u;
-            }
-    }
+    if (qok) store_o16(o, inv, Op + (int64_t)q * p.ldo, hi, p.accumulate);
 }
 
 // Short key sets — the text (77) + image (16) tokens of the cross-attention — with MANY query tiles: the whole K / V^T of a (frame, head)
 // is three 64-key tiles, so a workgroup stages them ONCE and then walks `xq` query tiles of that (frame, head) with no barrier at all
 // (round 5).  attn_kernel stages the same three tiles for every 128 queries — 24 KB of K / V^T per 32 KB of Q + O — and its workgroup
 // lives for four dependent global round trips: 227 us for the level-0 launch (377 MB: 1.7 TB/s).  Per query row the arithmetic is
-// attn_kernel's, operation for operation: the same bits.
-#if MUDG_PLANES == 1
+// attn_kernel's by construction: both kernels run FLASH_TILE / finish_set / store_o16 on the same staged bytes — the same bits.
 constexpr int XK_TILES = 3;                      // key tiles held: two of the first set (Nk <= 128), one of the second (Nk2 <= 64)
 template <bool TWO>
 __global__ __launch_bounds__(256, 2) void xattn_kernel(const MudgAttnDesc p, const int nqt, const int xq, const int nqc, const int total) {
@@ -252,49 +98,25 @@ __global__ __launch_bounds__(256, 2) void xattn_kernel(const MudgAttnDesc p, con
     h16* Vs = xlds + XK_TILES * ATILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
-    int w;
-    {
-        const int q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    const int w = xcd_work_item(total);
     const int pair = w / nqc, qc = w - pair * nqc;
     const int f = pair / p.heads, h = pair - f * p.heads;
     const h16* Qp = reinterpret_cast<const h16*>(p.Q) + (int64_t)f * p.Nq * p.ldq + h * 64;
     h16* Op = reinterpret_cast<h16*>(p.O) + (int64_t)f * p.Nq * p.ldo + h * 64;
-    const int nt0 = (p.Nk + KB - 1) / KB;
+    const int nt0 = (p.Nk + KB - 1) / KB;         // set 0 lives in tiles [0, nt0), set 1 from nt0 on
 
-    // ---- stage every key tile of both sets (rows lrow, lrow + 32 of a tile; 16-byte chunk kc), as attn_kernel's load_tiles / stage
+    // ---- stage every key tile of both sets
     {
         const int lrow = tid >> 3, kc = tid & 7;
 #pragma unroll
         for (int set = 0; set < (TWO ? 2 : 1); ++set) {
-            const h16* Kp = set == 0 ? reinterpret_cast<const h16*>(p.K) + (int64_t)(f / p.kv_div) * p.Nk * p.ldk + h * 64
-                                     : reinterpret_cast<const h16*>(p.K2) + (int64_t)(f / p.kv_div2) * p.Nk2 * p.ldk2 + h * 64;
-            const h16* Vp = set == 0 ? reinterpret_cast<const h16*>(p.Vt) + (int64_t)(f / p.kv_div) * p.svt + (int64_t)(h * 64) * p.ldvt
-                                     : reinterpret_cast<const h16*>(p.Vt2) + (int64_t)(f / p.kv_div2) * p.svt2 + (int64_t)(h * 64) * p.ldvt2;
-            const int Nk = set == 0 ? p.Nk : p.Nk2, ldk = set == 0 ? p.ldk : p.ldk2, ldvt = set == 0 ? p.ldvt : p.ldvt2;
-            const int nkt = (Nk + KB - 1) / KB;
+            const KvSet kv = kv_set(p, f, h, set);
+            const int nkt = (kv.Nk + KB - 1) / KB;
             for (int kt = 0; kt < nkt; ++kt) {
-                const int ti = set == 0 ? kt : nt0 + kt, j0 = kt * KB;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int row = lrow + 32 * i, j = j0 + row;
-                    const u32x4 kr = (j < Nk) ? ld16(Kp + (int64_t)j * ldk + kc * 8) : zero16();
-                    const int jc = j0 + kc * 8;
-                    u32x4 v = zero16();
-                    if (jc < Nk) {
-                        v = ld16(Vp + (int64_t)row * ldvt + jc);
-                        if (jc + 8 > Nk) {
-                            h16x8 hv = as_h16x8(v);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) if (jc + e >= Nk) hv[e] = (h16)0.f;
-                            v = as_u32x4(hv);
-                        }
-                    }
-                    st16(&Ks[ti * ATILE + row * ALD + kc * 8], kr);
-                    st16(&Vs[ti * ATILE + row * ALD + kc * 8], v);
-                }
+                const int ti = set == 0 ? kt : nt0 + kt;
+                u32x4 kr[1][2], vr[1][2];
+                load_kv_tile(kv, kt, lrow, kc, kr, vr);
+                stage_padded(Ks + ti * ATILE, Vs + ti * ATILE, lrow, kc, kr, vr);
             }
         }
     }
@@ -306,10 +128,8 @@ __global__ __launch_bounds__(256, 2) void xattn_kernel(const MudgAttnDesc p, con
         if (qt >= nqt) break;
         const int q = qt * QB + wave * 32 + l31;
         const bool qok = q < p.Nq;
-        h16x8 qf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            qf[ks] = as_h16x8(qok ? ld16(Qp + (int64_t)q * p.ldq + ks * 16 + hi * 8) : zero16());
+        h16x8 qf[1][4];
+        load_q_frags(qf[0], Qp, q, p.ldq, 0, qok, hi);
         f32x16 o[2], res[TWO ? 2 : 1];
         float inv = 0.f;
 #pragma unroll
@@ -321,109 +141,13 @@ __global__ __launch_bounds__(256, 2) void xattn_kernel(const MudgAttnDesc p, con
             const int nkt = (Nk + KB - 1) / KB;
             for (int kt = 0; kt < nkt; ++kt) {
                 const int ti = set == 0 ? kt : nt0 + kt;
-                f32x16 sc[2];
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sc[sub][r] = 0.f;
-                    const h16* kp = Ks + ti * ATILE + (sub * 32 + l31) * ALD + hi * 8;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + ks * 16);
-                        sc[sub] = MFMA_32x32x16(kf, qf[ks], sc[sub]);
-                    }
-                }
-                if (kt * KB + KB > Nk) {
-#pragma unroll
-                    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int j = kt * KB + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                            if (j >= Nk) sc[sub][r] = -INFINITY;
-                        }
-                }
-                float mx = sc[0][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[0][r]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[1][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const bool grew = !__all(mx <= m_run);
-                const float m_new = grew ? fmaxf(m_run, mx) : m_run;
-                const float alpha = grew ? __builtin_amdgcn_exp2f((m_run - m_new) * c) : 1.0f;
-                const float mc = m_new * c;
-                m_run = m_new;
-                float ps = 0.f;
-                h16x8 pk[2][2];
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float e = __builtin_amdgcn_exp2f(fmaf(sc[sub][r], c, -mc));
-                        ps += e;
-                        pk[sub][r >> 3][r & 7] = (h16)e;
-                    }
-                l_run = l_run * alpha + ps;
-                if (grew) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
-                }
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const h16* vp = Vs + ti * ATILE + (dt * 32 + l31) * ALD + 4 * hi;
-#pragma unroll
-                    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                        for (int jj = 0; jj < 2; ++jj) {
-                            const int kk = sub * 32 + jj * 16;
-                            const h16x4 lo = *reinterpret_cast<const h16x4*>(vp + kk);
-                            const h16x4 up = *reinterpret_cast<const h16x4*>(vp + kk + 8);
-                            h16x8 vf;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = up[e]; }
-                            o[dt] = MFMA_32x32x16(vf, pk[sub][jj], o[dt]);
-                        }
-                }
+                FLASH_TILE(Ks + ti * ATILE, Vs + ti * ATILE, qf, kt, Nk, c, m_run, l_run, o, l31, hi);
             }
-            const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-            inv = 1.f / l_tot;
-            if (!TWO && p.Lse && qok && hi == 0)
-                p.Lse[((int64_t)f * p.Nq + q) * p.heads + h] = m_run * c + __log2f(l_tot);
-            if (TWO) {
-                if (set == 0) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { res[0][r] = o[0][r] * inv; res[1][r] = o[1][r] * inv; }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { o[0][r] = fmaf(o[0][r], inv, res[0][r]); o[1][r] = fmaf(o[1][r], inv, res[1][r]); }
-                    inv = 1.f;
-                }
-            }
+            inv = finish_set<TWO>(p, set, f, h, q, qok, hi, c, m_run, l_run, o, res);
         }
-        if (qok) {
-            h16* orow = Op + (int64_t)q * p.ldo;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    h16* dst = orow + dt * 32 + 8 * g + 4 * hi;
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = o[dt][4 * g + j] * inv;
-                    if (p.accumulate) {
-                        Pack8 old; old.u = *reinterpret_cast<const u32x2*>(dst);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += (float)old.h[j];
-                    }
-                    Pack8 nw;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) nw.h[j] = (h16)v[j];
-                    *reinterpret_cast<u32x2*>(dst) = nw.u;
-                }
-        }
+        if (qok) store_o16(o, inv, Op + (int64_t)q * p.ldo, hi, p.accumulate);
     }
 }
-#endif
 
 // Variant with 64 query rows per wave (two 32-row blocks): every K / V^T fragment read from LDS feeds two MFMAs instead
 // of one — half the LDS traffic per FLOP — and the two blocks' softmax chains are independent.  Workgroup = 256 queries.
@@ -433,19 +157,12 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(const MudgAttnDesc p, c
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
-    int w;
-    {
-        const int q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    const int w = xcd_work_item(total);
     const int pair = w / nqt, qt = w - pair * nqt;
     const int f = pair / p.heads, h = pair - f * p.heads;
-    const int kvb = f / p.kv_div;
+    const KvSet kv = kv_set(p, f, h, 0);
 
     const h16* Qp = reinterpret_cast<const h16*>(p.Q) + (int64_t)f * p.Nq * p.ldq + h * 64;
-    const h16* Kp = reinterpret_cast<const h16*>(p.K) + (int64_t)kvb * p.Nk * p.ldk + h * 64;
-    const h16* Vp = reinterpret_cast<const h16*>(p.Vt) + (int64_t)kvb * p.svt + (int64_t)(h * 64) * p.ldvt;
     h16* Op = reinterpret_cast<h16*>(p.O) + (int64_t)f * p.Nq * p.ldo + h * 64;
 
     int qrow[2];
@@ -455,44 +172,21 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(const MudgAttnDesc p, c
     for (int qb = 0; qb < 2; ++qb) {
         qrow[qb] = qt * 256 + wave * 64 + qb * 32 + l31;
         qok[qb] = qrow[qb] < p.Nq;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            qf[qb][ks] = as_h16x8(qok[qb] ? ld16(Qp + (int64_t)qrow[qb] * p.ldq + ks * 16 + hi * 8) : zero16());
+        load_q_frags(qf[qb], Qp, qrow[qb], p.ldq, 0, qok[qb], hi);
     }
 
     const int lrow = tid >> 3, kc = tid & 7;
-    u32x4 kr[2], vr[2];
-    auto load_tiles = [&](int kt) {
-        const int j0 = kt * KB;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = lrow + 32 * i;
-            const int j = j0 + row;
-            kr[i] = (j < p.Nk) ? ld16(Kp + (int64_t)j * p.ldk + kc * 8) : zero16();
-            const int jc = j0 + kc * 8;
-            u32x4 v = zero16();
-            if (jc < p.Nk) {
-                v = ld16(Vp + (int64_t)row * p.ldvt + jc);
-                if (jc + 8 > p.Nk) {
-                    h16x8 hv = as_h16x8(v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) if (jc + e >= p.Nk) hv[e] = (h16)0.f;
-                    v = as_u32x4(hv);
-                }
-            }
-            vr[i] = v;
-        }
-    };
+    u32x4 kr[1][2], vr[1][2];
     // V^T columns are stored permuted inside each group of 16 keys — [0-3, 8-11, 4-7, 12-15] — which is the order the score
     // MFMA leaves a lane's keys in: a lane's 8 contraction slots of a PV MFMA are then one 16-byte LDS read, not two of 8.
     const int vlo = (kc >> 1) * 16 + ((kc & 1) ? 4 : 0), vhi = (kc >> 1) * 16 + ((kc & 1) ? 12 : 8);
     auto stage = [&](int buf) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            st16(&Ks[buf * ATILE + (lrow + 32 * i) * ALD + kc * 8], kr[i]);
+            st16(&Ks[buf * ATILE + (lrow + 32 * i) * ALD + kc * 8], kr[0][i]);
             h16* vrow = &Vs[buf * ATILE + (lrow + 32 * i) * ALD];
-            *reinterpret_cast<u32x2*>(vrow + vlo) = u32x2{vr[i][0], vr[i][1]};
-            *reinterpret_cast<u32x2*>(vrow + vhi) = u32x2{vr[i][2], vr[i][3]};
+            *reinterpret_cast<u32x2*>(vrow + vlo) = u32x2{vr[0][i][0], vr[0][i][1]};
+            *reinterpret_cast<u32x2*>(vrow + vhi) = u32x2{vr[0][i][2], vr[0][i][3]};
         }
     };
 
@@ -505,14 +199,14 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(const MudgAttnDesc p, c
     const float c = p.q_prescaled ? 1.0f : p.scale * 1.4426950408889634f;
 
     const int nkt = (p.Nk + KB - 1) / KB;
-    load_tiles(0);
+    load_kv_tile(kv, 0, lrow, kc, kr, vr);
     stage(0);
     __syncthreads();
 
     for (int kt = 0; kt < nkt; ++kt) {
         const int cur = kt & 1;
         const bool more = kt + 1 < nkt;
-        if (more) load_tiles(kt + 1);
+        if (more) load_kv_tile(kv, kt + 1, lrow, kc, kr, vr);
 
         f32x16 s[2][2];        // [qb][sub]
 #pragma unroll
@@ -529,44 +223,12 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(const MudgAttnDesc p, c
                 s[1][sub] = MFMA_32x32x16(kf, qf[1][ks], s[1][sub]);
             }
         }
-        if (kt * KB + KB > p.Nk) {
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int j = kt * KB + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (j >= p.Nk) { s[0][sub][r] = -INFINITY; s[1][sub][r] = -INFINITY; }
-                }
-        }
 
-        h16x8 pk[2][2][2];     // [qb][sub][jj]
+        h16x8 pk[2][1][2][2];     // [qb][piece][sub][jj]
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
-            float mx = s[qb][0][0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[qb][0][r]);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[qb][1][r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const bool grew = !__all(mx <= m_run[qb]);
-            const float m_new = grew ? fmaxf(m_run[qb], mx) : m_run[qb];
-            const float alpha = grew ? __builtin_amdgcn_exp2f((m_run[qb] - m_new) * c) : 1.0f;
-            const float mc = m_new * c;
-            m_run[qb] = m_new;
-            float ps = 0.f;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float e = __builtin_amdgcn_exp2f(fmaf(s[qb][sub][r], c, -mc));
-                    ps += e;
-                    pk[qb][sub][r >> 3][r & 7] = (h16)e;
-                }
-            l_run[qb] = l_run[qb] * alpha + ps;
-            if (grew) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { o[qb][0][r] *= alpha; o[qb][1][r] *= alpha; }
-            }
+            mask_ragged(s[qb], kt, p.Nk, hi);
+            softmax_step_classic(s[qb], c, m_run[qb], l_run[qb], o[qb], pk[qb]);
         }
 
 #pragma unroll
@@ -577,8 +239,8 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(const MudgAttnDesc p, c
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
                     const h16x8 vf = *reinterpret_cast<const h16x8*>(vp + sub * 32 + jj * 16);
-                    o[0][dt] = MFMA_32x32x16(vf, pk[0][sub][jj], o[0][dt]);
-                    o[1][dt] = MFMA_32x32x16(vf, pk[1][sub][jj], o[1][dt]);
+                    o[0][dt] = MFMA_32x32x16(vf, pk[0][0][sub][jj], o[0][dt]);
+                    o[1][dt] = MFMA_32x32x16(vf, pk[1][0][sub][jj], o[1][dt]);
                 }
         }
 
@@ -587,32 +249,7 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(const MudgAttnDesc p, c
     }
 
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        const float l_tot = l_run[qb] + __shfl_xor(l_run[qb], 32, 64);
-        const float inv = 1.f / l_tot;
-        if (p.Lse && qok[qb] && hi == 0) p.Lse[((int64_t)f * p.Nq + qrow[qb]) * p.heads + h] = m_run[qb] * c + __log2f(l_tot);
-        if (qok[qb]) {
-            h16* orow = Op + (int64_t)qrow[qb] * p.ldo;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    h16* dst = orow + dt * 32 + 8 * g + 4 * hi;
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = o[qb][dt][4 * g + j] * inv;
-                    if (p.accumulate) {
-                        Pack8 old; old.u = *reinterpret_cast<const u32x2*>(dst);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += (float)old.h[j];
-                    }
-                    Pack8 nw;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) nw.h[j] = (h16)v[j];
-                    *reinterpret_cast<u32x2*>(dst) = nw.u;
-                }
-        }
-    }
+    for (int qb = 0; qb < 2; ++qb) finish_block16(p, f, h, qrow[qb], qok[qb], hi, c, m_run[qb], l_run[qb], o[qb], Op);
 }
 
 // ------------------------------------------------------------------------------------------------ LDS-DMA variant
@@ -631,24 +268,12 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(const MudgAttnDesc p, c
 //    the fragment reads: chunk c of row r lives in slot c ^ ((r >> 1) & 7).
 //  * The score MFMA leaves a lane's keys in the order {0-3, 8-11 | 4-7, 12-15} per 16; instead of permuting V^T's columns
 //    (8-byte granules — impossible for a 16-byte DMA) the K tile's ROWS are permuted at the source by the involution that
-//    swaps the two middle 4-blocks of every 16: softmax does not care in which order keys arrive, and a lane's 8
+//    swaps the two middle 4-blocks of every 16 (swap_mid4): softmax does not care in which order keys arrive, and a lane's 8
 //    contraction slots of a PV MFMA are then 8 consecutive keys = one natural 16-byte chunk of V^T.
 //  * Tile t + 1 is requested at the top of iteration t into the other buffer; the barrier that closes the iteration
 //    (vmcnt(0) + s_barrier) is the only synchronisation.
+// (softmax_step_lean, LEAN_LIMIT, lean_or_classic, dma_offsets: attn_shared.h — attn_split_dma_kernel uses them too.)
 constexpr int DTILE = 64 * 64;          // h16 per unpadded tile
-// Largest per-lane tile sum of 2^(s - m_ref) the lean softmax accepts before the workgroup falls back to the classic loop.
-// P is stored as h16: a bf16 P has fp32's exponent range (2^40 leaves room for the row sum), an IEEE-half P overflows to
-// inf beyond 65504 — there the limit is 2^15, so that no single exponential can reach the h16 maximum undetected.
-#ifdef MUDG_OPERAND_FP16
-constexpr float LEAN_LIMIT = 32768.f;
-#else
-constexpr float LEAN_LIMIT = 1099511627776.f;      // 2^40
-#endif
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t attn_rsrc(const h16* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(base), 0, (int)0x80000000u, 0x00020000);
-}
-typedef __attribute__((address_space(3))) void* attn_lptr_t;
 
 // F8 (needs LEAN): the scores come from MX-fp8 copies of Q and K (MudgAttnDesc.Q8 ...): one
 // v_mfma_scale_f32_32x32x64_f8f6f4 per (32 keys x 32 queries) block covers the whole head width at twice the bf16 MFMA
@@ -666,19 +291,13 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    int w;
-    {
-        const int q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    const int w = xcd_work_item(total);
     const int pair = w / nqt, qt = w - pair * nqt;
     const int f = pair / p.heads, h = pair - f * p.heads;
     const int kvb = f / p.kv_div;
 
     const h16* Qp = reinterpret_cast<const h16*>(p.Q) + (int64_t)f * p.Nq * p.ldq + h * 64;
-    const h16* Kp = reinterpret_cast<const h16*>(p.K) + (int64_t)kvb * p.Nk * p.ldk + h * 64;
-    const h16* Vp = reinterpret_cast<const h16*>(p.Vt) + (int64_t)kvb * p.svt + (int64_t)(h * 64) * p.ldvt;
+    const KvSet kv = kv_set(p, f, h, 0);
     h16* Op = reinterpret_cast<h16*>(p.O) + (int64_t)f * p.Nq * p.ldo + h * 64;
 
     int qrow[2];
@@ -702,9 +321,7 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
             qf8[qb] = i32x8{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
             if (qok[qb]) qsc[qb] = reinterpret_cast<const unsigned char*>(p.Qs)[((int64_t)f * p.Nq + qrow[qb]) * p.ldqs + h * 2 + hi];
         } else {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                qf[qb][ks] = as_h16x8(qok[qb] ? ld16(Qp + (int64_t)qrow[qb] * p.ldq + ks * 16 + hi * 8) : zero16());
+            load_q_frags(qf[qb], Qp, qrow[qb], p.ldq, 0, qok[qb], hi);
         }
     }
     if constexpr (F8) {
@@ -712,34 +329,21 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
         Ksp = reinterpret_cast<const unsigned char*>(p.Ks) + (int64_t)kvb * p.Nk * p.ldks + h * 2;
     }
 
-    // DMA geometry: wave w stages rows [16w, 16w + 16) of both tiles, two 1-KiB instructions each; in instruction i lane l
-    // lands in row 16w + 8i + (l >> 3), slot l & 7.  (F8 K tile: ONE instruction per wave, row 16w + (l >> 2), slot l & 3.)
+    // DMA geometry (dma_offsets): wave w stages rows [16w, 16w + 16) of both tiles, two 1-KiB instructions each.
+    // (F8 K tile: ONE instruction per wave, row 16w + (l >> 2), slot l & 3.)
     const __amdgpu_buffer_rsrc_t rK = F8 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(K8p), 0, (int)0x80000000u, 0x00020000)
-                                         : attn_rsrc(Kp);
-    const __amdgpu_buffer_rsrc_t rV = attn_rsrc(Vp);
+                                         : attn_rsrc(kv.Kp);
+    const __amdgpu_buffer_rsrc_t rV = attn_rsrc(kv.Vp);
     unsigned vk[2], vv[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = 16 * wave + 8 * i + (lane >> 3), slot = lane & 7;
-        const int chunk = slot ^ ((row >> 1) & 7);
-        const int i16 = row & 15;
-        const int key = (row & ~15) | (i16 & 3) | ((i16 & 8) >> 1) | ((i16 & 4) << 1);     // swap the middle 4-blocks
-        vk[i] = (unsigned)key * (unsigned)p.ldk * 2u + (unsigned)chunk * 16u;
-        vv[i] = (unsigned)row * (unsigned)p.ldvt * 2u + (unsigned)chunk * 16u;
-    }
+    dma_offsets(wave, lane, p.ldk, p.ldvt, vk, vv);
     int kscale_off[2] = {0, 0};      // F8: byte offsets (inside a tile) of this lane's K scales for sub-tiles 0 / 1
     if constexpr (F8) {
         const int row = 16 * wave + (lane >> 2), slot = lane & 3;
         const int chunk = slot ^ ((row >> 2) & 3);
-        const int i16 = row & 15;
-        const int key = (row & ~15) | (i16 & 3) | ((i16 & 8) >> 1) | ((i16 & 4) << 1);
-        vk[0] = (unsigned)key * (unsigned)p.ldk8 + (unsigned)chunk * 16u;
+        vk[0] = (unsigned)swap_mid4(row) * (unsigned)p.ldk8 + (unsigned)chunk * 16u;
 #pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            const int r = sub * 32 + l31, j16 = r & 15;
-            const int k = (r & ~15) | (j16 & 3) | ((j16 & 8) >> 1) | ((j16 & 4) << 1);      // the key LDS row r holds
-            kscale_off[sub] = k * p.ldks + hi;
-        }
+        for (int sub = 0; sub < 2; ++sub)
+            kscale_off[sub] = swap_mid4(sub * 32 + l31) * p.ldks + hi;      // the scale of the key LDS row sub * 32 + l31 holds
     }
     auto request = [&](int kt, int buf) {
         const int sv = kt * 128;
@@ -803,14 +407,7 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
                 score_block(0, sub, s0[0][sub], s0[1][sub], F8 ? (int)Ksp[kscale_off[sub]] : 127);
             }
 #pragma unroll
-            for (int qb = 0; qb < 2; ++qb) {
-                float mx = s0[qb][0][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s0[qb][0][r]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s0[qb][1][r]);
-                m_run[qb] = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            }
+            for (int qb = 0; qb < 2; ++qb) m_run[qb] = row_max32(s0[qb]);
         }
 
         int ksc[2] = {127, 127};          // F8: this tile's K scales (requested one tile ahead)
@@ -839,28 +436,17 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
             }
             if constexpr (F8) { ksc[0] = ksn[0]; ksc[1] = ksn[1]; }
 
-            h16x8 pk[2][2][2];     // [qb][sub][jj]
+            h16x8 pk[2][1][2][2];     // [qb][piece][sub][jj]
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb) {
                 if constexpr (LN) {
-                    float ps = 0.f;
-#pragma unroll
-                    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const float e = __builtin_amdgcn_exp2f(s[qb][sub][r]);
-                            ps += e;
-                            pk[qb][sub][r >> 3][r & 7] = (h16)e;
-                        }
-                    l_run[qb] += ps;
-                    overflow = overflow || !(ps <= LEAN_LIMIT);             // true for inf / nan as well
+                    const bool over = softmax_step_lean(s[qb], l_run[qb], pk[qb]);
+                    overflow = overflow || over;
                 } else {
-                    float mx = s[qb][0][0];
-#pragma unroll
-                    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[qb][0][r]);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[qb][1][r]);
-                    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                    // softmax_step_classic, spelled out: this kernel sits at its 256-register budget, and through the shared helper the
+                    // fp8 instantiation's cold fallback spills 8 bytes more than the 44 it has here.  It must stay equal to the
+                    // helper (attn_shared.h) operation for operation: a change to one is a change to both.
+                    const float mx = row_max32(s[qb]);
                     const bool grew = !__all(mx <= m_run[qb]);
                     const float m_new = grew ? fmaxf(m_run[qb], mx) : m_run[qb];
                     const float alpha = grew ? __builtin_amdgcn_exp2f((m_run[qb] - m_new) * c) : 1.0f;
@@ -873,7 +459,7 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
                         for (int r = 0; r < 16; ++r) {
                             const float e = __builtin_amdgcn_exp2f(fmaf(s[qb][sub][r], c, -mc));
                             ps += e;
-                            pk[qb][sub][r >> 3][r & 7] = (h16)e;
+                            put_p(pk[qb], sub, r, e);
                         }
                     l_run[qb] = l_run[qb] * alpha + ps;
                     if (grew) {
@@ -892,49 +478,19 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {
                         const h16x8 vf = *reinterpret_cast<const h16x8*>(vp + (((4 * sub + 2 * jj + hi) ^ sw) << 3));
-                        o[0][dt] = MFMA_32x32x16(vf, pk[0][sub][jj], o[0][dt]);
-                        o[1][dt] = MFMA_32x32x16(vf, pk[1][sub][jj], o[1][dt]);
+                        o[0][dt] = MFMA_32x32x16(vf, pk[0][0][sub][jj], o[0][dt]);
+                        o[1][dt] = MFMA_32x32x16(vf, pk[1][0][sub][jj], o[1][dt]);
                     }
             }
             __syncthreads();         // tile kt + 1 has landed (vmcnt(0)) and everyone is done reading tile kt
         }
     };
-
-    if constexpr (LEAN) {
-        key_loop(std::true_type{});
-        if (__syncthreads_or(overflow ? 1 : 0)) key_loop(std::false_type{});      // cold: exact, merely slower
-    } else {
-        key_loop(std::false_type{});
-    }
+    lean_or_classic<LEAN>(overflow, key_loop);
 
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        const float l_tot = l_run[qb] + __shfl_xor(l_run[qb], 32, 64);
-        const float inv = 1.f / l_tot;
-        if (p.Lse && qok[qb] && hi == 0) p.Lse[((int64_t)f * p.Nq + qrow[qb]) * p.heads + h] = m_run[qb] * c + __log2f(l_tot);
-        if (qok[qb]) {
-            h16* orow = Op + (int64_t)qrow[qb] * p.ldo;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    h16* dst = orow + dt * 32 + 8 * g + 4 * hi;
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = o[qb][dt][4 * g + j] * inv;
-                    if (p.accumulate) {
-                        Pack8 old; old.u = *reinterpret_cast<const u32x2*>(dst);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] += (float)old.h[j];
-                    }
-                    Pack8 nw;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) nw.h[j] = (h16)v[j];
-                    *reinterpret_cast<u32x2*>(dst) = nw.u;
-                }
-        }
-    }
+    for (int qb = 0; qb < 2; ++qb) finish_block16(p, f, h, qrow[qb], qok[qb], hi, c, m_run[qb], l_run[qb], o[qb], Op);
 }
+#endif  // MUDG_PLANES == 1
 
 // ------------------------------------------------------------------------------------------------ temporal
 // TP = padded sequence length (16 or 32); DP = 64 / TP lanes share one query row, each owning DW = 64 / DP dims.
@@ -1196,184 +752,60 @@ __global__ __launch_bounds__(256, PLANES == 2 ? 2 : 1) void attn_split_kernel(co
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
-    int w;
-    {
-        const int q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    const int w = xcd_work_item(total);
     const int pair = w / nqt, qt = w - pair * nqt;
     const int f = pair / p.heads, h = pair - f * p.heads;
     const int psq = p.ldq / PLANES, pso = p.ldo / PLANES;
-    int psk = p.ldk / PLANES, psv = p.ldvt / PLANES;
 
     const h16* Qp = reinterpret_cast<const h16*>(p.Q) + (int64_t)f * p.Nq * p.ldq + h * 64;
     h16* Op = reinterpret_cast<h16*>(p.O) + (int64_t)f * p.Nq * p.ldo + h * 64;
-    const h16* Kp = reinterpret_cast<const h16*>(p.K) + (int64_t)(f / p.kv_div) * p.Nk * p.ldk + h * 64;
-    const h16* Vp = reinterpret_cast<const h16*>(p.Vt) + (int64_t)(f / p.kv_div) * p.svt + (int64_t)(h * 64) * p.ldvt;
-    int Nk = p.Nk, ldk = p.ldk, ldvt = p.ldvt;
 
     const int q = qt * QB + wave * 32 + l31;
     const bool qok = q < p.Nq;
     h16x8 qf[PLANES][4];
 #pragma unroll
-    for (int pl = 0; pl < PLANES; ++pl)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            qf[pl][ks] = as_h16x8(qok ? ld16(Qp + (int64_t)q * p.ldq + pl * psq + ks * 16 + hi * 8) : zero16());
+    for (int pl = 0; pl < PLANES; ++pl) load_q_frags(qf[pl], Qp, q, p.ldq, pl * psq, qok, hi);
 
     const int lrow = tid >> 3, kc = tid & 7;
     u32x4 kr[PLANES][2], vr[PLANES][2];
-    auto load_tiles = [&](int kt) {
-        const int j0 = kt * KB;
-#pragma unroll
-        for (int pl = 0; pl < PLANES; ++pl)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int row = lrow + 32 * i;
-                const int j = j0 + row;
-                kr[pl][i] = (j < Nk) ? ld16(Kp + (int64_t)j * ldk + pl * psk + kc * 8) : zero16();
-                const int jc = j0 + kc * 8;
-                u32x4 v = zero16();
-                if (jc < Nk) {
-                    v = ld16(Vp + (int64_t)row * ldvt + pl * psv + jc);
-                    if (jc + 8 > Nk) {
-                        h16x8 hv = as_h16x8(v);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) if (jc + e >= Nk) hv[e] = (h16)0.f;
-                        v = as_u32x4(hv);
-                    }
-                }
-                vr[pl][i] = v;
-            }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int pl = 0; pl < PLANES; ++pl)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                st16(&Ks[(buf * PLANES + pl) * ATILE + (lrow + 32 * i) * ALD + kc * 8], kr[pl][i]);
-                st16(&Vs[(buf * PLANES + pl) * ATILE + (lrow + 32 * i) * ALD + kc * 8], vr[pl][i]);
-            }
-    };
 
     f32x16 o[2], res[TWO ? 2 : 1];
     const float c = p.q_prescaled ? 1.0f : p.scale * 1.4426950408889634f;
 #pragma unroll
     for (int set = 0; set < (TWO ? 2 : 1); ++set) {
-    if (TWO && set == 1) {
-        Kp = reinterpret_cast<const h16*>(p.K2) + (int64_t)(f / p.kv_div2) * p.Nk2 * p.ldk2 + h * 64;
-        Vp = reinterpret_cast<const h16*>(p.Vt2) + (int64_t)(f / p.kv_div2) * p.svt2 + (int64_t)(h * 64) * p.ldvt2;
-        Nk = p.Nk2; ldk = p.ldk2; ldvt = p.ldvt2; psk = ldk / PLANES; psv = ldvt / PLANES;
-    }
+        const KvSet kv = kv_set(p, f, h, set);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
-    float m_run = -INFINITY, l_run = 0.f;
+        for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
+        float m_run = -INFINITY, l_run = 0.f;
 
-    const int nkt = (Nk + KB - 1) / KB;
-    load_tiles(0);
-    stage(0);
-    __syncthreads();
-
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1;
-        const bool more = kt + 1 < nkt;
-        if (more) load_tiles(kt + 1);
-
-        f32x16 s[2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[sub][r] = 0.f;
-#pragma unroll
-            for (int sg = 0; sg < NSEG; ++sg) {
-                const h16* kp = Ks + (cur * PLANES + seg_xp(sg)) * ATILE + (sub * 32 + l31) * ALD + hi * 8;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const h16x8 kf = *reinterpret_cast<const h16x8*>(kp + ks * 16);
-                    s[sub] = MFMA_32x32x16(kf, qf[seg_wp(sg)][ks], s[sub]);
-                }
-            }
-        }
-        if (kt * KB + KB > Nk) {
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int j = kt * KB + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (j >= Nk) s[sub][r] = -INFINITY;
-                }
-        }
-
-        float mx = s[0][0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[0][r]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // The softmax of this kernel was its bottleneck (rocprofv3: twice as many VALU issue cycles as MFMA cycles per key tile): the
-        // exponentials run on v_exp_f32 directly (1 ulp — fp32-class, as the split products around them) instead of the library
-        // exp2f with its range handling, and O is rescaled only when some row's maximum actually grew (wave-uniform test).
-        const bool grew = !__all(mx <= m_run);
-        const float m_new = grew ? fmaxf(m_run, mx) : m_run;
-        const float alpha = grew ? __builtin_amdgcn_exp2f((m_run - m_new) * c) : 1.0f;
-        const float mc = m_new * c;
-        m_run = m_new;
-        float ps = 0.f;
-        h16x8 pk[PLANES][2][2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e = __builtin_amdgcn_exp2f(fmaf(s[sub][r], c, -mc));
-                ps += e;
-                h16 piece[PLANES];
-                split_operand(e, piece);
-#pragma unroll
-                for (int pl = 0; pl < PLANES; ++pl) pk[pl][sub][r >> 3][r & 7] = piece[pl];
-            }
-        l_run = l_run * alpha + ps;
-        if (grew) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
-        }
-
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int sg = 0; sg < NSEG; ++sg) {
-                const h16* vp = Vs + (cur * PLANES + seg_xp(sg)) * ATILE + (dt * 32 + l31) * ALD + 4 * hi;
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const int kk = sub * 32 + jj * 16;
-                        const h16x4 lo = *reinterpret_cast<const h16x4*>(vp + kk);
-                        const h16x4 up = *reinterpret_cast<const h16x4*>(vp + kk + 8);
-                        h16x8 vf;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = up[e]; }
-                        o[dt] = MFMA_32x32x16(vf, pk[seg_wp(sg)][sub][jj], o[dt]);
-                    }
-            }
-
-        if (more) stage(cur ^ 1);
+        const int nkt = (kv.Nk + KB - 1) / KB;
+        load_kv_tile(kv, 0, lrow, kc, kr, vr);
+        stage_padded(Ks, Vs, lrow, kc, kr, vr);
         __syncthreads();
-    }
 
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+        for (int kt = 0; kt < nkt; ++kt) {
+            const int cur = kt & 1;
+            const bool more = kt + 1 < nkt;
+            if (more) load_kv_tile(kv, kt + 1, lrow, kc, kr, vr);
+            FLASH_TILE(Ks + cur * PLANES * ATILE, Vs + cur * PLANES * ATILE, qf, kt, kv.Nk, c, m_run, l_run, o, l31, hi);
+            if (more) stage_padded(Ks + (cur ^ 1) * PLANES * ATILE, Vs + (cur ^ 1) * PLANES * ATILE, lrow, kc, kr, vr);
+            __syncthreads();
+        }
+
+        // this build divides (the 16-bit kernels multiply by the reciprocal) and sums the two sets' results unfused
+        const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] /= l_tot; o[1][r] /= l_tot; }
-    if (TWO) {
-        if (set == 0) {
+        for (int r = 0; r < 16; ++r) { o[0][r] /= l_tot; o[1][r] /= l_tot; }
+        if (TWO) {
+            if (set == 0) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { res[0][r] = o[0][r]; res[1][r] = o[1][r]; }
-        } else {
+                for (int r = 0; r < 16; ++r) { res[0][r] = o[0][r]; res[1][r] = o[1][r]; }
+            } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { o[0][r] += res[0][r]; o[1][r] += res[1][r]; }
+                for (int r = 0; r < 16; ++r) { o[0][r] += res[0][r]; o[1][r] += res[1][r]; }
+            }
         }
     }
-    }   // sets
     if (qok) {
         h16* orow = Op + (int64_t)q * p.ldo;
 #pragma unroll
@@ -1414,52 +846,34 @@ __global__ __launch_bounds__(256, 2) void attn_split_dma_kernel(const MudgAttnDe
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    int w;
-    {
-        const int q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        w = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    const int w = xcd_work_item(total);
     const int pair = w / nqt, qt = w - pair * nqt;
     const int f = pair / p.heads, h = pair - f * p.heads;
-    const int kvb = f / p.kv_div;
-    const int psq = p.ldq / 2, psk = p.ldk / 2, psv = p.ldvt / 2, pso = p.ldo / 2;
+    const KvSet kv = kv_set(p, f, h, 0);
+    const int psq = p.ldq / 2, pso = p.ldo / 2;
 
     const h16* Qp = reinterpret_cast<const h16*>(p.Q) + (int64_t)f * p.Nq * p.ldq + h * 64;
-    const h16* Kp = reinterpret_cast<const h16*>(p.K) + (int64_t)kvb * p.Nk * p.ldk + h * 64;
-    const h16* Vp = reinterpret_cast<const h16*>(p.Vt) + (int64_t)kvb * p.svt + (int64_t)(h * 64) * p.ldvt;
     h16* Op = reinterpret_cast<h16*>(p.O) + (int64_t)f * p.Nq * p.ldo + h * 64;
 
     const int q = qt * QB + wave * 32 + l31;
     const bool qok = q < p.Nq;
     h16x8 qf[2][4];
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            qf[pl][ks] = as_h16x8(qok ? ld16(Qp + (int64_t)q * p.ldq + pl * psq + ks * 16 + hi * 8) : zero16());
+    for (int pl = 0; pl < 2; ++pl) load_q_frags(qf[pl], Qp, q, p.ldq, pl * psq, qok, hi);
 
-    // DMA geometry: wave w stages rows [16w, 16w + 16) of the four tiles, two 1-KiB instructions each
-    const __amdgpu_buffer_rsrc_t rK = attn_rsrc(Kp), rV = attn_rsrc(Vp);
+    // DMA geometry (dma_offsets): wave w stages rows [16w, 16w + 16) of the four tiles, two 1-KiB instructions each
+    const __amdgpu_buffer_rsrc_t rK = attn_rsrc(kv.Kp), rV = attn_rsrc(kv.Vp);
     unsigned vk[2], vv[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = 16 * wave + 8 * i + (lane >> 3), slot = lane & 7;
-        const int chunk = slot ^ ((row >> 1) & 7);
-        const int i16 = row & 15;
-        const int key = (row & ~15) | (i16 & 3) | ((i16 & 8) >> 1) | ((i16 & 4) << 1);     // swap the middle 4-blocks
-        vk[i] = (unsigned)key * (unsigned)p.ldk * 2u + (unsigned)chunk * 16u;
-        vv[i] = (unsigned)row * (unsigned)p.ldvt * 2u + (unsigned)chunk * 16u;
-    }
+    dma_offsets(wave, lane, p.ldk, p.ldvt, vk, vv);
     auto request = [&](int kt, int buf) {
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (attn_lptr_t)(Ks + (buf * 2 + pl) * SDT + (16 * wave + 8 * i) * 64), 16, (int)vk[i],
-                                                         (kt * 64 * p.ldk + pl * psk) * 2, 0, 0);
+                                                         (kt * 64 * p.ldk + pl * kv.psk) * 2, 0, 0);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rV, (attn_lptr_t)(Vs + (buf * 2 + pl) * SDT + (16 * wave + 8 * i) * 64), 16, (int)vv[i],
-                                                         (kt * 64 + pl * psv) * 2, 0, 0);
+                                                         (kt * 64 + pl * kv.psv) * 2, 0, 0);
             }
     };
     const int sw = (l31 >> 1) & 7;
@@ -1500,12 +914,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_dma_kernel(const MudgAttnDe
                 for (int r = 0; r < 16; ++r) s0[sub][r] = 0.f;
                 score_block(0, sub, s0[sub]);
             }
-            float mx = s0[0][0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s0[0][r]);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s0[1][r]);
-            m_run = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            m_run = row_max32(s0);
         }
         for (int kt = 0; kt < nkt; ++kt) {
             const int cur = kt & 1;
@@ -1519,47 +928,11 @@ __global__ __launch_bounds__(256, 2) void attn_split_dma_kernel(const MudgAttnDe
                 score_block(cur, sub, sc[sub]);
             }
             h16x8 pk[2][2][2];        // [piece][sub][jj]
-            float ps = 0.f;
             if constexpr (LN) {
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float e = __builtin_amdgcn_exp2f(sc[sub][r]);
-                        ps += e;
-                        const h16 p0 = (h16)e;
-                        pk[0][sub][r >> 3][r & 7] = p0;
-                        pk[1][sub][r >> 3][r & 7] = (h16)(e - (float)p0);
-                    }
-                l_run += ps;
-                overflow = overflow || !(ps <= LEAN_LIMIT);
+                const bool over = softmax_step_lean(sc, l_run, pk);
+                overflow = overflow || over;
             } else {
-                float mx = sc[0][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[0][r]);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[1][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const bool grew = !__all(mx <= m_run);
-                const float m_new = grew ? fmaxf(m_run, mx) : m_run;
-                const float alpha = grew ? __builtin_amdgcn_exp2f((m_run - m_new) * c) : 1.0f;
-                const float mc = m_new * c;
-                m_run = m_new;
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float e = __builtin_amdgcn_exp2f(fmaf(sc[sub][r], c, -mc));
-                        ps += e;
-                        const h16 p0 = (h16)e;
-                        pk[0][sub][r >> 3][r & 7] = p0;
-                        pk[1][sub][r >> 3][r & 7] = (h16)(e - (float)p0);
-                    }
-                l_run = l_run * alpha + ps;
-                if (grew) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
-                }
+                softmax_step_classic(sc, c, m_run, l_run, o, pk);
             }
             // P V: v1 p0 + v0 p1 + v0 p0; register group (sub, jj) of half hi holds keys 32 sub + 16 jj + 8 hi .. + 7
 #pragma unroll
@@ -1581,14 +954,9 @@ __global__ __launch_bounds__(256, 2) void attn_split_dma_kernel(const MudgAttnDe
             __syncthreads();                                      // every wave's; everyone is done reading tile kt
         }
     };
+    lean_or_classic<LEAN>(overflow, key_loop);
 
-    if constexpr (LEAN) {
-        key_loop(std::true_type{});
-        if (__syncthreads_or(overflow ? 1 : 0)) key_loop(std::false_type{});      // cold: exact, merely slower
-    } else {
-        key_loop(std::false_type{});
-    }
-
+    // the two-piece twin of store_o16
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.f / l_tot;
     if (qok) {
@@ -1851,19 +1219,21 @@ extern "C" int mudg_attention(const MudgAttnDesc* dp, void* stream) {
         constexpr int smem = 4 * PLANES * ATILE * (int)sizeof(h16);
         if (const int rc = mudg_lds_opt_in<&attn_split_kernel<false>>(smem, "mudg_attention")) return rc;
         if (const int rc = mudg_lds_opt_in<&attn_split_kernel<true>>(smem, "mudg_attention")) return rc;
-        bool dma_ok = false;
 #if MUDG_PLANES == 2
         // the long self-attention on LDS-DMA staged tiles (whole key tiles inside the 2-GiB window of a buffer descriptor)
-        dma_ok = wide && d.Nk % 64 == 0 && (int64_t)d.Nk * d.ldk * 2 < (1ll << 31) && (int64_t)64 * d.ldvt * 2 + (int64_t)d.Nk * 2 + d.ldvt < (1ll << 31);
+        const bool dma_ok = wide && d.Nk % 64 == 0 && (int64_t)d.Nk * d.ldk * 2 < (1ll << 31) && (int64_t)64 * d.ldvt * 2 + (int64_t)d.Nk * 2 + d.ldvt < (1ll << 31);
+#else
+        const bool dma_ok = false;      // attn_split_dma_kernel is the bf16x3 build's
+        (void)wide;
+#endif
         if (dma_ok) {
+#if MUDG_PLANES == 2
             if (const int rc = mudg_lds_opt_in<&attn_split_dma_kernel<true>>(SPLIT_DMA_SMEM, "mudg_attention")) return rc;
             if (const int rc = mudg_lds_opt_in<&attn_split_dma_kernel<false>>(SPLIT_DMA_SMEM, "mudg_attention")) return rc;
             if (d.q_prescaled) hipLaunchKernelGGL(attn_split_dma_kernel<true>, dim3((unsigned)total), dim3(256), SPLIT_DMA_SMEM, s, d, nqt, (int)total);
             else hipLaunchKernelGGL(attn_split_dma_kernel<false>, dim3((unsigned)total), dim3(256), SPLIT_DMA_SMEM, s, d, nqt, (int)total);
-        }
 #endif
-        (void)wide;
-        if (dma_ok) {}
+        }
         else if (d.K2) hipLaunchKernelGGL(attn_split_kernel<true>, dim3((unsigned)total), dim3(256), smem, s, d, nqt, (int)total);
         else hipLaunchKernelGGL(attn_split_kernel<false>, dim3((unsigned)total), dim3(256), smem, s, d, nqt, (int)total);
     }
@@ -1981,35 +1351,25 @@ extern "C" int mudg_temporal_attention(const void* QKV, void* O, int B, int T, i
     MUDG_REQUIRE(total < (1ll << 31), "mudg_temporal_attention: grid too large");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int slot = mudg_prof_begin(MUDG_FAM_TATTN, s);
-#if MUDG_PLANES > 1
-    const unsigned grid = (unsigned)((total + 3) / 4);
-#if MUDG_PLANES == 2
-    static int use_mfma = -1;               // MUDG_TATTN_MFMA=0: the fp32 FMA kernel for every length (A/B, tests)
-    if (use_mfma < 0) use_mfma = mudg_variant("TATTN_MFMA", 1);
-    if (T <= 16 && use_mfma)
-        hipLaunchKernelGGL(tattn_split_mfma_kernel, dim3((unsigned)((total + 4 * TATTN_SPLIT_ITEMS - 1) / (4 * TATTN_SPLIT_ITEMS))), dim3(256), 0, s,
+    auto launch = [&](auto kernel, int64_t items_per_block) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((total + items_per_block - 1) / items_per_block)), dim3(256), 0, s,
                            (const h16*)QKV, (h16*)O, B, T, HW, heads, ldqkv, ldo, scale, (int)total);
+    };
+#if MUDG_PLANES != 3
+    static int use_mfma = -1;               // MUDG_TATTN_MFMA=0: the VALU / fp32 FMA kernel for every length (A/B, tests)
+    if (use_mfma < 0) use_mfma = mudg_variant("TATTN_MFMA", 1);
+#endif
+#if MUDG_PLANES > 1
+#if MUDG_PLANES == 2
+    if (T <= 16 && use_mfma) launch(tattn_split_mfma_kernel, 4 * TATTN_SPLIT_ITEMS);
     else
 #endif
-    if (T <= 16)
-        hipLaunchKernelGGL(tattn_split_kernel<16>, dim3(grid), dim3(256), 0, s, (const h16*)QKV, (h16*)O, B, T, HW, heads,
-                           ldqkv, ldo, scale, (int)total);
-    else
-        hipLaunchKernelGGL(tattn_split_kernel<32>, dim3(grid), dim3(256), 0, s, (const h16*)QKV, (h16*)O, B, T, HW, heads,
-                           ldqkv, ldo, scale, (int)total);
+    if (T <= 16) launch(tattn_split_kernel<16>, 4);
+    else launch(tattn_split_kernel<32>, 4);
 #else
-    const unsigned grid = (unsigned)((total + 4 * TATTN_ITEMS - 1) / (4 * TATTN_ITEMS));
-    static int use_mfma = -1;               // MUDG_TATTN_MFMA=0: the VALU kernel for every length (A/B, tests)
-    if (use_mfma < 0) use_mfma = mudg_variant("TATTN_MFMA", 1);
-    if (T <= 16 && use_mfma)
-        hipLaunchKernelGGL(tattn_mfma_kernel, dim3(grid), dim3(256), 0, s, (const h16*)QKV, (h16*)O, B, T, HW, heads,
-                           ldqkv, ldo, scale, (int)total);
-    else if (T <= 16)
-        hipLaunchKernelGGL(tattn_kernel<16>, dim3(grid), dim3(256), 0, s, (const h16*)QKV, (h16*)O, B, T, HW, heads,
-                           ldqkv, ldo, scale, (int)total);
-    else
-        hipLaunchKernelGGL(tattn_kernel<32>, dim3(grid), dim3(256), 0, s, (const h16*)QKV, (h16*)O, B, T, HW, heads,
-                           ldqkv, ldo, scale, (int)total);
+    if (T <= 16 && use_mfma) launch(tattn_mfma_kernel, 4 * TATTN_ITEMS);
+    else if (T <= 16) launch(tattn_kernel<16>, 4 * TATTN_ITEMS);
+    else launch(tattn_kernel<32>, 4 * TATTN_ITEMS);
 #endif
     const int rc = mudg_check_launch("mudg_temporal_attention");
     mudg_prof_end(slot, s, 4.0 * total * (double)T * T * 64.0, (double)total * T * 64.0 * 2.0 * 4.0);

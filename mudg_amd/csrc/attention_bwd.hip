@@ -103,17 +103,12 @@ __device__ __forceinline__ void own_fragments(const h16* row, bool ok, int hi, h
 struct Geo {
     int w, f, h, g, t;       // work item, frame, head, key / value batch, tile index inside
 };
-__device__ __forceinline__ int xcd_item(int total) {
-    const int q8 = total >> 3, r8 = total & 7;
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-}
 
 // ---------------------------------------------------------------------------------------------- stats
 __global__ __launch_bounds__(256, 2) void attn_bwd_stats_kernel(const MudgAttnBwdDesc p, const int nqt, const int total) {
     __shared__ __attribute__((aligned(16))) h16 Ks[BTILE], Vs[BTILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const int w = xcd_item(total);
+    const int w = xcd_work_item(total);
     const int pair = w / nqt, qt = w - pair * nqt;
     const int f = pair / p.heads, h = pair - f * p.heads;
     const int q = qt * BTQ + wave * 32 + l31;
@@ -180,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_stats_kernel(const MudgAttnBw
 __global__ __launch_bounds__(256, 2) void attn_bwd_q_kernel(const MudgAttnBwdDesc p, const int nqt, const int total) {
     __shared__ __attribute__((aligned(16))) h16 Ks[BTILE], Vs[BTILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const int w = xcd_item(total);
+    const int w = xcd_work_item(total);
     const int pair = w / nqt, qt = w - pair * nqt;
     const int f = pair / p.heads, h = pair - f * p.heads;
     const int g = f / p.kv_div;
@@ -248,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_k_kernel(const MudgAttnBwdDes
     __shared__ __attribute__((aligned(16))) h16 Qs[BTILE], dOs[BTILE];
     __shared__ __attribute__((aligned(16))) float Ls[BT], Ds[BT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const int w = xcd_item(total);
+    const int w = xcd_work_item(total);
     const int pair = w / nktile, ktile = w - pair * nktile;
     const int g = pair / p.heads, h = pair - g * p.heads;
     const int k = ktile * BTQ + wave * 32 + l31;

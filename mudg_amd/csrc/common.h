@@ -171,6 +171,14 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// XCD-aware numbering of a 1-D grid of `total` workgroups: hardware places block b on XCD b % 8; give each XCD a contiguous
+// range of work items, so that neighbouring items (the query tiles of one (frame, head)) run on one XCD and share its L2.
+__device__ __forceinline__ int xcd_work_item(int total) {
+    const int q8 = total >> 3, r8 = total & 7;
+    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+}
+
 // ---- host side ---------------------------------------------------------------------------------
 // Kernel-variant switches (A/B measurements, tests that force a particular kernel): compiled in only with
 // -DMUDG_DEBUG_VARIANTS (libmudg_hip_dbg.so, used by tests/test_gemm_variants_gpu.py and tools/); the shipped libraries

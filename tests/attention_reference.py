@@ -13,7 +13,7 @@ from backward_reference import operand_planes
 F64 = torch.float64
 LOG2E = 1.4426950408889634
 CODE = 4.0                      # the gather codes are +-CODE: exact in every operand type
-LEAN_LIMIT_LOG2 = 40            # csrc/attention.hip LEAN_LIMIT with bf16 operands (2^15 with fp16 ones)
+LEAN_LIMIT_LOG2 = 40            # csrc/attn_shared.h LEAN_LIMIT with bf16 operands (2^15 with fp16 ones)
 
 
 def through(round_to, dtype=F64):
