@@ -9,7 +9,10 @@ that child, its bit-identity with the 128 x 128 kernels: test_wide288_is_bit_ide
 144 x 256 GEGLU kernel of round 6 forced for every GEGLU problem (both K-loop forms) and switched off, the 160 x 320 tile of round 6 forced
 for every problem it can run (test_wide160_is_bit_identical_to_the_one_tile_kernels runs in the children).  The attention dispatcher's A/B
 switches (MUDG_ATTN_Q, and MUDG_ATTN_DMA=0 / MUDG_ATTN_LEAN=0 / MUDG_ATTN_X=0: the register-staged 64-query kernel on whole key tiles, the
-classic softmax on prescaled Q, the one-tile kernel on many-tile cross-attention) run tests/test_attention_kernels_gpu.py."""
+classic softmax on prescaled Q, the one-tile kernel on many-tile cross-attention) run tests/test_attention_kernels_gpu.py.  Every child of
+VARIANTS and VARIANTS_X3 also runs tests/test_gemm_kernels_gpu.py — each forced kernel against the fp64 definitions, exactly, at every shape
+of that file it is eligible for — and VARIANTS_GEMM (the 288-row tile on the 160-row tile's loop, the 160-row tile with every residual
+seeding) run that file alone."""
 import os
 import subprocess
 import sys
@@ -49,6 +52,10 @@ VARIANTS_X3 = [{"MUDG_GEMM_W288": "2"}, {"MUDG_GEMM_W288": "0"}]
 # The attention dispatcher's own switches: these children run the per-kernel attention file only
 VARIANTS_ATTN = [{"MUDG_ATTN_DMA": "0"}, {"MUDG_ATTN_LEAN": "0"}, {"MUDG_ATTN_X": "0"}]
 ATTN_FILE = "tests/test_attention_kernels_gpu.py"
+# Reached by no other direct test: wq_kernel<..., 9> for every one-tile problem of the 288-row tile, and wq_kernel<..., 5> with 16-bit
+# residuals seeding the accumulators instead of waiting for the epilogue.  These children run the per-kernel GEMM file only
+VARIANTS_GEMM = [{"MUDG_GEMM_W288": "2", "MUDG_GEMM_W288Q": "2"}, {"MUDG_GEMM_W160": "2", "MUDG_GEMM_W160DEFER": "0"}]
+GEMM_FILE = "tests/test_gemm_kernels_gpu.py"
 _name = lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items())
 
 
@@ -58,14 +65,17 @@ def children():
     from helpers import ChildRuns
     runs = ChildRuns(workers=4)
     for i, env in enumerate(VARIANTS):
-        runs.submit(_name(env), [sys.executable, "-m", "pytest", "tests/test_kernels_gpu.py", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py",
+        runs.submit(_name(env), [sys.executable, "-m", "pytest", "tests/test_kernels_gpu.py", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py", GEMM_FILE,
                                  *([ATTN_FILE] if "MUDG_ATTN_Q" in env else []), "-m", "gpu", "-q", "-k", SELECT, "-p", "no:cacheprovider"],
                     ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", **env), 900, alone=(i == 0))
     for env in VARIANTS_ATTN:
         runs.submit(_name(env), [sys.executable, "-m", "pytest", ATTN_FILE, "-m", "gpu", "-q", "-p", "no:cacheprovider"],
                     ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", **env), 900)
+    for env in VARIANTS_GEMM:
+        runs.submit(_name(env), [sys.executable, "-m", "pytest", GEMM_FILE, "-m", "gpu", "-q", "-p", "no:cacheprovider"],
+                    ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", **env), 900)
     for env in VARIANTS_X3:
-        runs.submit("x3:" + _name(env), [sys.executable, "-m", "pytest", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py", "-m", "gpu", "-q",
+        runs.submit("x3:" + _name(env), [sys.executable, "-m", "pytest", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py", GEMM_FILE, "-m", "gpu", "-q",
                                          "-p", "no:cacheprovider"],
                     ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", MUDG_OPERAND="bf16x3", MUDG_PARITY_CHILD="1", MUDG_SKIP_FULLSIZE_ORACLE="1",
                                MUDG_SKIP_CONFIG0_CUT="1", **env), 900)
@@ -73,7 +83,7 @@ def children():
     runs.shutdown()
 
 
-@pytest.mark.parametrize("env", VARIANTS + VARIANTS_ATTN, ids=_name)
+@pytest.mark.parametrize("env", VARIANTS + VARIANTS_ATTN + VARIANTS_GEMM, ids=_name)
 def test_kernel_parity_under_variant(cuda, env, request):
     if os.environ.get("MUDG_DEBUG_VARIANTS") == "1":
         pytest.skip("already running under a variant switch")
