@@ -341,6 +341,29 @@ int mudg_splat_compose(const uint32_t* bg_colour, const float* bg_depth, const u
                        float* sparse_frames, float* sparse_depth, int64_t pose_stride, int poses, int T, int t, int H, int W,
                        uint8_t* rgb_out, float* depth_out, uint8_t* mask_out, void* stream);
 
+/* ------------------------------------------------------------------ scene clouds from LiDAR sweeps
+ * (data_process/tools/process_lidar.py:27-33, 45-82, 121-138, 229-250; fp64 in a stated order, no output depends on execution order.)
+ * cloud_sweep: one launch serves `frames` frames; frame f owns rays offsets[f] .. offsets[f + 1] of rays_o / rays_d (fp32 triples) and
+ *   ranges (`total` rays in all, `max_rays` the longest frame).  Device tables of 8-byte words: l2w[frames][12] doubles;
+ *   cams[frames][ncam][24] = w2c[12], K[9] doubles, then int64 h, w and the byte offset of the camera's uint8 (h, w, 3) image in
+ *   `images` (image_bytes long), ncam <= 8; objs[frames][nobj][16] doubles = w2l[12], the box extents[3], visible (non-zero).
+ *   Per ray: p = (R o + t) + (R d) range; colour of the last camera with zc > 0 whose truncated pixel is inside its image; label -1
+ *   when no camera sees p, else 1 + the first visible object k with |q.x| < bx / 2, |q.y| < by / 2, -bz / 2 + 0.25 < q.z < bz / 2,
+ *   q = w2l p, else 0.  points[ray] = 16 bytes (fp32 q for an object point, p otherwise; r | g << 8 | b << 16), labels[ray] int32.
+ * cloud_voxel_keys: keys[i] = (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20), i_axis = floor(double(p) / voxel); the caller has
+ *   checked |i_axis| < 2^20.
+ * cloud_voxel_reduce: order[j] = index of the j-th point by key, segments[j] = rank of its voxel (0 .. voxels - 1, non-decreasing);
+ *   sums[voxel][8] uint64, zero on entry, receive count, r, g, b, the three fixed-point in-voxel offsets floor((p - i v) / v * 2^32)
+ *   clamped to [0, 2^32 - 1], and the key.
+ * cloud_voxel_finish: points_out[voxel] = fp32(i v + v (S / (count 2^32))) per axis and (2 S_c + count) / (2 count) per channel. */
+int mudg_cloud_sweep(const float* rays_o, const float* rays_d, const float* ranges, const int64_t* offsets, int frames,
+                     int64_t max_rays, int64_t total, const double* l2w, const double* cams, int ncam, const double* objs,
+                     int nobj, const uint8_t* images, int64_t image_bytes, void* points, int32_t* labels, void* stream);
+int mudg_cloud_voxel_keys(const void* points, int64_t n, double voxel, int64_t* keys, void* stream);
+int mudg_cloud_voxel_reduce(const void* points, const int64_t* order, const int64_t* segments, int64_t n, double voxel,
+                            uint64_t* sums, int64_t voxels, void* stream);
+int mudg_cloud_voxel_finish(const uint64_t* sums, int64_t voxels, double voxel, void* points_out, void* stream);
+
 /* ------------------------------------------------------------------ training step
  * Reference: lvdm/models/ddpm3d.py:741-802 (p_losses), :1267-1300 (configure_optimizers -> torch.optim.AdamW),
  * main/utils_train.py:126-137 (data-parallel strategy).  The contractions of the backward pass (dX = dY W, dW = dY^T X,

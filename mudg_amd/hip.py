@@ -115,7 +115,7 @@ class WgradDesc(C.Structure):
 
 
 # name -> (restype, argtypes); this table is also what tests check against include/mudg_hip.h
-_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
     "mudg_version": (_I, []),
     "mudg_operand_dtype": (_I, []),
@@ -150,6 +150,10 @@ SIGNATURES = {
     "mudg_splat_points": (_I, [_P, _P, _L, _P, _I, _I, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P]),
     "mudg_splat_resolve": (_I, [_P, _P, _L, _P, _P, _L, _P]),
     "mudg_splat_compose": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "mudg_cloud_sweep": (_I, [_P, _P, _P, _P, _I, _L, _L, _P, _P, _I, _P, _I, _P, _L, _P, _P, _P]),
+    "mudg_cloud_voxel_keys": (_I, [_P, _L, _D, _P, _P]),
+    "mudg_cloud_voxel_reduce": (_I, [_P, _P, _P, _L, _D, _P, _L, _P]),
+    "mudg_cloud_voxel_finish": (_I, [_P, _L, _D, _P, _P]),
     "mudg_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_float), _P, _P]),
     "mudg_gaussian_sample": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "mudg_posterior_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _F, _P]),

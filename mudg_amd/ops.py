@@ -747,3 +747,67 @@ def splat_compose(bg, obj, sparse_frames, sparse_depth, t, *, images=False):
                                            3 * T * h * w, poses, T, int(t), h, w, _ptr(rgb), _ptr(depth), _ptr(mask), _stream()),
               "mudg_splat_compose")
     return (rgb, depth, mask) if images else None
+
+
+# ------------------------------------------------------------------------------------------------ scene clouds from LiDAR sweeps
+def cloud_sweep(rays_o, rays_d, ranges, offsets, max_rays, l2w, cams, objs, images):
+    """One launch for a batch of frames (DESIGN.md §13): rays_o / rays_d (n, 3) and ranges (n,) fp32, concatenated over the frames;
+    offsets (frames + 1,) int64 on the GPU, max_rays the longest frame; l2w (frames, 12) float64; cams (frames, ncam, 24) float64
+    (w2c, K, then h, w and the image's byte offset as int64 bit patterns) or None; objs (frames, nobj, 16) float64 or None; images a
+    flat uint8 buffer.  Returns packed points (n, 4) int32 and labels (n,) int32."""
+    _splat_tensor("cloud_sweep: rays_o", rays_o, torch.float32)
+    n = rays_o.shape[0]
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or n == 0:
+        raise hip.MudgError(f"cloud_sweep: expected rays (n > 0, 3), got {tuple(rays_o.shape)}")
+    _splat_tensor("cloud_sweep: rays_d", rays_d, torch.float32, (n, 3))
+    _splat_tensor("cloud_sweep: ranges", ranges, torch.float32, (n,))
+    _splat_tensor("cloud_sweep: offsets", offsets, torch.int64)
+    frames = offsets.numel() - 1
+    _splat_tensor("cloud_sweep: l2w", l2w, torch.float64, (frames, 12))
+    ncam = nobj = 0
+    if cams is not None:
+        _splat_tensor("cloud_sweep: cams", cams, torch.float64)
+        _splat_tensor("cloud_sweep: images", images, torch.uint8)
+        if cams.dim() != 3 or cams.shape[0] != frames or cams.shape[2] != 24 or images.dim() != 1:
+            raise hip.MudgError(f"cloud_sweep: camera table {tuple(cams.shape)} for {frames} frames, images {tuple(images.shape)}")
+        ncam = cams.shape[1]
+    if objs is not None:
+        _splat_tensor("cloud_sweep: objs", objs, torch.float64)
+        if objs.dim() != 3 or objs.shape[0] != frames or objs.shape[2] != 16:
+            raise hip.MudgError(f"cloud_sweep: object table {tuple(objs.shape)} for {frames} frames")
+        nobj = objs.shape[1]
+    points = torch.empty((n, 4), dtype=torch.int32, device=rays_o.device)
+    labels = torch.empty((n,), dtype=torch.int32, device=rays_o.device)
+    hip.check(hip.lib().mudg_cloud_sweep(rays_o.data_ptr(), rays_d.data_ptr(), ranges.data_ptr(), offsets.data_ptr(), frames, int(max_rays), n,
+                                         l2w.data_ptr(), _ptr(cams) if ncam else None, ncam, _ptr(objs) if nobj else None, nobj,
+                                         _ptr(images) if ncam else None, images.numel() if ncam else 0, points.data_ptr(), labels.data_ptr(),
+                                         _stream()), "mudg_cloud_sweep")
+    return points, labels
+
+
+def cloud_voxel_keys(points, voxel):
+    """Packed points (n, 4) int32 -> (n,) int64 voxel keys on the absolute grid of size `voxel` (the caller has checked the range)."""
+    _splat_tensor("cloud_voxel_keys: points", points, torch.int32)
+    keys = torch.empty((points.shape[0],), dtype=torch.int64, device=points.device)
+    hip.check(hip.lib().mudg_cloud_voxel_keys(points.data_ptr(), points.shape[0], float(voxel), keys.data_ptr(), _stream()), "mudg_cloud_voxel_keys")
+    return keys
+
+
+def cloud_voxel_reduce(points, order, segments, voxel, voxels):
+    """Integer sums per voxel, (voxels, 8) int64: count, r, g, b, three fixed-point offsets, the key.  order / segments: (n,) int64."""
+    n = points.shape[0]
+    _splat_tensor("cloud_voxel_reduce: points", points, torch.int32, (n, 4))
+    _splat_tensor("cloud_voxel_reduce: order", order, torch.int64, (n,))
+    _splat_tensor("cloud_voxel_reduce: segments", segments, torch.int64, (n,))
+    sums = torch.zeros((int(voxels), 8), dtype=torch.int64, device=points.device)
+    hip.check(hip.lib().mudg_cloud_voxel_reduce(points.data_ptr(), order.data_ptr(), segments.data_ptr(), n, float(voxel), sums.data_ptr(), int(voxels),
+                                                _stream()), "mudg_cloud_voxel_reduce")
+    return sums
+
+
+def cloud_voxel_finish(sums, voxel):
+    """(voxels, 8) sums -> packed points (voxels, 4) int32: the mean position and the round-half-up mean colour of every voxel."""
+    _splat_tensor("cloud_voxel_finish: sums", sums, torch.int64)
+    out = torch.empty((sums.shape[0], 4), dtype=torch.int32, device=sums.device)
+    hip.check(hip.lib().mudg_cloud_voxel_finish(sums.data_ptr(), sums.shape[0], float(voxel), out.data_ptr(), _stream()), "mudg_cloud_voxel_finish")
+    return out

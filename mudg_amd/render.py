@@ -206,3 +206,14 @@ class Scene:
     intr: np.ndarray            # (3, 3) or (frames, 3, 3)
     c2w: np.ndarray             # (frames, 4, 4)
     hw_native: tuple            # (H0, W0) the intrinsics refer to
+
+    @classmethod
+    def from_scenario(cls, scenario, load_lidar, load_image, camera="camera_FRONT", *, frames=None, **kwargs):
+        """Build the clouds from the scenario's LiDAR sweeps (cloud.build_scene_clouds, which takes **kwargs) and take `camera`'s
+        intrinsics, poses and size for the frames used."""
+        from . import cloud
+        background, objects, _ = cloud.build_scene_clouds(scenario, load_lidar, load_image, frames=frames, **kwargs)
+        data = scenario["observers"][camera]["data"]
+        rows = list(range(scenario["observers"]["lidar_TOP"]["n_frames"])) if frames is None else [int(f) for f in frames]
+        return cls(background, objects, np.asarray(data["intr"], dtype=np.float64)[rows], np.asarray(data["c2w"], dtype=np.float64)[rows],
+                   tuple(int(v) for v in data["hw"][rows[0]]))

@@ -77,3 +77,82 @@ def street_scene(n_background=2_000_000, frames=4, seed=0, n_objects=4, object_p
     intr = np.array([[2000.0, 0, 960.0], [0, 2000.0, 640.0], [0, 0, 1]])
     return {"bg_xyz": bg_xyz, "bg_rgb": bg_rgb, "objects": objects, "transform_obj": np.stack(transforms), "visibility": visibility,
             "intr": intr, "c2w": np.stack(c2w), "hw_native": (1280, 1920)}
+
+
+def street_sweeps(frames=6, beams=32, azimuths=625, seed=0, n_objects=3, n_static=1, n_other=1, front_hw=(320, 480), side_hw=(222, 360)):
+    """A seeded synthetic scenario in the layout of the reference's scenario.pt for mudg_amd.cloud (tests, tools/cloud_bench.py):
+    returns (scenario, load_lidar, load_image).  World: x forward, y left, z up, the ground at z = 0 and walls at y = +-12.  A
+    spinning LiDAR (beams x azimuths rays, 2 m above the ego vehicle, which drives 0.8 m per frame with a slight yaw) is cast
+    against the ground, the walls and the boxes; only rays that hit within 75 m are returns, so the frames differ in length.
+    n_objects Vehicle boxes drive ahead (object 1 is not tracked in frame 1), n_static more stand still and n_other more are Signs.
+    camera_FRONT looks ahead, the smaller camera_SIDE_LEFT 60 degrees to the left; their images are procedural and avoid 0."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    total = n_objects + n_static + n_other
+    scale = np.array([4.5, 2.0, 1.6])
+    start = np.stack([rng.uniform(8, 40, total), rng.uniform(-8, 8, total), np.full(total, scale[2] / 2)], axis=1)
+    speed = np.where(np.arange(total) < n_objects, rng.uniform(0.4, 1.5, total), 0.0)
+    yaw0 = rng.uniform(-0.3, 0.3, total)
+
+    def rot_z(a):
+        return np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+
+    def rigid(r, t):
+        m = np.eye(4)
+        m[:3, :3], m[:3, 3] = r, t
+        return m
+
+    obj_tf = np.stack([np.stack([rigid(rot_z(yaw0[k] + (0.01 * f if speed[k] else 0.0)), start[k] + [speed[k] * f, 0, 0]) for f in range(frames)])
+                       for k in range(total)]) if total else np.zeros((0, frames, 4, 4))
+    objects = {}
+    for k in range(total):
+        shown = [f for f in range(frames) if not (k == 1 and f == 1 and frames > 1)]
+        runs = [[shown[0]]] if shown else []
+        for f in shown[1:]:
+            runs[-1].append(f) if f == runs[-1][-1] + 1 else runs.append([f])
+        objects[f"obj_{k}"] = {"id": k, "class_name": "Sign" if k >= n_objects + n_static else "Vehicle",
+                               "segments": [{"start_frame": r[0], "n_frames": len(r), "data": {"transform": obj_tf[k, r], "scale": np.tile(scale, (len(r), 1))}}
+                                            for r in runs]}
+    ego = [rigid(rot_z(0.01 * f), [0.8 * f, 0.1 * f, 0.0]) for f in range(frames)]
+    l2w = np.stack([e @ rigid(np.eye(3), [0.0, 0.0, 2.0]) for e in ego])
+    cv = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])                 # the camera's x right, y down, z ahead in the ego frame
+    mounts = {"camera_FRONT": (rigid(cv, [1.5, 0.0, 1.6]), front_hw), "camera_SIDE_LEFT": (rigid(rot_z(np.pi / 3) @ cv, [1.2, 0.5, 1.6]), side_hw)}
+    observers = {"lidar_TOP": {"n_frames": frames, "data": {"l2w": l2w}}}
+    for name, (mount, (h, w)) in mounts.items():
+        k = np.array([[0.6 * w, 0.0, w / 2.0], [0.0, 0.6 * w, h / 2.0], [0.0, 0.0, 1.0]])
+        observers[name] = {"n_frames": frames, "data": {"c2w": np.stack([e @ mount for e in ego]), "intr": np.tile(k, (frames, 1, 1)),
+                                                         "hw": np.tile(np.array([h, w]), (frames, 1))}}
+    scenario = {"observers": observers, "objects": objects}
+
+    elev = np.linspace(np.radians(-17.0), np.radians(2.5), beams)
+    azim = np.linspace(-np.pi, np.pi, azimuths, endpoint=False)
+    el, az = (a.reshape(-1) for a in np.meshgrid(elev, azim, indexing="ij"))
+    dirs = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=1)
+
+    def load_lidar(frame):
+        g = np.random.default_rng([seed, 1, frame])
+        o = g.normal(0.0, 0.01, dirs.shape)
+        ow = o @ l2w[frame, :3, :3].T + l2w[frame, :3, 3]
+        dw = dirs @ l2w[frame, :3, :3].T
+        with np.errstate(all="ignore"):
+            t = np.where(dw[:, 2] < 0, -ow[:, 2] / dw[:, 2], np.inf)
+            for wall in (-12.0, 12.0):
+                tw = (wall - ow[:, 1]) / dw[:, 1]
+                t = np.minimum(t, np.where(tw > 0, tw, np.inf))
+            for k in range(total):
+                inv = np.linalg.inv(obj_tf[k, frame])
+                ol, dl = ow @ inv[:3, :3].T + inv[:3, 3], dw @ inv[:3, :3].T
+                t0, t1 = (-scale / 2 - ol) / dl, (scale / 2 - ol) / dl
+                near, far = np.minimum(t0, t1).max(axis=1), np.maximum(t0, t1).min(axis=1)
+                t = np.minimum(t, np.where((near < far) & (near > 0), near + 0.02, np.inf))      # 2 cm under the surface
+        hit = t < 75.0
+        return o[hit].astype(np.float32), dirs[hit].astype(np.float32), (t[hit] + g.normal(0.0, 0.01, int(hit.sum()))).astype(np.float32)
+
+    def load_image(camera, frame):
+        h, w = mounts[camera][1]
+        y, x = np.mgrid[0:h, 0:w]
+        c = len(camera)
+        return np.stack([1 + (x * 7 + y * 13 + frame * 17 + c) % 255, 1 + (x * 3 + y * 5 + frame * 11 + 2 * c) % 255, 1 + (x + y * 2 + frame * 29 + 3 * c) % 255],
+                        axis=2).astype(np.uint8)
+
+    return scenario, load_lidar, load_image
