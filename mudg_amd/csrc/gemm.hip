@@ -559,29 +559,13 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
     if constexpr (G::WIDE) {
         float* stg = reinterpret_cast<float*>(smem);
         float* sbias = stg + BM * WSTG;
-        bool gbias_rows = p.gbias != nullptr;
-        if (p.gbias && !p.geglu) {
-            const int mlast = (m0 + BM <= p.M ? m0 + BM : p.M) - 1;
-            const int g0 = m0 / p.rows_per_group;
-            if (g0 == mlast / p.rows_per_group) {
-                gbias_rows = false;
-                for (int t = tid; t < BN; t += NTH) {
-                    float b = (p.bias && n0 + t < p.N) ? p.bias[n0 + t] : 0.f;
-                    if (n0 + t < p.N) b += p.gbias[(int64_t)g0 * p.N + n0 + t];
-                    sbias[t] = b;
-                }
-            }
-        }
-        if (gbias_rows || !p.gbias || p.geglu) {     // straddling tile: bias + group bias go row by row as one pre-summed constant (see below)
-            for (int t = tid; t < BN; t += NTH) sbias[t] = (!(gbias_rows && !p.geglu) && p.bias && n0 + t < p.N) ? p.bias[n0 + t] : 0.f;
-        }
+        const bool gbias_rows = stage_bias(sbias, p, m0, n0, BM, BN, tid, NTH);
         __syncthreads();
 
         const float alpha = p.alpha;
         const int Nout = p.geglu ? p.N / 2 : p.N;
         const int nout0 = p.geglu ? n0 / 2 : n0;
         const int cc = tid & 15, rr = (tid >> 4) & 15, half = tid >> 8;
-        const int hw_o = MODE == 1 ? p.Hout * p.Wout : 1;
         constexpr int NPASSW = (NI + 1) / 2;
         const int RK = p.R ? p.res_fp32 : 3, OK = p.out_fp32;          // storage kinds of the residual (3 = none) and of Y
         const char* Rb = reinterpret_cast<const char*>(p.R) + bz * p.sR * (RK == KIND_F32 ? 4 : 2);
@@ -604,7 +588,7 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
                                 const int nb = q * 128 + nl;                               // column inside the tile (bias index)
                                 f32x4 v;
 #pragma unroll
-                                for (int j = 0; j < 4; ++j) v[j] = alpha * acc[ni < NI ? ni : 0][mi][4 * g + j] + sbias[nb + j];
+                                for (int j = 0; j < 4; ++j) v[j] = scale_bias(alpha, acc[ni < NI ? ni : 0][mi][4 * g + j], sbias[nb + j]);
                                 if (p.act) {
 #pragma unroll
                                     for (int j = 0; j < 4; ++j) v[j] = gelu_fast(v[j]);
@@ -618,23 +602,14 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int nb = q * 128 + wn * 64 + 8 * g + 4 * hi;                 // value columns inside the tile
-                        f32x4 v;
-                        float gate[4];
+                        float v[4], gate[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            v[j] = alpha * acc[2 * q][mi][4 * g + j] + sbias[nb + j];
-                            gate[j] = alpha * acc[2 * q + 1][mi][4 * g + j] + sbias[nb + 32 + j];
+                            v[j] = scale_bias(alpha, acc[2 * q][mi][4 * g + j], sbias[nb + j]);
+                            gate[j] = scale_bias(alpha, acc[2 * q + 1][mi][4 * g + j], sbias[nb + 32 + j]);
                         }
-                        // (table or polynomial: decided per group, not inside the per-value expression — there the compiler kept a branch
-                        // and a serialised LDS round trip per value; wgemm.hip, w_epilogue)
-                        if (phi) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) v[j] *= gelu_lut(gate[j], phis);
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) v[j] *= gelu_fast(gate[j]);
-                        }
-                        *reinterpret_cast<f32x4*>(&stg[ml * WSTG + wn * 32 + 8 * g + 4 * hi]) = v;
+                        geglu_gate<4>(v, gate, phi != nullptr, phis);
+                        *reinterpret_cast<f32x4*>(&stg[ml * WSTG + wn * 32 + 8 * g + 4 * hi]) = f32x4{v[0], v[1], v[2], v[3]};
                     }
                 }
             }
@@ -678,80 +653,18 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
                 for (int u = 0; u < 4; ++u) {
                     if (!ok[u]) continue;
                     const int64_t m = mrow[u];
-                    if (gbias_rows) {
-                        const float* gb = p.gbias + (int64_t)(m / p.rows_per_group) * Nout + n;
-                        const bool withb = p.bias && !p.geglu;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) if (j < nvalid) v[u][j] += withb ? p.bias[n + j] + gb[j] : gb[j];
-                    }
+                    if (gbias_rows) add_group_bias_row(v[u], p, (int)m, n, Nout, nvalid);
                     if (RK != 3) {
-                        if (wideR) {
-                            if (RK == KIND_F32) {
-                                union { u32x4 w; f32x4 f; } ta, tb; ta.w = ra[u]; tb.w = rb[u];
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) { v[u][j] += ta.f[j]; v[u][4 + j] += tb.f[j]; }
-                            } else if (RK == KIND_F16) {
-                                union { u32x4 w; f16x8 h; } t; t.w = ra[u];
-#pragma unroll
-                                for (int j = 0; j < 8; ++j) v[u][j] += (float)t.h[j];
-                            } else {
-                                const h16x8 t = as_h16x8(ra[u]);
-#pragma unroll
-                                for (int j = 0; j < 8; ++j) v[u][j] += (float)t[j];
-                            }
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) if (j < nvalid) {
-                                const int64_t ro = bz * p.sR + m * p.ldr + n + j;
-                                v[u][j] += RK == KIND_F32 ? reinterpret_cast<const float*>(p.R)[ro]
-                                         : (RK == KIND_F16 ? (float)reinterpret_cast<const _Float16*>(p.R)[ro] : (float)reinterpret_cast<const h16*>(p.R)[ro]);
-                            }
-                        }
+                        if (wideR) add_residual_raw(v[u], ra[u], rb[u], RK);
+                        else add_residual(v[u], p.R, RK, bz * p.sR + m * p.ldr + n, p.ldr / PLANES, nvalid, false);
                     }
                     if (p.stats) {
-                        float t[8];                     // what the store will hold — the storage kind decided once per row (wgemm.hip, w_epilogue)
-                        if (OK == KIND_F32) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) t[j] = v[u][j];
-                        } else if (OK == KIND_F16) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) t[j] = (float)f16_sat(v[u][j]);
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) t[j] = (float)(h16)v[u][j];
-                        }
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float tt = (j < nvalid) ? t[j] : 0.f;
-                            gs[j] += tt; gq[j] = fmaf(tt, tt, gq[j]);
-                        }
+                        float t[8];
+                        stored_value(v[u], OK, t);
+                        stats_add(t, nvalid, gs, gq);
                     }
-                    int64_t yoff;
-                    if (sub) {
-                        const int f = (int)(m / hw_o), r = (int)(m - (int64_t)f * hw_o);
-                        const int oy = r / p.Wout, ox = r - oy * p.Wout;
-                        yoff = (((int64_t)(f * p.Hout + oy) * 2 + dy0) * (2 * p.Wout) + 2 * ox + dx0) * p.ldy + n;
-                    } else {
-                        yoff = bz * p.sY + m * p.ldy + n;
-                    }
-                    if (OK == KIND_F16) {
-                        _Float16* yp = reinterpret_cast<_Float16*>(p.Y) + yoff;
-                        if (wideY) store8_f16(yp, v[u]);
-                        else for (int j = 0; j < nvalid; ++j) yp[j] = f16_sat(v[u][j]);
-                    } else if (OK == KIND_F32) {
-                        float* yp = reinterpret_cast<float*>(p.Y) + yoff;
-                        if (wideY) {
-                            f32x4 a, b;
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) { a[j] = v[u][j]; b[j] = v[u][4 + j]; }
-                            *reinterpret_cast<f32x4*>(yp) = a;
-                            *reinterpret_cast<f32x4*>(yp + 4) = b;
-                        } else for (int j = 0; j < nvalid; ++j) yp[j] = v[u][j];
-                    } else {
-                        h16* yp = reinterpret_cast<h16*>(p.Y) + yoff;
-                        if (wideY) store8_operand(yp, p.ldy, v[u]);
-                        else for (int j = 0; j < nvalid; ++j) yp[j] = (h16)v[u][j];
-                    }
+                    const int64_t yoff = (sub ? subpixel_row_offset(p, (int)m, dy0, dx0) : bz * p.sY + m * p.ldy) + n;
+                    store_piece(p.Y, yoff, OK, p.ldy / PLANES, v[u], nvalid, wideY);
                 }
             }
             __syncthreads();                      // staging is free again
@@ -784,27 +697,8 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
     float* stg = reinterpret_cast<float*>(smem);
     constexpr int PROWS = epi_rows<G>(FAST, SB), NPASS = BM / PROWS;
     float* sbias = stg + PROWS * STGLD;
-    // Per-group bias (a ResBlock's embedding term): when all rows of the tile belong to one group — always, for the
-    // UNet's shapes — it is one more per-column constant and rides in the staged bias; a tile that straddles groups adds
-    // it row by row in the store loop.
-    bool gbias_rows = p.gbias != nullptr;
-    if (p.gbias && !p.geglu) {
-        const int mlast = (m0 + BM <= p.M ? m0 + BM : p.M) - 1;
-        const int g0 = m0 / p.rows_per_group;
-        if (g0 == mlast / p.rows_per_group) {
-            gbias_rows = false;
-            for (int t = tid; t < BN; t += NTH) {
-                float b = (p.bias && n0 + t < p.N) ? p.bias[n0 + t] : 0.f;
-                if (n0 + t < p.N) b += p.gbias[(int64_t)g0 * p.N + n0 + t];
-                sbias[t] = b;
-            }
-        }
-    }
-    // (a straddling tile adds bias + group bias row by row, as ONE pre-summed constant like the staged one: a row's bits must not
-    // depend on which of the two paths its tile took — that changes with M, i.e. with how many clips share the launch)
-    if (gbias_rows || !p.gbias || p.geglu) {
-        for (int t = tid; t < BN; t += NTH) sbias[t] = (!(gbias_rows && !p.geglu) && p.bias && n0 + t < p.N) ? p.bias[n0 + t] : 0.f;
-    }
+    // Per-group bias (a ResBlock's embedding term): rides in the staged bias, or goes row by row in the store loop (stage_bias).
+    const bool gbias_rows = stage_bias(sbias, p, m0, n0, BM, BN, tid, NTH);
     __syncthreads();
 
     const float alpha = p.alpha;
@@ -822,9 +716,7 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
         rstep = NTH / cpr; r0 = tid / cpr; cc = tid - r0 * cpr;
         if (r0 >= rstep) r0 = PROWS;               // idle
     }
-    const h16* R = (p.R && p.res_fp32 == KIND_OPERAND) ? reinterpret_cast<const h16*>(p.R) + bz * p.sR : nullptr;
-    const float* Rf = (p.R && p.res_fp32 == KIND_F32) ? reinterpret_cast<const float*>(p.R) + bz * p.sR : nullptr;
-    const _Float16* Rh = (p.R && p.res_fp32 == KIND_F16) ? reinterpret_cast<const _Float16*>(p.R) + bz * p.sR : nullptr;
+    const int RK = p.res_fp32, OK = p.out_fp32;        // storage kinds of the residual and of Y
     float gs[8], gq[8];            // GroupNorm partials of this thread's 8 output channels (p.stats)
 #pragma unroll
     for (int j = 0; j < 8; ++j) { gs[j] = 0.f; gq[j] = 0.f; }
@@ -843,7 +735,7 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
                     const int nl = wn * (32 * NI) + ni * 32 + 8 * g + 4 * hi;
                     f32x4 v;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = alpha * acc[ni][mi][4 * g + j] + sbias[nl + j];
+                    for (int j = 0; j < 4; ++j) v[j] = scale_bias(alpha, acc[ni][mi][4 * g + j], sbias[nl + j]);
                     if (p.act) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) v[j] = PLANES > 2 ? gelu_erf_f(v[j]) : gelu_fast(v[j]);
@@ -856,24 +748,14 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int nl = wn * (32 * NI) + q * 64 + 8 * g + 4 * hi;      // value columns of pair q; its gates sit 32 further
-                f32x4 v;
-                float gate[4];
+                float v[4], gate[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    v[j] = alpha * acc[2 * q][mi][4 * g + j] + sbias[nl + j];
-                    gate[j] = alpha * acc[2 * q + 1][mi][4 * g + j] + sbias[nl + 32 + j];
+                    v[j] = scale_bias(alpha, acc[2 * q][mi][4 * g + j], sbias[nl + j]);
+                    gate[j] = scale_bias(alpha, acc[2 * q + 1][mi][4 * g + j], sbias[nl + 32 + j]);
                 }
-                if (PLANES > 2) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] *= gelu_erf_f(gate[j]);
-                } else if (phi) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] *= gelu_lut(gate[j], phis);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] *= gelu_fast(gate[j]);
-                }
-                *reinterpret_cast<f32x4*>(&stg[ml * STGLD + wn * (16 * NI) + q * 32 + 8 * g + 4 * hi]) = v;
+                geglu_gate<4>(v, gate, phi != nullptr, phis);
+                *reinterpret_cast<f32x4*>(&stg[ml * STGLD + wn * (16 * NI) + q * 32 + 8 * g + 4 * hi]) = f32x4{v[0], v[1], v[2], v[3]};
             }
         }
     }
@@ -882,35 +764,7 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
 
     const int n = nout0 + cc * 8;
     const int nvalid = n >= Nout ? 0 : ((Nout - n) < 8 ? (Nout - n) : 8);
-    if (sub) {
-        // sub-pixel conv: bias only (host-checked), rows scattered to this parity class's pixels of the full-resolution image
-        for (int row = r0; row < PROWS; row += rstep) {
-            const int m = m0 + pass * PROWS + row;
-            if (m >= p.M || nvalid == 0) break;
-            const int hw = p.Hout * p.Wout;
-            const int f = m / hw, r = m - f * hw;
-            const int oy = r / p.Wout, ox = r - oy * p.Wout;
-            const int64_t yoff = (((int64_t)(f * p.Hout + oy) * 2 + dy0) * (2 * p.Wout) + 2 * ox + dx0) * p.ldy + n;
-            float v[8];
-            const f32x4 a = *reinterpret_cast<const f32x4*>(&stg[row * STGLD + cc * 8]);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(&stg[row * STGLD + cc * 8 + 4]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-            const bool wide = nvalid == 8 && (vflags & VF_Y);
-            if (p.out_fp32 == KIND_F16) {
-                _Float16* yp = reinterpret_cast<_Float16*>(p.Y) + yoff;
-                if (wide) store8_f16(yp, v);
-                else for (int j = 0; j < nvalid; ++j) yp[j] = f16_sat(v[j]);
-            } else if (p.out_fp32) {
-                float* yp = reinterpret_cast<float*>(p.Y) + yoff;
-                for (int j = 0; j < nvalid; ++j) yp[j] = v[j];
-            } else {
-                h16* yp = reinterpret_cast<h16*>(p.Y) + yoff;
-                if (wide) store8_operand(yp, p.ldy / PLANES, v);
-                else for (int j = 0; j < nvalid; ++j) store1_operand(yp + j, p.ldy / PLANES, v[j]);
-            }
-        }
-    } else
+    const bool wideY = nvalid == 8 && (vflags & VF_Y), wideR = nvalid == 8 && (vflags & VF_R);
     for (int row = r0; row < PROWS; row += rstep) {
         const int m = m0 + pass * PROWS + row;
         if (m >= p.M || nvalid == 0) break;
@@ -922,111 +776,28 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
 #pragma unroll
             for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
         }
-        if (gbias_rows) {
-            const float* gb = p.gbias + (int64_t)(m / p.rows_per_group) * Nout + n;
-            const bool withb = p.bias && !p.geglu;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) if (j < nvalid) v[j] += withb ? p.bias[n + j] + gb[j] : gb[j];
-        }
-        if (R) {
-            const h16* rp = R + mp * p.ldr + n;
-            if (nvalid == 8 && (vflags & VF_R)) {
-                float rr[8];
-                load8_operand(rp, p.ldr / PLANES, rr);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] += rr[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < nvalid) v[j] += load1_operand(rp + j, p.ldr / PLANES);
-            }
-        }
-        if (Rf) {
-            const float* rp = Rf + mp * p.ldr + n;
-            if (nvalid == 8 && (vflags & VF_R)) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(rp), b = *reinterpret_cast<const f32x4*>(rp + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { v[j] += a[j]; v[4 + j] += b[j]; }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < nvalid) v[j] += rp[j];
-            }
-        }
-        if (Rh) {
-            const _Float16* rp = Rh + mp * p.ldr + n;
-            if (nvalid == 8 && (vflags & VF_R)) {
-                float rr[8];
-                load8_f16(rp, rr);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] += rr[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < nvalid) v[j] += (float)rp[j];
-            }
-        }
+        // (a sub-pixel conv has bias only — host-checked: no group bias, residual, partials or fp8 copy)
+        if (gbias_rows) add_group_bias_row(v, p, m, n, Nout, nvalid);
+        if (p.R) add_residual(v, p.R, RK, bz * p.sR + mp * p.ldr + n, p.ldr / PLANES, nvalid, wideR);
         if (p.stats) {
             float t[8];
-            if (p.out_fp32 == KIND_F32) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) t[j] = v[j];
-            } else if (p.out_fp32 == KIND_F16) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) t[j] = (float)f16_sat(v[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) t[j] = operand_round(v[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float tt = (j < nvalid) ? t[j] : 0.f;
-                gs[j] += tt; gq[j] = fmaf(tt, tt, gq[j]);
-            }
+            stored_value(v, OK, t);
+            stats_add(t, nvalid, gs, gq);
         }
-        const int64_t yoff = bz * p.sY + mp * p.ldy + n;
-        if (p.out_fp32 == KIND_F16) {
-            _Float16* yp = reinterpret_cast<_Float16*>(p.Y) + yoff;
-            if (nvalid == 8 && (vflags & VF_Y)) {
-                store8_f16(yp, v);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < nvalid) yp[j] = f16_sat(v[j]);
-            }
-        } else if (p.out_fp32) {
-            float* yp = reinterpret_cast<float*>(p.Y) + yoff;
-            if (nvalid == 8 && (vflags & VF_Y)) {
-                f32x4 a, b;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { a[j] = v[j]; b[j] = v[4 + j]; }
-                *reinterpret_cast<f32x4*>(yp) = a;
-                *reinterpret_cast<f32x4*>(yp + 4) = b;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < nvalid) yp[j] = v[j];
-            }
-        } else {
-            h16* yp = reinterpret_cast<h16*>(p.Y) + yoff;
-            if (nvalid == 8 && (vflags & VF_Y)) {
-                store8_operand(yp, p.ldy / PLANES, v);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < nvalid) store1_operand(yp + j, p.ldy / PLANES, v[j]);
-            }
+        // sub-pixel conv: rows scattered to this parity class's pixels of the full-resolution image
+        const int64_t yoff = (sub ? subpixel_row_offset(p, m, dy0, dx0) : bz * p.sY + mp * p.ldy) + n;
+        store_piece(p.Y, yoff, OK, p.ldy / PLANES, v, nvalid, wideY);
 #if MUDG_PLANES == 1
-            if constexpr (!SB) if (p.Y8) {      // (the 4-per-CU variant has no registers to spare: Y8 problems run on this one) MX-fp8 copy of what was just stored: a 32-column block = the four adjacent lanes cc & ~3 .. + 3 of this row
-                float r8[8], amax = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { r8[j] = (float)(h16)v[j]; amax = fmaxf(amax, fabsf(r8[j])); }
-                amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-                amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-                const int E = mx_block_exponent(amax);
-                const float inv = __uint_as_float((unsigned)(127 - E) << 23);
-                u32x2 w8;
-                w8[0] = mx_pack4_e4m3(r8[0], r8[1], r8[2], r8[3], inv);
-                w8[1] = mx_pack4_e4m3(r8[4], r8[5], r8[6], r8[7], inv);
-                *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned char*>(p.Y8) + mp * p.ldy8 + n) = w8;
-                if ((cc & 3) == 0) reinterpret_cast<unsigned char*>(p.S8)[(int64_t)m * p.lds8 + (n >> 5)] = (unsigned char)(E + 127);
-            }
-#endif
+        if constexpr (!SB) if (OK == KIND_OPERAND && p.Y8) {      // (the 4-per-CU variant has no registers to spare: Y8 problems run on this one) MX-fp8 copy of what was just stored: a 32-column block = the four adjacent lanes cc & ~3 .. + 3 of this row
+            float r8[8];
+            float amax = mx8_round(v, r8);
+            amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+            amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+            const int E = mx_block_exponent(amax);
+            *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned char*>(p.Y8) + mp * p.ldy8 + n) = mx8_pack8(r8, mx8_inv_scale(E));
+            if ((cc & 3) == 0) reinterpret_cast<unsigned char*>(p.S8)[(int64_t)m * p.lds8 + (n >> 5)] = (unsigned char)(E + 127);
         }
+#endif
     }
     // GroupNorm partials are per 128-row block of Y (MudgGemmDesc.stats): flush whenever the passes done so far end one.
     const bool flush = p.stats && (((pass + 1) * PROWS) % 128 == 0 || pass == NPASS - 1);

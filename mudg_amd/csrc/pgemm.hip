@@ -360,17 +360,7 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
                     float v[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = 0.f;
-                    if (32 * mi < mrem && n < p.N) {
-                        if (RK == KIND_F32) {
-                            const f32x4 a = *reinterpret_cast<const f32x4*>(Rb + re * 4), b = *reinterpret_cast<const f32x4*>(Rb + re * 4 + 16);
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-                        } else if (RK == KIND_F16) {
-                            load8_f16(reinterpret_cast<const _Float16*>(Rb) + re, v);
-                        } else {
-                            load8_operand(reinterpret_cast<const h16*>(Rb) + re, p.ldr / PLANES, v);
-                        }
-                    }
+                    if (32 * mi < mrem && n < p.N) load_piece8(Rb, RK, re, p.ldr / PLANES, v);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) acc[ni][mi][8 * q + j] = v[j];
                 }
@@ -391,15 +381,9 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
         unsigned yo[MI];
         const int row0 = wm * 64 + l31;                       // + 32 mi
         if (subp) {
-            const int hw = p.Hout * p.Wout;
-            auto off = [&](int m) -> int64_t {
-                const int f = m / hw, r = m - f * hw;
-                const int oy = r / p.Wout, ox = r - oy * p.Wout;
-                return (((int64_t)(f * p.Hout + oy) * 2 + edy) * (2 * p.Wout) + 2 * ox + edx) * p.ldy;
-            };
-            ybase = off(em0);
+            ybase = subpixel_row_offset(p, em0, edy, edx);
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi) yo[mi] = (unsigned)(off(em0 + row0 + 32 * mi) - ybase);
+            for (int mi = 0; mi < MI; ++mi) yo[mi] = (unsigned)(subpixel_row_offset(p, em0 + row0 + 32 * mi, edy, edx) - ybase);
         } else {
             ybase = (int64_t)ez * p.sY + (int64_t)em0 * p.ldy;
 #pragma unroll
@@ -434,12 +418,13 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
                 const bool live = 32 * mi < mrem && cols;
                 float v[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = alpha * acc[GEGLU ? 0 : NIX][mi][8 * Q + j] + bv[j];
+                for (int j = 0; j < 8; ++j) v[j] = scale_bias(alpha, acc[GEGLU ? 0 : NIX][mi][8 * Q + j], bv[j]);
                 if constexpr (GEGLU) {
                     float gate[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) gate[j] = alpha * acc[1][mi][8 * Q + j] + bg[j];
-                    if (phi) {                            // (decided per row, not per value: wgemm.hip, w_epilogue)
+                    for (int j = 0; j < 8; ++j) gate[j] = scale_bias(alpha, acc[1][mi][8 * Q + j], bg[j]);
+                    // geglu_gate<8> (gemm_shared.h) spelled out: through the helper the 128-register kernel spilled 24 bytes instead of 20
+                    if (phi) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) v[j] *= gelu_lut(gate[j], phis);
                     } else {
@@ -448,17 +433,9 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
                     }
                 } else if (RS && p.stats) {
                     // partial sums over what is stored: the lane's two rows here, the 32 pixels of the half-wave below
-                    float tk[8];                        // the storage kind decided once per row (wgemm.hip, w_epilogue)
-                    if (OK == KIND_F32) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) tk[j] = v[j];
-                    } else if (OK == KIND_F16) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) tk[j] = (float)f16_sat(v[j]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) tk[j] = operand_round(v[j]);
-                    }
+                    // (the two-row sum t0 + t, fma(t, t, t0 t0) is this kernel's own association: not stats_add's)
+                    float tk[8];
+                    stored_value(v, OK, tk);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const float t = live ? tk[j] : 0.f;
@@ -467,25 +444,13 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
                     }
                 }
                 if (live) {
-                    const size_t ye = (size_t)yo[mi] + n;                                     // element offset from Yb
-                    if (OK == KIND_F32) {
-                        float* yp = reinterpret_cast<float*>(Yb) + ye;
-                        f32x4 a, b;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) { a[j] = v[j]; b[j] = v[4 + j]; }
-                        *reinterpret_cast<f32x4*>(yp) = a;
-                        *reinterpret_cast<f32x4*>(yp + 4) = b;
-                    } else if (OK == KIND_F16) {
-                        store8_f16(reinterpret_cast<_Float16*>(Yb) + ye, v);
-                    } else {
-                        store8_operand(reinterpret_cast<h16*>(Yb) + ye, p.ldy / PLANES, v);
-                        if constexpr (Y8OK) if (p.Y8) {
-                            float amax = 0.f;
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) { y8v[mi][Q][j] = (float)(h16)v[j]; amax = fmaxf(amax, fabsf(y8v[mi][Q][j])); }
-                            y8a[mi] = Q == 0 ? amax : fmaxf(y8a[mi], amax);
-                        }
+                    store_piece(Yb, (int64_t)((size_t)yo[mi] + n), OK, p.ldy / PLANES, v, 8, true);     // element offset from Yb
+#if MUDG_PLANES == 1
+                    if constexpr (Y8OK) if (OK == KIND_OPERAND && p.Y8) {
+                        const float amax = mx8_round(v, y8v[mi][Q]);
+                        y8a[mi] = Q == 0 ? amax : fmaxf(y8a[mi], amax);
                     }
+#endif
                 }
             }
 #if MUDG_PLANES == 1
@@ -498,16 +463,11 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
                     const float amax = fmaxf(mine, __shfl_xor(mine, 32, 64));
                     if (!live) continue;
                     const int E = mx_block_exponent(amax);
-                    const float inv = __uint_as_float((unsigned)(127 - E) << 23);
+                    const float inv = mx8_inv_scale(E);
                     const int64_t m = em0 + row0 + 32 * mi;
                     unsigned char* y8 = reinterpret_cast<unsigned char*>(p.Y8) + m * p.ldy8 + n - 16;
 #pragma unroll
-                    for (int qq = 0; qq < 2; ++qq) {
-                        u32x2 w8;
-                        w8[0] = mx_pack4_e4m3(y8v[mi][qq][0], y8v[mi][qq][1], y8v[mi][qq][2], y8v[mi][qq][3], inv);
-                        w8[1] = mx_pack4_e4m3(y8v[mi][qq][4], y8v[mi][qq][5], y8v[mi][qq][6], y8v[mi][qq][7], inv);
-                        *reinterpret_cast<u32x2*>(y8 + 16 * qq) = w8;
-                    }
+                    for (int qq = 0; qq < 2; ++qq) *reinterpret_cast<u32x2*>(y8 + 16 * qq) = mx8_pack8(y8v[mi][qq], inv);
                     if (hi == 0) reinterpret_cast<unsigned char*>(p.S8)[m * p.lds8 + (n >> 5)] = (unsigned char)(E + 127);
                 }
             }

@@ -298,18 +298,16 @@ __device__ __forceinline__ void w_epilogue(const MudgGemmDesc& p, f32x4 (&acc)[N
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float a = acc[i][e >> 2][e & 3], b = acc[i][2 + (e >> 2)][e & 3];
-                    val[e] = UA ? a + bv[e] : alpha * a + bv[e];
-                    gate[e] = UA ? b + bg[e] : alpha * b + bg[e];
+                    val[e] = UA ? a + bv[e] : scale_bias(alpha, a, bv[e]);
+                    gate[e] = UA ? b + bg[e] : scale_bias(alpha, b, bg[e]);
                 }
-                if constexpr (!TAB) {
+                if constexpr (!TAB || (PLANES != 2 && LUT == 1)) {      // the polynomial, or the plain table: the shared gate
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = val[e] * gelu_fast(gate[e]);
+                    for (int e = 0; e < 8; ++e) v[e] = val[e];
+                    geglu_gate<8>(v, gate, TAB, tail);
                 } else if constexpr (PLANES == 2) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = val[e] * gelu_hermite(gate[e], phis);
-                } else if constexpr (LUT == 1) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = val[e] * gelu_lut(gate[e], tail);
                 } else {                                  // gelu_lut2 in stages: eight indices, eight reads, eight interpolations
                     float u[8];
                     f32x2 t[8];
@@ -324,53 +322,17 @@ __device__ __forceinline__ void w_epilogue(const MudgGemmDesc& p, f32x4 (&acc)[N
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float a = acc[i][2 * P + (e >> 2)][e & 3];
-                    v[e] = UA ? a + bv[e] : alpha * a + bv[e];
+                    v[e] = UA ? a + bv[e] : scale_bias(alpha, a, bv[e]);
                 }
-                if constexpr (DR) {
-                    constexpr int RT = decltype(rtag)::value;             // 1: fp16 stream, 2: operand storage
-                    if constexpr (RT == 1) {
-                        union { u32x4 w; f16x8 hh; } t; t.w = sraw[i][P];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += (float)t.hh[e];
-                    } else {
-                        const h16x8 t = as_h16x8(sraw[i][P]);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += (float)t[e];
-                    }
-                }
+                // (rtag — 1: fp16 stream, 2: operand storage; the kind is a constant of the instantiation)
+                if constexpr (DR) add_residual_raw(v, sraw[i][P], zero16(), decltype(rtag)::value == 1 ? KIND_F16 : KIND_OPERAND);
             }
             if (!GEGLU && p.stats) {
-                // what the store will hold, per storage kind — the kind decided once per row, not inside the per-value expression (there
-                // it was a chain of scalar compares and branches per VALUE: round 6)
                 float t[8];
-                if (OK == KIND_F32) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) t[e] = v[e];
-                } else if (OK == KIND_F16) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) t[e] = (float)f16_sat(v[e]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) t[e] = operand_round(v[e]);
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float tt = live ? t[e] : 0.f;
-                    gs[e] += tt; gq[e] = fmaf(tt, tt, gq[e]);
-                }
+                stored_value(v, OK, t);
+                stats_add(t, live ? 8 : 0, gs, gq);
             }
-            if (live) {
-                const int64_t yoff = m * p.ldy + n;
-                if (OK == KIND_F16) store8_f16(reinterpret_cast<_Float16*>(p.Y) + yoff, v);
-                else if (OK == KIND_F32) {
-                    float* yp = reinterpret_cast<float*>(p.Y) + yoff;
-                    f32x4 a, b;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { a[e] = v[e]; b[e] = v[4 + e]; }
-                    *reinterpret_cast<f32x4*>(yp) = a;
-                    *reinterpret_cast<f32x4*>(yp + 4) = b;
-                } else store8_operand(reinterpret_cast<h16*>(p.Y) + yoff, p.ldy / PLANES, v);
-            }
+            if (live) store_piece(p.Y, m * p.ldy + n, OK, p.ldy / PLANES, v, 8, true);
         }
         if (!GEGLU && p.stats) {
             // the 16 pixels of the fragment column (a DPP row) folded in a fixed order; lane px = 0 of each q hands its M half's sums over
@@ -403,58 +365,14 @@ __device__ __forceinline__ void w_epilogue(const MudgGemmDesc& p, f32x4 (&acc)[N
             const bool live = m < p.M;
             float v[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { const float a = acc[i][J < NREP ? J : 0][e]; v[e] = UA ? a + bv[e] : alpha * a + bv[e]; }
-            if constexpr (DR) {
-                if constexpr (decltype(rtag)::value == 1) {
-                    union { u32x2 w; _Float16 hh[4]; } t; t.w = srs[i];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)t.hh[e];
-                } else {
-                    Pack8 t; t.u = srs[i];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)t.h[e];
-                }
-            }
+            for (int e = 0; e < 4; ++e) { const float a = acc[i][J < NREP ? J : 0][e]; v[e] = UA ? a + bv[e] : scale_bias(alpha, a, bv[e]); }
+            if constexpr (DR) add_residual_raw(v, srs[i], decltype(rtag)::value == 1 ? KIND_F16 : KIND_OPERAND);
             if (p.stats) {
                 float t[4];
-                if (OK == KIND_F32) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] = v[e];
-                } else if (OK == KIND_F16) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] = (float)f16_sat(v[e]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] = operand_round(v[e]);
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float tt = live ? t[e] : 0.f;
-                    gs[e] += tt; gq[e] = fmaf(tt, tt, gq[e]);
-                }
+                stored_value(v, OK, t);
+                stats_add(t, live ? 4 : 0, gs, gq);
             }
-            if (live) {
-                const int64_t yoff = m * p.ldy + n;
-                if (OK == KIND_F16) {
-                    union { u32x2 w; _Float16 h[4]; } t;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t.h[e] = f16_sat(v[e]);
-                    *reinterpret_cast<u32x2*>(reinterpret_cast<_Float16*>(p.Y) + yoff) = t.w;
-                } else if (OK == KIND_F32) {
-                    f32x4 a;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a[e] = v[e];
-                    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.Y) + yoff) = a;
-                } else {
-#pragma unroll
-                    for (int pl = 0; pl < PLANES; ++pl) {               // the pieces of store8_operand, four channels wide
-                        Pack8 t;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { t.h[e] = (h16)v[e]; v[e] -= (float)t.h[e]; }
-                        *reinterpret_cast<u32x2*>(reinterpret_cast<h16*>(p.Y) + yoff + pl * (p.ldy / PLANES)) = t.u;
-                    }
-                }
-            }
+            if (live) store_piece(p.Y, m * p.ldy + n, OK, p.ldy / PLANES, v, 4, true);
         }
         if (p.stats) {
 #pragma unroll
