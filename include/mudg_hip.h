@@ -364,6 +364,32 @@ int mudg_cloud_voxel_reduce(const void* points, const int64_t* order, const int6
                             uint64_t* sums, int64_t voxels, void* stream);
 int mudg_cloud_voxel_finish(const uint64_t* sums, int64_t voxels, double voxel, void* points_out, void* stream);
 
+/* ------------------------------------------------------------------ metric depth and lifted views
+ * (data_process/depthlab_tools.py:67-87, 114-136; virtual_render/eval_tools.py:137-306; integer sums and fp64 / fp32 operations in a
+ * stated order: no output depends on execution order.)  frames_u8 is (frames, H, W, 3) uint8, the depth stream as frames_to_u8
+ * writes it; k = r + g + b per pixel, the stream's depth is k / 765.  frames <= 65535 and H W <= 2^24 everywhere.
+ * depth_align_sums: sums[frame][5] uint64, zero on entry, receive n, sum k, sum k^2, sum q and sum k q over the pixels with k > 0 and
+ *   0 < lidar < 256, q = rint(lidar 2^20) (fp64, half to even), lidar (frames, H, W) fp32 metres.
+ * depth_align_solve: the line lidar ~ m (k / 765) + c per frame: den = N Skk - Sk Sk, m' = (N Skq - Sk Sq) / den,
+ *   c' = (Sq - m' Sk) / N, coef[frame] = (m' 765 / 2^20, c' / 2^20) fp64, fitted[frame] = 1; n < 2 or den <= 0: (100, 0) and 0.
+ * depth_finish: depth[frame][H][W] fp32 = fp32(clip(m (double(k) / 765) + c, 0, 100)), 100 where labels (int64, or NULL: no sky rule)
+ *   equals sky_label; vis (frames, H, W, 3) uint8 (or NULL) is the Spectral picture of depth / 100.
+ * colormap_spectral: n fp32 values -> bytes (n, 3) uint8 and / or colours (n, 3) fp32 (either may be NULL): x = (x - fp32(val_min)) /
+ *   fp32(val_max - val_min) unless the range is (0, 1), pos = clamp(x, 0, 1) 10, left = (int)pos, right = min(left + 1, 10),
+ *   d = pos - left, colour = (1 - d) L + d R over the eleven Spectral colours (reversed: the table backwards), byte = (int)(colour 255).
+ * depth_unproject: table[frame][16] doubles = the top three rows of camera-to-world, then fx, fy, cx, cy at (H, W).  Pixel (row j,
+ *   column i) with depth z: xn = ((i + 0.5) - cx) / fx, yn likewise, p = c2w (xn z, yn z, z); points[frame][j][i] = 16 bytes (fp32 p,
+ *   r | g << 8 | b << 16 of rgb (frames, H, W, 3) uint8), valid[frame][j][i] = 1 iff min_depth < z < max_depth and the label is not
+ *   sky_label (labels NULL: no sky rule); a pixel that is not valid stores a zero point. */
+int mudg_depth_align_sums(const uint8_t* frames_u8, const float* lidar, int frames, int H, int W, uint64_t* sums, void* stream);
+int mudg_depth_align_solve(const uint64_t* sums, int frames, double* coef, uint8_t* fitted, void* stream);
+int mudg_depth_finish(const uint8_t* frames_u8, const double* coef, const int64_t* labels, int64_t sky_label, int frames, int H,
+                      int W, float* depth, uint8_t* vis, void* stream);
+int mudg_colormap_spectral(const float* values, int64_t n, double val_min, double val_max, int reversed, uint8_t* bytes,
+                           float* colours, void* stream);
+int mudg_depth_unproject(const float* depth, const uint8_t* rgb, const int64_t* labels, int64_t sky_label, const double* table,
+                         int frames, int H, int W, double min_depth, double max_depth, void* points, uint8_t* valid, void* stream);
+
 /* ------------------------------------------------------------------ training step
  * Reference: lvdm/models/ddpm3d.py:741-802 (p_losses), :1267-1300 (configure_optimizers -> torch.optim.AdamW),
  * main/utils_train.py:126-137 (data-parallel strategy).  The contractions of the backward pass (dX = dY W, dW = dY^T X,

@@ -811,3 +811,77 @@ def cloud_voxel_finish(sums, voxel):
     out = torch.empty((sums.shape[0], 4), dtype=torch.int32, device=sums.device)
     hip.check(hip.lib().mudg_cloud_voxel_finish(sums.data_ptr(), sums.shape[0], float(voxel), out.data_ptr(), _stream()), "mudg_cloud_voxel_finish")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ metric depth and lifted views
+def _depth_frames(name, frames):
+    _splat_tensor(f"{name}: frames", frames, torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise hip.MudgError(f"{name}: expected (frames, h, w, 3) uint8 frames, got {tuple(frames.shape)}")
+    return tuple(frames.shape[:3])
+
+
+def depth_align_sums(frames, lidar):
+    """frames (f, h, w, 3) uint8, the depth stream; lidar (f, h, w) fp32 metres -> (f, 5) int64 integer sums n, sum k, sum k^2, sum q,
+    sum k q over the pixels with k = r + g + b > 0 and 0 < lidar < 256, q = rint(lidar * 2^20)."""
+    f, h, w = _depth_frames("depth_align_sums", frames)
+    _splat_tensor("depth_align_sums: lidar", lidar, torch.float32, (f, h, w))
+    sums = torch.zeros((f, 5), dtype=torch.int64, device=frames.device)
+    hip.check(hip.lib().mudg_depth_align_sums(frames.data_ptr(), lidar.data_ptr(), f, h, w, sums.data_ptr(), _stream()), "mudg_depth_align_sums")
+    return sums
+
+
+def depth_align_solve(sums):
+    """(f, 5) sums -> (coef (f, 2) float64 = (m, c) of lidar ~ m * (k / 765) + c, fitted (f,) uint8); a frame with fewer than two counted
+    pixels or no spread in k gets (100, 0) and fitted = 0.  Nothing comes to the host."""
+    _splat_tensor("depth_align_solve: sums", sums, torch.int64)
+    if sums.dim() != 2 or sums.shape[1] != 5 or sums.shape[0] == 0:
+        raise hip.MudgError(f"depth_align_solve: expected (frames, 5) sums, got {tuple(sums.shape)}")
+    coef = torch.empty((sums.shape[0], 2), dtype=torch.float64, device=sums.device)
+    fitted = torch.empty((sums.shape[0],), dtype=torch.uint8, device=sums.device)
+    hip.check(hip.lib().mudg_depth_align_solve(sums.data_ptr(), sums.shape[0], coef.data_ptr(), fitted.data_ptr(), _stream()), "mudg_depth_align_solve")
+    return coef, fitted
+
+
+def depth_finish(frames, coef, labels=None, *, sky_label=10, visualise=False):
+    """frames (f, h, w, 3) uint8 and coef (f, 2) float64 -> depth (f, h, w) fp32 metres in [0, 100], 100 where labels (f, h, w) int64
+    equals sky_label; with visualise also the Spectral picture of depth / 100, (f, h, w, 3) uint8.  Returns (depth, vis or None)."""
+    f, h, w = _depth_frames("depth_finish", frames)
+    _splat_tensor("depth_finish: coef", coef, torch.float64, (f, 2))
+    if labels is not None:
+        _splat_tensor("depth_finish: labels", labels, torch.int64, (f, h, w))
+    depth = torch.empty((f, h, w), dtype=torch.float32, device=frames.device)
+    vis = torch.empty((f, h, w, 3), dtype=torch.uint8, device=frames.device) if visualise else None
+    hip.check(hip.lib().mudg_depth_finish(frames.data_ptr(), coef.data_ptr(), _ptr(labels), int(sky_label), f, h, w, depth.data_ptr(), _ptr(vis),
+                                          _stream()), "mudg_depth_finish")
+    return depth, vis
+
+
+def colormap_spectral(values, val_min=0.0, val_max=1.0, *, reversed=False, bytes=True):
+    """fp32 values of any shape -> their Spectral colours, shape + (3,): uint8 (bytes) or fp32, the reference's method_custom operation
+    for operation (eval_tools.py:206-246); values are first taken from [val_min, val_max] to [0, 1] unless that range is (0, 1)."""
+    _splat_tensor("colormap_spectral: values", values, torch.float32)
+    if values.numel() == 0:
+        raise hip.MudgError("colormap_spectral: no values")
+    if not float(val_max) > float(val_min):
+        raise hip.MudgError(f"colormap_spectral: invalid values range [{val_min}, {val_max}]")
+    out = torch.empty(tuple(values.shape) + (3,), dtype=torch.uint8 if bytes else torch.float32, device=values.device)
+    hip.check(hip.lib().mudg_colormap_spectral(values.data_ptr(), values.numel(), float(val_min), float(val_max), int(bool(reversed)),
+                                               out.data_ptr() if bytes else None, None if bytes else out.data_ptr(), _stream()), "mudg_colormap_spectral")
+    return out
+
+
+def depth_unproject(depth, rgb, table, labels=None, *, sky_label=10, min_depth=0.0, max_depth=100.0):
+    """depth (f, h, w) fp32 metres, rgb (f, h, w, 3) uint8 and table (f, 16) float64 (the top three rows of camera-to-world, then
+    fx, fy, cx, cy at (h, w)) -> packed points (f * h * w, 4) int32 and valid (f * h * w,) uint8: a pixel is valid iff
+    min_depth < depth < max_depth and its label is not sky_label; one that is not stores a zero point."""
+    f, h, w = _depth_frames("depth_unproject", rgb)
+    _splat_tensor("depth_unproject: depth", depth, torch.float32, (f, h, w))
+    _splat_tensor("depth_unproject: table", table, torch.float64, (f, 16))
+    if labels is not None:
+        _splat_tensor("depth_unproject: labels", labels, torch.int64, (f, h, w))
+    points = torch.empty((f * h * w, 4), dtype=torch.int32, device=depth.device)
+    valid = torch.empty((f * h * w,), dtype=torch.uint8, device=depth.device)
+    hip.check(hip.lib().mudg_depth_unproject(depth.data_ptr(), rgb.data_ptr(), _ptr(labels), int(sky_label), table.data_ptr(), f, h, w,
+                                             float(min_depth), float(max_depth), points.data_ptr(), valid.data_ptr(), _stream()), "mudg_depth_unproject")
+    return points, valid

@@ -49,6 +49,15 @@ class PointCloud:
     def from_arrays(cls, xyz, rgb, device="cuda"):
         return cls(_pack(xyz, rgb, torch.device(device)))
 
+    @classmethod
+    def concatenated(cls, *clouds):
+        """The clouds' packed buffers one after the other, nothing else (data_process/tools/merge_points.py:77-90 on packed points)."""
+        if not clouds or not all(isinstance(c, PointCloud) for c in clouds):
+            raise hip.MudgError("PointCloud.concatenated: expected one or more PointClouds")
+        if len({c.points.device for c in clouds}) != 1:
+            raise hip.MudgError("PointCloud.concatenated: the clouds are on different devices")
+        return cls(torch.cat([c.points for c in clouds], dim=0))
+
     def __len__(self):
         return self.points.shape[0]
 

@@ -141,3 +141,32 @@ def render_windows(scene, dense_frames, pose, video_length=16):
         sparse = cond["sparse_frames"].repeat(3, 1, 1, 1, 1)
         sparse[:, :, 0] = dense[:, :, 0].to(sparse.device)
         yield {"sparse": sparse, "dense": dense, "sparse_depth": cond["sparse_depth"].repeat(3, 1, 1, 1, 1), "class_label": labels}
+
+
+def window_outputs(samples, window_conditions, variant=0):
+    """What a window's three generated streams are worth downstream, all on the GPU.
+
+    samples: one entry of synthesize_windows' result, (3, n_samples, c, t, h, w) in [-1, 1], the colour, depth and semantic streams;
+    window_conditions: mudg_amd.render.render_conditions(..., return_images=True) of that window's frames at the pose it was generated
+    at (one pose: "depth" is (1, t, h, w) metres, 0 where no LiDAR return landed).  Returns a dict:
+      "color"            (t, h, w, 3) uint8     the colour stream, as save_virtual_color_results writes it (eval_tools.py:22-28)
+      "semantic_labels"  (t, h, w) int64        the nearest of the 19 class colours (eval_tools.py:309-347)
+      "semantic"         (t, h, w, 3) uint8     the labels' own colours
+      "depth"            (t, h, w) fp32 metres  the depth stream fitted per frame to the rendered LiDAR depth, 100 m on sky (class 10),
+                                                clipped to [0, 100] (data_process/depthlab_tools.py:67-87, 114-136)
+      "depth_vis"        (t, h, w, 3) uint8     its Spectral picture (eval_tools.py:137-306)
+      "coef", "fitted"   (t, 2) float64, (t,) uint8   the fitted line per frame; fitted = 0 where a frame had too few returns and the
+                                                stream's own 100 m scale was kept
+    variant: which of the n_samples to take."""
+    from mudg_amd import depth, ops
+    if samples.dim() != 6 or samples.shape[0] != 3 or samples.shape[2] != 3:
+        raise ValueError(f"window_outputs: samples {tuple(samples.shape)}, expected (3, n_samples, 3, t, h, w)")
+    lidar = window_conditions["depth"]
+    if lidar.dim() != 4 or lidar.shape[0] != 1 or tuple(lidar.shape[1:]) != (samples.shape[3],) + tuple(samples.shape[4:]):
+        raise ValueError(f"window_outputs: rendered depth {tuple(lidar.shape)} for samples {tuple(samples.shape)} (one pose, the window's frames)")
+    u8 = ops.frames_to_uint8(samples[:, variant])                             # (3, t, h, w, 3)
+    vis, labels = zip(*(ops.semantic_nearest(frame.permute(2, 0, 1)) for frame in u8[2]))
+    labels = torch.stack(labels)
+    metric = depth.metric_depth(u8[1], lidar[0], labels, visualise=True)
+    return {"color": u8[0], "semantic_labels": labels, "semantic": torch.stack(vis).permute(0, 2, 3, 1).contiguous(),
+            "depth": metric["depth"], "depth_vis": metric["vis"], "coef": metric["coef"], "fitted": metric["fitted"]}
