@@ -390,6 +390,27 @@ int mudg_colormap_spectral(const float* values, int64_t n, double val_min, doubl
 int mudg_depth_unproject(const float* depth, const uint8_t* rgb, const int64_t* labels, int64_t sky_label, const double* table,
                          int frames, int H, int W, double min_depth, double max_depth, void* points, uint8_t* valid, void* stream);
 
+/* ------------------------------------------------------------------ scores of generated views
+ * (This project's own rules: integer sums and fp64 operations in a stated order, no output depends on execution order.)  Colour frames
+ * are (frames, H, W, 3) uint8; frames <= 65535 and H W <= 2^24 everywhere; every output is zero on entry.
+ * metric_sse: sse[frame] uint64 receives the sum of (a - b)^2 over all pixels and channels.
+ * metric_ssim: Wang et al. 2004 over the valid region (H - 10) x (W - 10), H, W >= 11, per channel: integer window w (eleven taps that sum
+ *   to 2^16, see DESIGN), the five moments Sx, Sy, Sxx, Syy, Sxy = sum_ij w_i w_j (x, y, x^2, y^2, x y) as exact integers, then in fp64
+ *   mx = Sx / 2^32, vx = Sxx / 2^32 - mx mx, cxy = Sxy / 2^32 - mx my, s = ((2 mx my + C1)(2 cxy + C2)) / ((mx mx + my my + C1)(vx + vy + C2)),
+ *   C1 = 6.5025, C2 = 58.5225; sums[frame] int64 receives the sum of rint(s 2^32) (half to even) over valid pixels and channels.
+ * metric_depth: depth z and lidar y (frames, H, W) fp32 metres.  A pixel counts iff min_depth < y < max_depth and z is a number; z is
+ *   taken into [0, 256]; e = |z - y|, r = e / y, t = max(z / y, y / z) in fp64.  sums[frame][8] int64 receive n, sum rint(e 2^20),
+ *   sum rint(e e 2^20), sum rint(r 2^20), the counts of t < 1.25, 1.5625, 1.953125, and one spare that stays zero.
+ *   2^-6 <= min_depth < max_depth <= 256.
+ * metric_confusion: pred and gt (frames, H, W) int64; confusion[frame][gt][pred] int64 over classes <= 32; a pixel whose gt is outside
+ *   [0, classes) is ignored; one whose pred is outside is counted in bad[frame] and in no cell. */
+int mudg_metric_sse(const uint8_t* a_u8, const uint8_t* b_u8, int frames, int H, int W, uint64_t* sse, void* stream);
+int mudg_metric_ssim(const uint8_t* a_u8, const uint8_t* b_u8, int frames, int H, int W, int64_t* sums, void* stream);
+int mudg_metric_depth(const float* depth, const float* lidar, int frames, int H, int W, double min_depth, double max_depth,
+                      int64_t* sums, void* stream);
+int mudg_metric_confusion(const int64_t* pred, const int64_t* gt, int frames, int H, int W, int classes, int64_t* confusion,
+                          int64_t* bad, void* stream);
+
 /* ------------------------------------------------------------------ training step
  * Reference: lvdm/models/ddpm3d.py:741-802 (p_losses), :1267-1300 (configure_optimizers -> torch.optim.AdamW),
  * main/utils_train.py:126-137 (data-parallel strategy).  The contractions of the backward pass (dX = dY W, dW = dY^T X,

@@ -159,6 +159,10 @@ SIGNATURES = {
     "mudg_depth_finish": (_I, [_P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),
     "mudg_colormap_spectral": (_I, [_P, _L, _D, _D, _I, _P, _P, _P]),
     "mudg_depth_unproject": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _D, _D, _P, _P, _P]),
+    "mudg_metric_sse": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "mudg_metric_ssim": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "mudg_metric_depth": (_I, [_P, _P, _I, _I, _I, _D, _D, _P, _P]),
+    "mudg_metric_confusion": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "mudg_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_float), _P, _P]),
     "mudg_gaussian_sample": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "mudg_posterior_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _F, _P]),

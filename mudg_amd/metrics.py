@@ -1,0 +1,87 @@
+"""Scores of generated views against the truths that are already on the GPU: PSNR and SSIM for colour, depth errors against the rendered
+LiDAR depth, class IoU for the semantic stream.
+
+The reference has no scoring code (its eval_tools.py writes files, its validation_step logs the loss); its paper reports these
+numbers.  The rules here are this project's own and DESIGN.md §15 states them: every kernel of csrc/metrics.hip reduces a frame to a
+few integers that do not depend on the order of execution, and the scores are formed from those integers in float64 on the device.
+Results are small device tensors, nothing synchronises, and there is no CPU fallback: tensors that are not on the GPU are an error.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import hip, ops
+from .depth import _on_gpu
+
+MIN_DEPTH, MAX_DEPTH = 0.1, 80.0          # the range of LiDAR depths that depth errors are taken over
+CLASSES = 19                              # ops.semantic_nearest's classes
+_D = torch.float64
+
+
+def _frames(name, a, b):
+    a = _on_gpu(name, "the first frame stack", a, torch.uint8)
+    if a.dim() != 4 or a.shape[3] != 3:
+        raise hip.MudgError(f"{name}: expected (F, H, W, 3) frames, got {tuple(a.shape)}")
+    return a, _on_gpu(name, "the second frame stack", b, torch.uint8, a.shape)
+
+
+def psnr_ssim(a_u8, b_u8):
+    """Two (F, H, W, 3) uint8 frame stacks (ops.frames_to_uint8's, window_outputs' "color"), H, W >= 11.  Returns {"psnr": (F,) float64 =
+    10 log10(255^2 3 H W / sse), inf where the frames are equal; "ssim": (F,) float64, the mean over the valid region and the channels;
+    "sse", "ssim_sum": (F,) int64, the integers both come from}."""
+    a, b = _frames("psnr_ssim", a_u8, b_u8)
+    f, h, w = a.shape[:3]
+    if h < 11 or w < 11:
+        raise hip.MudgError(f"psnr_ssim: {h} x {w} frames, SSIM's 11 x 11 window needs at least 11 x 11")
+    sse, ssim_sum = ops.metric_sse(a, b), ops.metric_ssim(a, b)
+    const = lambda v: torch.full((), float(v), dtype=_D, device=a.device)    # a device tensor: dividing by a Python number multiplies by its reciprocal
+    psnr = 10.0 * torch.log10(const(255.0 ** 2 * 3 * h * w) / sse.to(_D))
+    ssim = ssim_sum.to(_D) / const(2.0 ** 32 * (3 * (h - 10) * (w - 10)))
+    return {"psnr": psnr, "ssim": ssim, "sse": sse, "ssim_sum": ssim_sum}
+
+
+def depth_errors(depth, lidar_depth, *, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH):
+    """depth: (F, H, W) fp32 metres (metric_depth's, window_outputs' "depth"); lidar_depth: (F, H, W) fp32 metres, 0 where no return
+    landed.  Over the pixels with min_depth < lidar < max_depth whose depth is a number, per frame in float64: {"n" (int64), "mae",
+    "rmse", "abs_rel", "d1", "d2", "d3" (the shares with max(z / y, y / z) < 1.25, 1.25^2, 1.25^3), "sums": (F, 8) int64}; a frame without
+    such a pixel scores nan."""
+    depth = _on_gpu("depth_errors", "the depth", depth, torch.float32)
+    if depth.dim() != 3:
+        raise hip.MudgError(f"depth_errors: expected (F, H, W) depths, got {tuple(depth.shape)}")
+    lidar = _on_gpu("depth_errors", "the LiDAR depth", lidar_depth, torch.float32, depth.shape)
+    sums = ops.metric_depth(depth, lidar, min_depth=min_depth, max_depth=max_depth)
+    s = sums.to(_D)
+    n = s[:, 0]                                                              # 0 / 0 = nan: a frame with nothing counted
+    return {"n": sums[:, 0], "mae": s[:, 1] / (2.0 ** 20 * n), "rmse": torch.sqrt(s[:, 2] / (2.0 ** 20 * n)), "abs_rel": s[:, 3] / (2.0 ** 20 * n),
+            "d1": s[:, 4] / n, "d2": s[:, 5] / n, "d3": s[:, 6] / n, "sums": sums}
+
+
+def segmentation_scores(pred_labels, gt_labels, *, classes=CLASSES):
+    """Two (F, H, W) int64 label maps in ops.semantic_nearest's format.  Returns {"confusion": (F, classes, classes) int64, [gt][pred];
+    "iou": (F, classes) float64, nan for a class in neither map; "miou": (F,) the mean over the defined classes; "pixel_acc": (F,);
+    "bad": (F,) int64, predictions outside [0, classes), which are in no cell}.  Ground truth outside [0, classes) (255, -1) is ignored."""
+    pred = _on_gpu("segmentation_scores", "the predicted labels", pred_labels, torch.int64)
+    if pred.dim() != 3:
+        raise hip.MudgError(f"segmentation_scores: expected (F, H, W) labels, got {tuple(pred.shape)}")
+    gt = _on_gpu("segmentation_scores", "the ground-truth labels", gt_labels, torch.int64, pred.shape)
+    confusion, bad = ops.metric_confusion(pred, gt, classes)
+    c = confusion.to(_D)
+    diag = torch.diagonal(c, dim1=1, dim2=2)
+    iou = diag / (c.sum(2) + c.sum(1) - diag)                                # 0 / 0 = nan: the class is in neither map
+    defined = ~torch.isnan(iou)
+    miou = torch.where(defined, iou, torch.zeros_like(iou)).sum(1) / defined.sum(1).to(_D)
+    return {"confusion": confusion, "iou": iou, "miou": miou, "pixel_acc": diag.sum(1) / (c.sum((1, 2)) + bad.to(_D)), "bad": bad}
+
+
+def score_window(outputs, *, color=None, lidar_depth=None, labels=None, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH, classes=CLASSES):
+    """outputs: the dict virtual_render.virtual_pose_render.window_outputs returns; color: (T, H, W, 3) uint8, the camera frames;
+    lidar_depth: (T, H, W) fp32 metres at the window's pose; labels: (T, H, W) int64.  Returns the union of psnr_ssim, depth_errors and
+    segmentation_scores for the truths that were given, keyed "color_*", "depth_*" and "semantic_*"; an absent truth adds no key."""
+    scores = {}
+    if color is not None:
+        scores.update({"color_" + k: v for k, v in psnr_ssim(outputs["color"], color).items()})
+    if lidar_depth is not None:
+        scores.update({"depth_" + k: v for k, v in depth_errors(outputs["depth"], lidar_depth, min_depth=min_depth, max_depth=max_depth).items()})
+    if labels is not None:
+        scores.update({"semantic_" + k: v for k, v in segmentation_scores(outputs["semantic_labels"], labels, classes=classes).items()})
+    return scores

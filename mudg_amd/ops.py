@@ -885,3 +885,67 @@ def depth_unproject(depth, rgb, table, labels=None, *, sky_label=10, min_depth=0
     hip.check(hip.lib().mudg_depth_unproject(depth.data_ptr(), rgb.data_ptr(), _ptr(labels), int(sky_label), table.data_ptr(), f, h, w,
                                              float(min_depth), float(max_depth), points.data_ptr(), valid.data_ptr(), _stream()), "mudg_depth_unproject")
     return points, valid
+
+
+# ------------------------------------------------------------------------------------------------ scores of generated views
+SSIM_WINDOW = (67, 498, 2359, 7167, 13960, 17434, 13960, 7167, 2359, 498, 67)     # the taps sum to 2^16
+SSIM_TILE = 32                   # outputs per side of one workgroup of mudg_metric_ssim
+
+
+def _metric_pair(name, a, b):
+    f, h, w = _depth_frames(name, a)
+    _splat_tensor(f"{name}: the second stack", b, torch.uint8, (f, h, w, 3))
+    return f, h, w
+
+
+def metric_sse(a, b):
+    """Two (f, h, w, 3) uint8 frame stacks -> (f,) int64, the sum of (a - b)^2 over all pixels and channels of every frame."""
+    f, h, w = _metric_pair("metric_sse", a, b)
+    sse = torch.zeros((f,), dtype=torch.int64, device=a.device)
+    hip.check(hip.lib().mudg_metric_sse(a.data_ptr(), b.data_ptr(), f, h, w, sse.data_ptr(), _stream()), "mudg_metric_sse")
+    return sse
+
+
+def metric_ssim(a, b):
+    """Two (f, h, w, 3) uint8 frame stacks, h, w >= 11 -> (f,) int64, the sum over the valid region (h - 10) x (w - 10) and the three
+    channels of rint(SSIM 2^32) per pixel (integer window, exact moments, fp64 in a stated order)."""
+    f, h, w = _metric_pair("metric_ssim", a, b)
+    if h < len(SSIM_WINDOW) or w < len(SSIM_WINDOW):
+        raise hip.MudgError(f"metric_ssim: {h} x {w} frames, the 11 x 11 window needs at least 11 x 11")
+    sums = torch.zeros((f,), dtype=torch.int64, device=a.device)
+    hip.check(hip.lib().mudg_metric_ssim(a.data_ptr(), b.data_ptr(), f, h, w, sums.data_ptr(), _stream()), "mudg_metric_ssim")
+    return sums
+
+
+def metric_depth(depth, lidar, *, min_depth=0.1, max_depth=80.0):
+    """depth and lidar (f, h, w) fp32 metres -> (f, 8) int64: n, sum rint(e 2^20), sum rint(e e 2^20), sum rint(r 2^20), the counts of
+    t < 1.25, 1.25^2, 1.25^3 and a zero, over the pixels with min_depth < lidar < max_depth whose depth is a number."""
+    _splat_tensor("metric_depth: depth", depth, torch.float32)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise hip.MudgError(f"metric_depth: expected (frames, h, w) depths, got {tuple(depth.shape)}")
+    f, h, w = depth.shape
+    _splat_tensor("metric_depth: lidar", lidar, torch.float32, (f, h, w))
+    if not (2.0 ** -6 <= float(min_depth) < float(max_depth) <= 256.0):
+        raise hip.MudgError(f"metric_depth: depth range ({min_depth}, {max_depth}), expected 2^-6 <= min_depth < max_depth <= 256")
+    sums = torch.zeros((f, 8), dtype=torch.int64, device=depth.device)
+    hip.check(hip.lib().mudg_metric_depth(depth.data_ptr(), lidar.data_ptr(), f, h, w, float(min_depth), float(max_depth), sums.data_ptr(),
+                                          _stream()), "mudg_metric_depth")
+    return sums
+
+
+def metric_confusion(pred, gt, classes=19):
+    """pred and gt (f, h, w) int64 label maps -> (confusion (f, classes, classes) int64 indexed [gt][pred], bad (f,) int64).  A pixel
+    whose gt is outside [0, classes) is ignored; one whose pred is outside is counted in bad and in no cell."""
+    _splat_tensor("metric_confusion: pred", pred, torch.int64)
+    if pred.dim() != 3 or pred.numel() == 0:
+        raise hip.MudgError(f"metric_confusion: expected (frames, h, w) labels, got {tuple(pred.shape)}")
+    f, h, w = pred.shape
+    _splat_tensor("metric_confusion: gt", gt, torch.int64, (f, h, w))
+    classes = int(classes)
+    if not 1 <= classes <= 32:
+        raise hip.MudgError(f"metric_confusion: {classes} classes, expected 1 .. 32")
+    confusion = torch.zeros((f, classes, classes), dtype=torch.int64, device=pred.device)
+    bad = torch.zeros((f,), dtype=torch.int64, device=pred.device)
+    hip.check(hip.lib().mudg_metric_confusion(pred.data_ptr(), gt.data_ptr(), f, h, w, classes, confusion.data_ptr(), bad.data_ptr(), _stream()),
+              "mudg_metric_confusion")
+    return confusion, bad

@@ -9,11 +9,13 @@ export are host I/O outside the path.  The depth colour map is not: for "Spectra
   colormap            eval_tools.py:137-261                  "Spectral" / "Spectral_r", the reference's method_custom; same signature
   visualize_depth     eval_tools.py:264-306                  same signature; (H, W, 3) uint8 arrays where the reference returns PIL images
   aligned_depth       data_process/depthlab_tools.py:67-87, 114-136   the depth stream in metres: fitted to the LiDAR depth, sky at 100 m
+  score_window        (none: the reference only saves files)          PSNR / SSIM, depth errors and class IoU of a window
 """
 import numpy as np
 import torch
 
 from mudg_amd import depth as _depth
+from mudg_amd import metrics as _metrics
 from mudg_amd import ops
 
 _COLOR_MAPS = ("Spectral", "Spectral_r")
@@ -80,3 +82,9 @@ def aligned_depth(grid_frames, lidar_depth, labels=None):
     metres: align_depth's least-squares line per frame, then process_sky's 100 m on class 10 and its clip to [0, 100]
     (mudg_amd.depth.metric_depth, which also returns the line and whether a frame could be fitted)."""
     return _depth.metric_depth(grid_frames, lidar_depth, labels)["depth"]
+
+
+def score_window(outputs, *, color=None, lidar_depth=None, labels=None, **options):
+    """window_outputs' dict and whichever ground truths there are -> "color_psnr", "color_ssim", "depth_mae", ..., "semantic_miou", ... as
+    small tensors on the GPU (mudg_amd.metrics.score_window)."""
+    return _metrics.score_window(outputs, color=color, lidar_depth=lidar_depth, labels=labels, **options)
