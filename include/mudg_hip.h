@@ -185,6 +185,17 @@ int mudg_quantize_mxfp8(const void* X, int ldx, int64_t rows, int cols, void* Y8
  * QKV rows are ((b*T + t)*HW + p); q at columns [h*64..], k at C + h*64, v at 2C + h*64. */
 int mudg_temporal_attention(const void* QKV, void* O, int B, int T, int HW, int heads,
                             int ldqkv, int ldo, float scale, void* stream);
+/* The same attention with its q | k | v projection in front, in one kernel (16-bit builds; attention.py:53-55 to_q / to_k / to_v,
+ * bias-free): O = attention over T of (X Wh^T), where the projected rows are rounded to the operand type exactly as mudg_gemm
+ * stores them but never leave the CU.  X: operand rows [B T HW][ldx], C = 64 heads channels (the LayerNorm's output); Wh: the
+ * HEAD-PACKED weight [3 C][ldw], row 192 h + 64 j + d = row 64 h + d of to_q (j = 0), to_k (1), to_v (2); O: operand rows
+ * [B T HW][ldo].  Needs what the query below checks, a dry call that reads nothing: T = 16, HW % 8 == 0, head width 64
+ * (C == 64 heads), row strides that are multiples of 8 and at least C, a 16-bit build (0 in the split-operand builds).  Anything
+ * else takes mudg_gemm and mudg_temporal_attention.  Booked in MUDG_FAM_GEMM with flops = 2 M 3C C + 4 items T T 64 and the
+ * algorithmic bytes (X, Wh and O once). */
+int mudg_temporal_self_attention_ok(int T, int HW, int heads, int C, int64_t ldx, int64_t ldw, int64_t ldo);
+int mudg_temporal_self_attention(const void* X, const void* Wh, void* O, int B, int T, int HW, int heads, int C, int64_t ldx,
+                                 int64_t ldw, int64_t ldo, float scale, void* stream);
 
 /* ------------------------------------------------------------------ normalisation
  * GroupNorm(32 groups) on channels-last data with optional fused SiLU / swish

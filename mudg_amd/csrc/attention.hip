@@ -624,6 +624,58 @@ typedef __attribute__((ext_vector_type(4))) short mf4;
 #define MFMA_16x16x16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0)
 #endif
 
+// One (pixel, head) item of the temporal attention on per-wave LDS tiles in the layouts described above (q / k chunk-swizzled, v
+// unit-swizzled): scores, fp32 softmax over the 16 keys, P as two 16-bit pieces, P V.  Lane (c, g) leaves with ov[4m + i] = dim
+// 32 (m / 2) + 8g + 4 (m % 2) + i of query c.  Shared by tattn_mfma_kernel (tiles fetched from a q | k | v matrix) and
+// tsattn_fused_kernel (tiles written by its own projection): one copy of the arithmetic, bit-equal results.
+__device__ __forceinline__ int tattn_fz(int rg) { return (rg & 1) | ((rg >> 1) << 3); }      // V's swizzle of row group rg: bits 0 and 3 of the 8-byte unit index
+__device__ __forceinline__ void tattn_item_mfma(const char* qs, const char* ks, const char* vs, const int c, const int g, const int T,
+                                                const float scale, float (&ov)[16]) {
+    f32x4 st = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {                // dims 8g + 32s .. + 7 = chunk g + 4s of row c
+        const int off = c * 128 + (((g + 4 * s) ^ (c & 7)) << 4);
+        st = MFMA_16x16x32(as_h16x8(ld16(ks + off)), as_h16x8(ld16(qs + off)), st);
+    }
+
+    // softmax over tk = 4g + i: in-lane over i, then across the four lane groups
+    float sc[4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { sc[i] = (4 * g + i < T) ? st[i] * scale : -INFINITY; mx = fmaxf(mx, sc[i]); }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    // the probabilities enter the second contraction as TWO 16-bit pieces (p = p0 + p1, four more MFMAs on a kernel that waits
+    // for memory): the fp32-probability arithmetic of the VALU kernel it replaces, not one more 16-bit rounding per layer
+    float sum = 0.f;
+    union { mf4 m; h16 e[4]; } pt, pr;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float pv = __expf(sc[i] - mx);
+        sum += pv;
+        pt.e[i] = (h16)pv;
+        pr.e[i] = (h16)(pv - (float)pt.e[i]);
+    }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv = 1.f / sum;
+
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        union { mf4 m4; unsigned short e[4]; } vt;
+        // row c of block m stands for dim 32 (m / 2) + 8 (c / 4) + 4 (m % 2) + c % 4 = unit 8 (m / 2) + 2 (c / 4) + m % 2, element c % 4
+        const int u = (8 * (m >> 1) + 2 * (c >> 2) + (m & 1)) ^ tattn_fz(g);    // row 4g + j has r / 4 = g
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            vt.e[j] = *reinterpret_cast<const unsigned short*>(vs + (4 * g + j) * 128 + (u << 3) + 2 * (c & 3));
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        acc = MFMA_16x16x16(vt.m4, pr.m, acc);
+        acc = MFMA_16x16x16(vt.m4, pt.m, acc);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ov[4 * m + i] = acc[i] * inv;
+    }
+}
+
 __global__ __launch_bounds__(256) void tattn_mfma_kernel(const h16* __restrict__ QKV, h16* __restrict__ O,
                                                           int B, int T, int HW, int heads, int ldqkv, int ldo,
                                                           float scale, int total) {
@@ -637,7 +689,6 @@ __global__ __launch_bounds__(256) void tattn_mfma_kernel(const h16* __restrict__
     char* qs = reinterpret_cast<char*>(&Ts[wave][0][0]);
     char* ks = reinterpret_cast<char*>(&Ts[wave][1][0]);
     char* vs = reinterpret_cast<char*>(&Ts[wave][2][0]);
-    auto fz = [](int rg) { return (rg & 1) | ((rg >> 1) << 3); };     // V's swizzle of row group rg: bits 0 and 3 of the 8-byte unit index
 
     u32x4 qn[2], kn[2], vn[2];                       // the item being fetched: [row half]
     int64_t pixn = 0; int hn = 0; bool itemn = false;
@@ -670,7 +721,7 @@ __global__ __launch_bounds__(256) void tattn_mfma_kernel(const h16* __restrict__
             const int r = lr + 8 * s;
             st16(qs + r * 128 + ((lj ^ (r & 7)) << 4), qn[s]);
             st16(ks + r * 128 + ((lj ^ (r & 7)) << 4), kn[s]);
-            const int z = fz(r >> 2);
+            const int z = tattn_fz(r >> 2);
             u32x2 lo = {vn[s][0], vn[s][1]}, hi = {vn[s][2], vn[s][3]};
             *reinterpret_cast<u32x2*>(vs + r * 128 + (((2 * lj) ^ z) << 3)) = lo;
             *reinterpret_cast<u32x2*>(vs + r * 128 + (((2 * lj + 1) ^ z) << 3)) = hi;
@@ -678,50 +729,8 @@ __global__ __launch_bounds__(256) void tattn_mfma_kernel(const h16* __restrict__
         __builtin_amdgcn_wave_barrier();
         if (it + 1 < TATTN_ITEMS) fetch(w0 + it + 1);
 
-        f32x4 st = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {                // dims 8g + 32s .. + 7 = chunk g + 4s of row c
-            const int off = c * 128 + (((g + 4 * s) ^ (c & 7)) << 4);
-            st = MFMA_16x16x32(as_h16x8(ld16(ks + off)), as_h16x8(ld16(qs + off)), st);
-        }
-
-        // softmax over tk = 4g + i: in-lane over i, then across the four lane groups
-        float sc[4];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { sc[i] = (4 * g + i < T) ? st[i] * scale : -INFINITY; mx = fmaxf(mx, sc[i]); }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // the probabilities enter the second contraction as TWO 16-bit pieces (p = p0 + p1, four more MFMAs on a kernel that waits
-        // for memory): the fp32-probability arithmetic of the VALU kernel it replaces, not one more 16-bit rounding per layer
-        float sum = 0.f;
-        union { mf4 m; h16 e[4]; } pt, pr;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float pv = __expf(sc[i] - mx);
-            sum += pv;
-            pt.e[i] = (h16)pv;
-            pr.e[i] = (h16)(pv - (float)pt.e[i]);
-        }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.f / sum;
-
         float ov[16];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            union { mf4 m4; unsigned short e[4]; } vt;
-            // row c of block m stands for dim 32 (m / 2) + 8 (c / 4) + 4 (m % 2) + c % 4 = unit 8 (m / 2) + 2 (c / 4) + m % 2, element c % 4
-            const int u = (8 * (m >> 1) + 2 * (c >> 2) + (m & 1)) ^ fz(g);    // row 4g + j has r / 4 = g
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                vt.e[j] = *reinterpret_cast<const unsigned short*>(vs + (4 * g + j) * 128 + (u << 3) + 2 * (c & 3));
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = MFMA_16x16x16(vt.m4, pr.m, acc);
-            acc = MFMA_16x16x16(vt.m4, pt.m, acc);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ov[4 * m + i] = acc[i] * inv;
-        }
+        tattn_item_mfma(qs, ks, vs, c, g, T, scale, ov);
         if (c < T) {
             // ov[4m + i] is dim 32 (m / 2) + 8g + 4 (m % 2) + i: blocks 0, 1 are dims 8g .. 8g + 7, blocks 2, 3 the same + 32 — a store
             // instruction covers 64 contiguous bytes per query row
@@ -733,6 +742,123 @@ __global__ __launch_bounds__(256) void tattn_mfma_kernel(const h16* __restrict__
                 for (int e = 0; e < 8; ++e) t[e] = (h16)ov[half * 8 + e];
                 st16(dst + half * 32, as_u32x4(t));
             }
+        }
+    }
+}
+
+// The q | k | v projection and the attention above in one kernel (mudg_temporal_self_attention): the projected tile never leaves the
+// CU, so the [M][3C] matrix — written once and read once, 1.13 GB per call at the UNet's level 0 — is neither stored nor fetched.
+// A workgroup owns 8 pixels x 16 frames of one clip (128 rows: tile row 16 p + t is row (b T + t) HW + px0 + p, the tiling of the
+// slab-major temporal convs) and ONE head: it contracts the rows with the 192 weight rows [q_h | k_h | v_h] of the head-packed
+// weight over K = C.  Heads are the fast index of the XCD-aware work numbering, so the heads of a row tile run next to each other
+// on one XCD and the tile's x rows come from HBM once and from that XCD's L2 afterwards.
+//   K loop    64 channels per stage: 128 x rows + 192 weight rows of 128 B, chunk-swizzled like the q / k tiles above (fragment
+//             reads are conflict-free), two stages (80 KB: two workgroups per CU); the next stage is fetched into registers before
+//             the MFMAs of the current one and stored after them, one barrier per stage.
+//   waves     wave w owns tile rows 32 w .. 32 w + 31 = pixels 2w, 2w + 1, all 192 columns: 2 x 12 accumulators of
+//             v_mfma_f32_16x16x32 with the WEIGHT rows as A and the x rows as B, so lane (c, g) holds columns 16 nb + 4g .. + 3 of
+//             frame c — four consecutive head dims of one row: an 8-byte unit of the tiles tattn_item_mfma reads.
+//   epilogue  after the last barrier the stages are dead: each wave rounds its accumulators to the operand type (the rounding the
+//             GEMM's store applies) and writes its two items' q, k, v tiles into its own 12 KB of them — no workgroup barrier, the
+//             LDS operations of a wave execute in order — then runs tattn_item_mfma per item and stores 128 x 64 results.
+constexpr int TSA_KT = 64;                                   // channels per stage
+constexpr int TSA_ROWS = 128, TSA_COLS = 192;                // tile: rows of x, weight rows of one head
+constexpr int TSA_STAGE = (TSA_ROWS + TSA_COLS) * TSA_KT * 2;     // bytes
+constexpr int TSA_LDS = 2 * TSA_STAGE;                       // 81920
+static_assert(TSA_LDS >= 4 * 2 * 3 * 2048, "the dead stages must hold 4 waves x 2 items x 3 tiles (q, k, v) x 2 KB");
+
+__global__ __launch_bounds__(256, 2) void tsattn_fused_kernel(const h16* __restrict__ X, const h16* __restrict__ W, h16* __restrict__ O,
+                                                               const int HW, const int heads, const int C, const int64_t ldx,
+                                                               const int64_t ldw, const int64_t ldo, const float scale, const int total) {
+    extern __shared__ __attribute__((aligned(16))) char tsa_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;          // MFMA coordinates
+    const int item = xcd_work_item(total);           // tile * heads + head
+    const int tile = item / heads, h = item - tile * heads;
+    const int tpc = HW >> 3;                         // tiles per clip
+    const int b = tile / tpc, px0 = (tile - b * tpc) << 3;
+    const int64_t row0 = (int64_t)b * 16 * HW + px0; // tile row 16 p + t is row row0 + t HW + p
+
+    // fetch coordinates: staged row lrow + 32 i (x rows 0 .. 127, then the head's weight rows 0 .. 191), 16-byte chunk lch
+    const int lrow = tid >> 3, lch = tid & 7;
+    const h16* src[10];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = lrow + 32 * i;
+        src[i] = X + (row0 + (int64_t)(r & 15) * HW + (r >> 4)) * ldx + lch * 8;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) src[4 + i] = W + (int64_t)(h * TSA_COLS + lrow + 32 * i) * ldw + lch * 8;
+    const int soff = lrow * 128 + ((lch ^ (lrow & 7)) << 4);     // + 4096 i: (lrow + 32 i) & 7 == lrow & 7
+
+    u32x4 nx[10];
+    auto fetch = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < 10; ++i) nx[i] = ld16(src[i] + kt * TSA_KT);
+    };
+    auto stage = [&](char* st) {
+#pragma unroll
+        for (int i = 0; i < 10; ++i) st16(st + soff + 4096 * i, nx[i]);
+    };
+
+    f32x4 acc[2][12];
+#pragma unroll
+    for (int pi = 0; pi < 2; ++pi)
+#pragma unroll
+        for (int nb = 0; nb < 12; ++nb) acc[pi][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = C / TSA_KT;
+    fetch(0);
+    stage(tsa_smem);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const char* cur = tsa_smem + (kt & 1) * TSA_STAGE;
+        if (kt + 1 < nk) fetch(kt + 1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {                // channels 8g + 32s .. + 7 of the stage = chunk g + 4s
+            const int foff = c * 128 + (((g + 4 * s) ^ (c & 7)) << 4);
+            const h16x8 xf0 = as_h16x8(ld16(cur + (32 * wave) * 128 + foff));
+            const h16x8 xf1 = as_h16x8(ld16(cur + (32 * wave + 16) * 128 + foff));
+#pragma unroll
+            for (int nb = 0; nb < 12; ++nb) {
+                const h16x8 wf = as_h16x8(ld16(cur + (TSA_ROWS + 16 * nb) * 128 + foff));
+                acc[0][nb] = MFMA_16x16x32(wf, xf0, acc[0][nb]);
+                acc[1][nb] = MFMA_16x16x32(wf, xf1, acc[1][nb]);
+            }
+        }
+        if (kt + 1 < nk) stage(tsa_smem + ((kt + 1) & 1) * TSA_STAGE);   // the other stage: everyone left it before the last barrier
+        __syncthreads();
+    }
+
+    // every wave is past its last fragment read: the stages become the per-wave q / k / v tiles
+    char* mine = tsa_smem + wave * (2 * 3 * 2048);
+#pragma unroll
+    for (int pi = 0; pi < 2; ++pi) {
+        char* qs = mine + pi * (3 * 2048);
+#pragma unroll
+        for (int nb = 0; nb < 12; ++nb) {
+            Pack8 t;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t.h[i] = (h16)acc[pi][nb][i];
+            const int u = 4 * (nb & 3) + g;          // 8-byte unit of row c: head dims 4u .. 4u + 3
+            const int off = (nb >> 2) == 2 ? c * 128 + ((u ^ tattn_fz(c >> 2)) << 3)
+                                           : c * 128 + (((u >> 1) ^ (c & 7)) << 4) + ((u & 1) << 3);
+            *reinterpret_cast<u32x2*>(qs + (nb >> 2) * 2048 + off) = t.u;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int pi = 0; pi < 2; ++pi) {
+        const char* qs = mine + pi * (3 * 2048);
+        float ov[16];
+        tattn_item_mfma(qs, qs + 2048, qs + 4096, c, g, 16, scale, ov);
+        h16* dst = O + (row0 + (int64_t)c * HW + (2 * wave + pi)) * ldo + h * 64 + g * 8;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            h16x8 t;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) t[e] = (h16)ov[half * 8 + e];
+            st16(dst + half * 32, as_u32x4(t));
         }
     }
 }
@@ -1374,4 +1500,43 @@ extern "C" int mudg_temporal_attention(const void* QKV, void* O, int B, int T, i
     const int rc = mudg_check_launch("mudg_temporal_attention");
     mudg_prof_end(slot, s, 4.0 * total * (double)T * T * 64.0, (double)total * T * 64.0 * 2.0 * 4.0);
     return rc;
+}
+
+// Whether mudg_temporal_self_attention runs this problem (a dry query: nothing is read).  The row tiling wants whole 8-pixel x
+// 16-frame tiles, the stage loader whole 64-channel steps and 16-byte row pieces, the item arithmetic head width 64.
+extern "C" int mudg_temporal_self_attention_ok(int T, int HW, int heads, int C, int64_t ldx, int64_t ldw, int64_t ldo) {
+#if MUDG_PLANES == 1
+    return T == 16 && HW > 0 && HW % 8 == 0 && heads > 0 && C == heads * 64 && ldx % 8 == 0 && ldw % 8 == 0 && ldo % 8 == 0 && ldx >= C &&
+           ldw >= C && ldo >= C;
+#else
+    (void)T; (void)HW; (void)heads; (void)C; (void)ldx; (void)ldw; (void)ldo;
+    return 0;
+#endif
+}
+
+extern "C" int mudg_temporal_self_attention(const void* X, const void* Wh, void* O, int B, int T, int HW, int heads, int C, int64_t ldx,
+                                            int64_t ldw, int64_t ldo, float scale, void* stream) {
+#if MUDG_PLANES == 1
+    MUDG_REQUIRE(X && Wh && O, "mudg_temporal_self_attention: null pointer");
+    MUDG_REQUIRE(B > 0, "mudg_temporal_self_attention: empty problem");
+    MUDG_REQUIRE(aligned16(X) && aligned16(Wh) && aligned16(O), "mudg_temporal_self_attention: alignment");
+    if (!mudg_temporal_self_attention_ok(T, HW, heads, C, ldx, ldw, ldo))
+        MUDG_FAIL(MUDG_EUNSUPPORTED, "mudg_temporal_self_attention: T=%d HW=%d heads=%d C=%d outside the fused kernel (T = 16, HW %% 8 == 0, "
+                  "C = 64 heads, dense 16-byte rows): project with mudg_gemm and call mudg_temporal_attention", T, HW, heads, C);
+    const int64_t total = (int64_t)B * (HW / 8) * heads;
+    MUDG_REQUIRE(total < (1ll << 31), "mudg_temporal_self_attention: grid too large");
+    const int rc0 = mudg_lds_opt_in<tsattn_fused_kernel>(TSA_LDS, "mudg_temporal_self_attention");
+    if (rc0 != MUDG_OK) return rc0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int slot = mudg_prof_begin(MUDG_FAM_GEMM, s);
+    hipLaunchKernelGGL(tsattn_fused_kernel, dim3((unsigned)total), dim3(256), TSA_LDS, s, (const h16*)X, (const h16*)Wh, (h16*)O, HW, heads, C,
+                       ldx, ldw, ldo, scale, (int)total);
+    const int rc = mudg_check_launch("mudg_temporal_self_attention");
+    const double M = (double)B * T * HW;
+    mudg_prof_end(slot, s, 2.0 * M * 3.0 * C * C + 4.0 * (double)B * HW * heads * T * T * 64.0, (2.0 * M * C + 3.0 * C * C) * 2.0);
+    return rc;
+#else
+    (void)X; (void)Wh; (void)O; (void)B; (void)T; (void)HW; (void)heads; (void)C; (void)ldx; (void)ldw; (void)ldo; (void)scale; (void)stream;
+    MUDG_FAIL(MUDG_EUNSUPPORTED, "mudg_temporal_self_attention: the fused kernel belongs to the 16-bit operand builds");
+#endif
 }

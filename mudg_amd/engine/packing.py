@@ -83,6 +83,21 @@ def linear_cat(owner, name, mods):
     return cached(owner, name, ws, lambda: operand(torch.cat([w.detach().float() for w in ws], 0)))
 
 
+def qkv_by_head(owner, to_q, to_k, to_v, heads):
+    """The rows of linear_cat(q, k, v) reordered head by head — [q_h | k_h | v_h], 192 rows per head — for the kernel that
+    projects and attends one head per workgroup (ops.temporal_self_attention).  Same values, same one cast."""
+    ws = (to_q.weight, to_k.weight, to_v.weight)
+    for w in ws:
+        _need_cuda(w, "qkv")
+    c = to_q.weight.shape[1]
+
+    def build():
+        t = torch.stack([w.detach().float().reshape(heads, 64, c) for w in ws], 1)      # heads, 3, 64, C
+        return operand(t.reshape(3 * heads * 64, c))
+
+    return cached(owner, f"qkv_by_head:{heads}", ws, build)
+
+
 def qk_prescaled(owner, to_q, to_k, scale):
     """[q | k] projection rows with the attention scale AND log2(e) folded into the q rows (in fp32, before the one cast
     to the operand type — no extra rounding): Q K^T then is the base-2 exponent of the softmax directly

@@ -30,6 +30,7 @@ from . import packing as pk
 import os as _os
 _LEAN_ATTENTION = _os.environ.get("MUDG_ATTN_LEAN", "1") != "0"       # A/B switch, read once
 _TCONV_SLAB = _os.environ.get("MUDG_TCONV_SLAB", "1") != "0"         # A/B switch: slab-major temporal convs (tiles of 8 pixels x 16 frames)
+_TSATTN_FUSED = _os.environ.get("MUDG_TSATTN_FUSED", "1") != "0"     # A/B switch: temporal self-attention projects q | k | v inside the attention kernel
 _FP8_ATTENTION = _os.environ.get("MUDG_ATTN_FP8", "0") == "1"         # opt-in: MX-fp8 scores in the long self-attention
 
 
@@ -216,12 +217,38 @@ def spatial_transformer(mod, x, h, w, ctx):
     return _linear(mod.proj_out, cur, residual=x, stream=True, stats=True, hw=hw)
 
 
+_TSATTN_MAX_C = 640
+
+
+def _tsattn_fused(t, hw, heads, c, x, out):
+    """Selection rule of the fused temporal self-attention: what the library's query accepts (16-bit build, T = 16, hw % 8 == 0, head
+    width 64), up to C = 640.  Measured per launch on one MI355X, fused against gemm + temporal_attention alternating, by
+    `tools/kernel_bench.py fused` (profiles/temporal_fused/ab_shapes.md), rows x C, us:
+      C = 320    81920 (MDM512): 75 against 119;  294912 (MDM1024): 253 against 476;  884736 (three clips): 750 against 1321
+      C = 512    40960: 89 against 112;  147456: 286 against 428;  442368: 846 against 1263   (the input-stage transformer)
+      C = 640    20480: 72 against 87;  73728: 209 against 296;  221184: 635 against 849
+      C = 1280   1280: 28 against 29;  4608: 59 against 67;  5120: 72 against 68;  13824: 159 against 168;  18432: 207 against 185;
+                 55296: 617 against 619
+    Every C <= 640 shape of the three configurations wins by 17 - 47 %, its slowest repeat still below the pair's fastest.  At
+    C = 1280 twenty heads re-read a row tile over a K loop that is already long: it loses or ties at the rows that carry the time and
+    wins 1 - 9 us at the smallest (two calls per step), so C = 1280 keeps the two launches.  The small UNet of the tests (C 64 - 256,
+    384 - 6144 rows: 10 against 19 us) is in the same table."""
+    return (_TSATTN_FUSED and c == heads * 64 and c <= _TSATTN_MAX_C
+            and ops.temporal_self_attention_ok(t, hw, heads, c, x.stride(0), c, out.stride(0)))
+
+
 def temporal_block(blk, hcur, hw, ctx, last):
     for attn, norm in ((blk.attn1, blk.norm1), (blk.attn2, blk.norm2)):     # both are self-attention over T
         c = hcur.shape[1]
-        qkv = ops.gemm(_ln(norm, hcur), pk.linear_cat(attn, "qkv", (attn.to_q, attn.to_k, attn.to_v)), frame_rows=hw)
+        n = _ln(norm, hcur)
         att = ops.empty_rows(hcur.shape[0], c, ops.H16(), hcur.device)
-        ops.temporal_attention(qkv, att, clips=ctx.B, t=ctx.T, hw=hw, heads=attn.heads, scale=attn.scale)
+        if _tsattn_fused(ctx.T, hw, attn.heads, c, n, att):
+            # q | k | v never reach memory: one launch projects a tile of 8 pixels x 16 frames per head and attends in LDS
+            ops.temporal_self_attention(n, pk.qkv_by_head(attn, attn.to_q, attn.to_k, attn.to_v, attn.heads), att, clips=ctx.B, t=ctx.T,
+                                        hw=hw, heads=attn.heads, scale=attn.scale)
+        else:
+            qkv = ops.gemm(n, pk.linear_cat(attn, "qkv", (attn.to_q, attn.to_k, attn.to_v)), frame_rows=hw)
+            ops.temporal_attention(qkv, att, clips=ctx.B, t=ctx.T, hw=hw, heads=attn.heads, scale=attn.scale)
         hcur = _linear(attn.to_out[0], att, residual=hcur, stream=True, hw=hw)
     return _feed_forward(blk.ff, _ln(blk.norm3, hcur), hcur, stream=not last, hw=hw)
 

@@ -126,6 +126,8 @@ SIGNATURES = {
     "mudg_attention": (_I, [C.POINTER(AttnDesc), _P]),
     "mudg_quantize_mxfp8": (_I, [_P, _I, _L, _I, _P, _I, _P, _I, _P]),
     "mudg_temporal_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "mudg_temporal_self_attention_ok": (_I, [_I, _I, _I, _I, _L, _L, _L]),
+    "mudg_temporal_self_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L, _F, _P]),
     "mudg_groupnorm_ws_floats": (_L, [_I, _I, _I]),
     "mudg_groupnorm": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
     "mudg_groupnorm_fused": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),

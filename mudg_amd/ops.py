@@ -338,6 +338,27 @@ def temporal_attention(qkv, out, *, clips, t, hw, heads, scale=0.125):
     return out
 
 
+def temporal_self_attention_ok(t, hw, heads, c, ldx=None, ldw=None, ldo=None):
+    """Whether mudg_temporal_self_attention runs this problem (a dry query; row strides default to dense rows)."""
+    return bool(hip.lib().mudg_temporal_self_attention_ok(t, hw, heads, c, c if ldx is None else ldx, c if ldw is None else ldw,
+                                                          c if ldo is None else ldo))
+
+
+def temporal_self_attention(x, wh, out, *, clips, t, hw, heads, scale=0.125):
+    """q | k | v projection of the normalised rows `x` and the attention over T in one launch: `wh` is the head-packed weight
+    (packing.qkv_by_head), `out` receives what gemm + temporal_attention would leave in it.  16-bit builds, T = 16, hw % 8 == 0."""
+    _rows(x); _rows(wh); _rows(out)
+    rows, c = x.shape
+    if rows != clips * t * hw or tuple(out.shape) != (rows, c) or tuple(wh.shape) != (3 * c, c):
+        raise hip.MudgError(f"temporal_self_attention: x {tuple(x.shape)}, wh {tuple(wh.shape)}, out {tuple(out.shape)} are not "
+                            f"[clips * t * hw = {clips * t * hw}][C], [3C][C], [clips * t * hw][C]")
+    _drop_stats(out)
+    hip.check(hip.lib().mudg_temporal_self_attention(x.data_ptr(), wh.data_ptr(), out.data_ptr(), clips, t, hw, heads, x.shape[1],
+                                                     x.stride(0), wh.stride(0), out.stride(0), scale, _stream()),
+              "mudg_temporal_self_attention")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ norms
 def _rows_any(t):
     if t.dim() != 2 or t.stride(1) != 1 or t.dtype not in (H16(), torch.float32, torch.float16) or not t.is_cuda:

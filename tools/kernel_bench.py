@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the kernels at the shapes the MDM1024 UNet issues (B = 1): TFLOP/s or GB/s per launch.
-Run on the GPU box:  python tools/kernel_bench.py [filter]"""
+Run on the GPU box:  python tools/kernel_bench.py [filter]
+`python tools/kernel_bench.py fused` is the table behind the rule of the fused temporal self-attention (fused_temporal below)."""
 import os
 import sys
 
@@ -39,8 +40,61 @@ def report(name, sec, flops=None, bytes_=None):
     print(msg, flush=True)
 
 
+def spread(fn, repeats=7, iters=10):
+    """(median, min, max) seconds per call over `repeats` timings of `iters` back-to-back calls."""
+    fn()
+    ts = sorted(timeit(fn, iters=iters, warm=1) for _ in range(repeats))
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+# (name, clips, (level, hw, C) ...) of the temporal transformers: the one behind the input convolution (`in`: C = 512 on half the
+# level-0 pixels, the shape a step profile shows) and those of the four levels.  Cond + uncond are stacked, so a step of B clips runs
+# 2 B clips.  The last is the small UNet of the tests (tests/golden/unet_a.pt), whose 6-pixel level the query refuses.
+def _mdm(h, w):
+    return (("in", h * w // 2, 512),) + tuple((lv, (h >> lv) * (w >> lv), c) for lv, c in enumerate((320, 640, 1280, 1280)))
+
+
+TEMPORAL_CONFIGS = [("MDM1024", 2, _mdm(72, 128)), ("MDM512", 2, _mdm(40, 64)), ("MDM1024 B=3", 6, _mdm(72, 128)),
+                    ("test UNet", 1, ((0, 384, 64), (1, 96, 128), (2, 24, 256), (3, 6, 256)))]
+
+
+def fused_temporal(T=16):
+    """The fused temporal self-attention against the two launches it replaces, per level of every configuration the rule in
+    engine/unet.py (_tsattn_fused) has to decide: the qkv GEMM alone, the temporal attention alone, the two alternating as a step
+    issues them (`pair`: the figure the rule compares; it is not the sum of the two columns before it, which time each kernel
+    back-to-back with itself), and the fused launch.  One markdown row per shape."""
+    print("| config | level | rows | C | gemm us | tattn us | pair us (min..max) | fused us (min..max) | fused TFLOP/s | fused / pair |")
+    print("|---|---:|---:|---:|---:|---:|---:|---:|---:|---:|")
+    for name, clips, levels in TEMPORAL_CONFIGS:
+        for level, hw, c in levels:
+            heads, M = c // 64, clips * T * hw
+            if not ops.temporal_self_attention_ok(T, hw, heads, c):
+                print(f"| {name} | {level} | {M} | {c} | refused by the query |", flush=True)
+                continue
+            x, w = rn(M, c), rn(3 * c, c)           # timing does not depend on the row order of w: no head packing here
+            out = torch.empty(M, c, device=dev, dtype=BF)
+            qkv = ops.gemm(x, w, frame_rows=hw)
+
+            def pair():
+                q = ops.gemm(x, w, frame_rows=hw)
+                ops.temporal_attention(q, out, clips=clips, t=T, hw=hw, heads=heads)
+
+            g = spread(lambda: ops.gemm(x, w, frame_rows=hw))
+            a = spread(lambda: ops.temporal_attention(qkv, out, clips=clips, t=T, hw=hw, heads=heads))
+            p = spread(pair)
+            f = spread(lambda: ops.temporal_self_attention(x, w, out, clips=clips, t=T, hw=hw, heads=heads))
+            flops = 2.0 * M * 3 * c * c + 4.0 * clips * hw * heads * T * T * 64
+            us = lambda s: f"{s[0] * 1e6:.1f} ({s[1] * 1e6:.1f}..{s[2] * 1e6:.1f})"
+            print(f"| {name} | {level} | {M} | {c} | {g[0] * 1e6:.1f} | {a[0] * 1e6:.1f} | {us(p)} | {us(f)} | {flops / f[0] / 1e12:.0f} | "
+                  f"{f[0] / p[0]:.3f} |", flush=True)
+            del x, w, out, qkv
+            torch.cuda.empty_cache()
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
+    if flt == "fused":
+        return fused_temporal()
     T = 16
     levels = [(72 * 128, 320), (36 * 64, 640), (18 * 32, 1280), (9 * 16, 1280)]
     if "gemm" in flt or not flt:

@@ -8,6 +8,7 @@ import re
 import sys
 
 FAM = {"0": "gemm", "1": "conv3x3", "2": "tconv3"}
+PLAIN_GEMM_KERNELS = [("hgeglu_kernel", "hgeglu_kernel<..>"), ("tsattn_fused_kernel", "tsattn_fused_kernel")]
 
 
 def table(path, counter):
@@ -16,12 +17,17 @@ def table(path, counter):
         # kernel names: gemm_kernel<Geo<4, 2>, MODE, FAST, SB> (round 3 on; the tile geometry comes first) or gemm_kernel<MODE, ...>
         # (round 5: wgemm_kernel<MODE, NREP, GEGLU> — the 288 x 320 tile — and its persistent plain-GEMM form wgemm_pkernel<NREP, GEGLU>)
         m = re.match(r"\| `([pw]?gemm\w*_p?kernel)<(?:\(anonymous namespace\)::)?(?:Geo<\d+, \d+>, )?(\d)[^`]*` \| " + counter + r" \| (\d+) \| ([0-9.e+]+) \|", line)
-        h = re.match(r"\| `(?:\(anonymous namespace\)::)?(hgeglu_kernel)<[^`]*` \| " + counter + r" \| (\d+) \| ([0-9.e+]+) \|", line)
-        if h:           # round 6: the two-workgroup 144 x 256 GEGLU kernel (plain GEMM family)
-            e = out.setdefault("gemm", {"kernels": [], "launches": 0, "kib": 0.0})
-            e["kernels"].append("hgeglu_kernel<..>")
-            e["launches"] += int(h.group(2))
-            e["kib"] += float(h.group(3))
+        # kernels of the plain GEMM family that are no gemm_kernel template: the two-workgroup 144 x 256 GEGLU kernel (round 6) and the
+        # fused temporal self-attention (q | k | v projection + attention over T, booked as the GEMM it contains)
+        for name, label in PLAIN_GEMM_KERNELS:
+            h = re.match(r"\| `(?:\(anonymous namespace\)::)?" + name + r"\b[^`]*` \| " + counter + r" \| (\d+) \| ([0-9.e+]+) \|", line)
+            if h:
+                e = out.setdefault("gemm", {"kernels": [], "launches": 0, "kib": 0.0})
+                e["kernels"].append(label)
+                e["launches"] += int(h.group(1))
+                e["kib"] += float(h.group(2))
+                break
+        if h:
             continue
         if m:
             fam = "gemm" if m.group(1) == "wgemm_pkernel" else FAM[m.group(2)]
@@ -29,6 +35,8 @@ def table(path, counter):
             e["kernels"].append(f"{m.group(1)}<{m.group(2)},..>")
             e["launches"] += int(m.group(3))
             e["kib"] += float(m.group(4))
+        elif re.match(r"\| `[^`]*(gemm|geglu|tsattn)[^`]*kernel[^`]*` \| " + counter + r" \|", line):
+            print(f"{path}: not counted in any family (name it above if it is a contraction of the step): {line.strip()}", file=sys.stderr)
     return out
 
 

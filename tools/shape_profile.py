@@ -86,6 +86,23 @@ def attn_flops(r, q, k, vt, out, **kw):
     return 4.0 * kw["frames"] * kw["heads"] * kw["nq"] * kw["nk"] * 64
 
 
+def tattn_key(r, qkv, out, **kw):
+    return (out.shape[0], out.shape[1], 0, f"T{kw['t']} heads{kw['heads']}")
+
+
+def tattn_flops(r, qkv, out, **kw):
+    return 4.0 * kw["clips"] * kw["hw"] * kw["heads"] * kw["t"] * kw["t"] * 64
+
+
+def tsattn_key(r, x, wh, out, **kw):
+    """The fused projection + attention: M x 3C x C like the qkv GEMM it contains."""
+    return (x.shape[0], wh.shape[0], wh.shape[1], f"T{kw['t']} heads{kw['heads']}")
+
+
+def tsattn_flops(r, x, wh, out, **kw):
+    return 2.0 * x.shape[0] * wh.shape[0] * wh.shape[1] + 4.0 * kw["clips"] * kw["hw"] * kw["heads"] * kw["t"] * kw["t"] * 64
+
+
 def gn_key(r, x, *a, **kw):
     return (x.shape[0], x.shape[1], 0, str(x.dtype).replace("torch.", "") + (" x2" if kw.get("x2") is not None else ""))
 
@@ -119,6 +136,8 @@ def main():
     wrap("conv3x3", conv_key, mnk_flops)
     wrap("tconv3", tconv_key, mnk_flops)
     wrap("attention", attn_key, attn_flops)
+    wrap("temporal_attention", tattn_key, tattn_flops)
+    wrap("temporal_self_attention", tsattn_key, tsattn_flops)
     wrap("groupnorm", gn_key, zero)
     wrap("layernorm", gn_key, zero)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
