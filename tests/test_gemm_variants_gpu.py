@@ -12,7 +12,8 @@ switches (MUDG_ATTN_Q, and MUDG_ATTN_DMA=0 / MUDG_ATTN_LEAN=0 / MUDG_ATTN_X=0: t
 classic softmax on prescaled Q, the one-tile kernel on many-tile cross-attention) run tests/test_attention_kernels_gpu.py.  Every child of
 VARIANTS and VARIANTS_X3 also runs tests/test_gemm_kernels_gpu.py — each forced kernel against the fp64 definitions, exactly, at every shape
 of that file it is eligible for — and VARIANTS_GEMM (the 288-row tile on the 160-row tile's loop, the 160-row tile with every residual
-seeding) run that file alone."""
+seeding) run that file alone.  VARIANTS_NORM (the LDS-table GroupNorm apply kernel for every width, the one-wave-per-row LayerNorm kernel for
+the five UNet widths) run tests/test_norm_kernels_gpu.py alone."""
 import os
 import subprocess
 import sys
@@ -56,6 +57,9 @@ ATTN_FILE = "tests/test_attention_kernels_gpu.py"
 # residuals seeding the accumulators instead of waiting for the epilogue.  These children run the per-kernel GEMM file only
 VARIANTS_GEMM = [{"MUDG_GEMM_W288": "2", "MUDG_GEMM_W288Q": "2"}, {"MUDG_GEMM_W160": "2", "MUDG_GEMM_W160DEFER": "0"}]
 GEMM_FILE = "tests/test_gemm_kernels_gpu.py"
+# The per-kernel norm file under its two switches: gn_apply_kernel for every GroupNorm case, ln_kernel at 320 / 512 / 640 / 1024 / 1280
+VARIANTS_NORM = [{"MUDG_GN_REG": "0"}, {"MUDG_LN_ROWS": "0"}]
+NORM_FILE = "tests/test_norm_kernels_gpu.py"
 _name = lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items())
 
 
@@ -74,6 +78,9 @@ def children():
     for env in VARIANTS_GEMM:
         runs.submit(_name(env), [sys.executable, "-m", "pytest", GEMM_FILE, "-m", "gpu", "-q", "-p", "no:cacheprovider"],
                     ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", **env), 900)
+    for env in VARIANTS_NORM:
+        runs.submit(_name(env), [sys.executable, "-m", "pytest", NORM_FILE, "-m", "gpu", "-q", "-p", "no:cacheprovider"],
+                    ROOT, dict(os.environ, MUDG_DEBUG_VARIANTS="1", **env), 900)
     for env in VARIANTS_X3:
         runs.submit("x3:" + _name(env), [sys.executable, "-m", "pytest", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py", GEMM_FILE, "-m", "gpu", "-q",
                                          "-p", "no:cacheprovider"],
@@ -83,7 +90,7 @@ def children():
     runs.shutdown()
 
 
-@pytest.mark.parametrize("env", VARIANTS + VARIANTS_ATTN + VARIANTS_GEMM, ids=_name)
+@pytest.mark.parametrize("env", VARIANTS + VARIANTS_ATTN + VARIANTS_GEMM + VARIANTS_NORM, ids=_name)
 def test_kernel_parity_under_variant(cuda, env, request):
     if os.environ.get("MUDG_DEBUG_VARIANTS") == "1":
         pytest.skip("already running under a variant switch")

@@ -30,16 +30,17 @@ MODES = {
              ["tests/test_kernels_gpu.py", "tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py",
               "tests/test_pipeline_gpu.py", "tests/test_sampler_options_gpu.py", "tests/test_fullsize_gpu.py",
               "tests/test_training_gpu.py", "tests/test_backward_kernels_gpu.py", "tests/test_attention_kernels_gpu.py",
-              "tests/test_gemm_kernels_gpu.py"]),
+              "tests/test_gemm_kernels_gpu.py", "tests/test_norm_kernels_gpu.py"]),
     # test_kernels_gpu.py builds its inputs as plain 16-bit tensors; the split modes run the mode-agnostic kernel suite.
     # bf16x3 is the mode that carries the contract: the full-size config-0 cut asserts the literal 1e-3 there
     "bf16x3": ({"MUDG_OPERAND": "bf16x3"},
                ["tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py", "tests/test_pipeline_gpu.py",
                 "tests/test_sampler_options_gpu.py", "tests/test_training_gpu.py", "tests/test_backward_kernels_gpu.py",
-                "tests/test_attention_kernels_gpu.py", "tests/test_gemm_kernels_gpu.py", CUT, FWD512, FWD1024, STEP1024]),
+                "tests/test_attention_kernels_gpu.py", "tests/test_gemm_kernels_gpu.py", "tests/test_norm_kernels_gpu.py", CUT, FWD512, FWD1024,
+                STEP1024]),
     "bf16x6": ({"MUDG_OPERAND": "bf16x6"},
                ["tests/test_operand_modes_gpu.py", "tests/test_unet_gpu.py", "tests/test_pipeline_gpu.py", "tests/test_attention_kernels_gpu.py",
-                "tests/test_gemm_kernels_gpu.py"]),
+                "tests/test_gemm_kernels_gpu.py", "tests/test_norm_kernels_gpu.py"]),
     # BASELINE.json configs[4]: MX-fp8 scores in the long self-attention (>= 512 tokens of head width 64: the full-size
     # topology, not the small fixtures), END TO END: the full-size MDM512 UNet forward, the 4-frame MDM1024 forward and the config-0
     # cut (guided DDIM step + decode) against the CPU oracle under the switch, the MDM1024 property tests, and the kernel-level
