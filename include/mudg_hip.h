@@ -422,6 +422,37 @@ int mudg_metric_depth(const float* depth, const float* lidar, int frames, int H,
 int mudg_metric_confusion(const int64_t* pred, const int64_t* gt, int frames, int H, int W, int classes, int64_t* confusion,
                           int64_t* bad, void* stream);
 
+/* ------------------------------------------------------------------ frames in: camera, depth and label frames to clips
+ * (lvdm/data/waymo_data.py:55-412 and virtual_render/data_tools.py:7-215 ask this of cv2.resize on the host, per frame and stream;
+ * the rules are this project's, written out in DESIGN §16, and bit-equal to tests/frames_reference.py.)
+ * A table has one 16-byte entry per output sample of an axis, made on the host: int32 s0, s1 (the two source indices; nearest reads s0
+ * only) and the coefficients of s0 and s1 — int32 that sum to 2048 for the 8-bit rule, fp32 bit patterns w0, w1 for the fp32 rule.
+ * xtab has W entries, ytab H.  T, H <= 65535; H0 W0, H W <= 2^28.
+ * resize_u8:  src (T, H0, W0, C) uint8 -> dst (T, H, W, C), C = 1 or 3.  Linear: R = S[x0] a0 + S[x1] a1 per source row in int32,
+ *   out = (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2                    waymo_data.py:80, 92 (INTER_LINEAR)
+ *   nearest: out = S[y.s0][x.s0]                                                          waymo_data.py:86 (INTER_NEAREST)
+ *   palette != 0 (linear, C = 3): src is (T, H0, W0) class ids and S is the id's colour of the 21 (an id above 20: black), looked up
+ *   on the four taps                                                                      data_process/tools/semantic_tools.py:45-73
+ * resize_f32: src (T, H0, W0) fp32 -> dst (T, H, W): R = S[x0] w0 + S[x1] w1, out = R0 v0 + R1 v1, every operation rounded on its own.
+ * dense_stream: one stream of a clip, three fp32 planes per frame: value (channel c, frame t, row y, column x) goes to
+ *   dst + slab stream_stride + (frame0 + t) frame_stride + c channel_stride + y W + x (floats).  kind colour: src (T, H0, W0, 3) uint8,
+ *   the 8-bit rule, then norm[v], the caller's 256 values of (v / 255 - 0.5) * 2          waymo_data.py:103, 117
+ *   semantic: src (T, H0, W0) ids, the palette form of the 8-bit rule, then norm[v]; depth: src (T, H0, W0) fp32 metres, the fp32
+ *   rule, then (clamp(d, 0, 100) / 100 - 0.5) * 2 in that order, the same value in the three channels (norm may be NULL).
+ *   u8_out (or NULL; NULL for depth): the resized bytes (T, H, W, 3), what resize_u8 gives. */
+#define MUDG_RESIZE_LINEAR 0
+#define MUDG_RESIZE_NEAREST 1
+#define MUDG_STREAM_COLOUR 0
+#define MUDG_STREAM_SEMANTIC 1
+#define MUDG_STREAM_DEPTH 2
+int mudg_resize_u8(const uint8_t* src, uint8_t* dst, int T, int H0, int W0, int C, int H, int W, int mode, int palette,
+                   const int32_t* xtab, const int32_t* ytab, void* stream);
+int mudg_resize_f32(const float* src, float* dst, int T, int H0, int W0, int H, int W, const int32_t* xtab, const int32_t* ytab,
+                    void* stream);
+int mudg_dense_stream(int kind, const void* src, int T, int H0, int W0, int H, int W, const int32_t* xtab, const int32_t* ytab,
+                      const float* norm, float* dst, int64_t stream_stride, int64_t channel_stride, int64_t frame_stride, int slab,
+                      int frame0, uint8_t* u8_out, void* stream);
+
 /* ------------------------------------------------------------------ training step
  * Reference: lvdm/models/ddpm3d.py:741-802 (p_losses), :1267-1300 (configure_optimizers -> torch.optim.AdamW),
  * main/utils_train.py:126-137 (data-parallel strategy).  The contractions of the backward pass (dX = dY W, dW = dY^T X,

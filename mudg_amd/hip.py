@@ -165,6 +165,9 @@ SIGNATURES = {
     "mudg_metric_ssim": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "mudg_metric_depth": (_I, [_P, _P, _I, _I, _I, _D, _D, _P, _P]),
     "mudg_metric_confusion": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "mudg_resize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "mudg_resize_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "mudg_dense_stream": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P]),
     "mudg_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_float), _P, _P]),
     "mudg_gaussian_sample": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "mudg_posterior_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _F, _P]),

@@ -970,3 +970,135 @@ def metric_confusion(pred, gt, classes=19):
     hip.check(hip.lib().mudg_metric_confusion(pred.data_ptr(), gt.data_ptr(), f, h, w, classes, confusion.data_ptr(), bad.data_ptr(), _stream()),
               "mudg_metric_confusion")
     return confusion, bad
+
+
+# ------------------------------------------------------------------------------------------------ frames in: resize to clips
+RESIZE_MODES = ("linear_u8", "linear_f32", "nearest")
+STREAM_KINDS = {"color": 0, "semantic": 1, "depth": 2}           # mudg_dense_stream's kind
+COEF_ONE = 2048                                                 # the 8-bit rule's coefficient pairs sum to this
+_RESIZE_TABLES = {}
+_NORM_TABLES = {}
+
+
+def resize_table(n_src, n_dst, mode):
+    """The sample table of one axis, host numpy (n_dst, 4) int32: s0, s1 and the two coefficients — int32 that sum to 2048
+    (linear_u8), fp32 bit patterns 1 - f, f (linear_f32) or zeros (nearest: s1 = s0).  Everything is computed here, in float64 and fp32 as
+    the rule states; a kernel computes no coordinate."""
+    import numpy as np
+    n_src, n_dst = int(n_src), int(n_dst)
+    if n_src < 1 or n_dst < 1 or mode not in RESIZE_MODES:
+        raise hip.MudgError(f"resize_table: {n_src} -> {n_dst} samples, mode {mode!r} ({' | '.join(RESIZE_MODES)})")
+    d = np.arange(n_dst, dtype=np.float64)
+    scale = np.float64(n_src) / np.float64(n_dst)
+    table = np.zeros((n_dst, 4), dtype=np.int32)
+    if mode == "nearest":
+        table[:, 0] = table[:, 1] = np.minimum(np.floor(d * scale).astype(np.int64), n_src - 1)
+        return table
+    f = ((d + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f)
+    f = f - s                                                   # fp32, exact
+    s = s.astype(np.int64)
+    low = s < 0
+    s[low], f[low] = 0, 0
+    high = s >= n_src - 1
+    s[high], f[high] = n_src - 1, 0
+    table[:, 0], table[:, 1] = s, np.minimum(s + 1, n_src - 1)
+    one = np.float32(1)
+    if mode == "linear_u8":
+        k = np.float32(COEF_ONE)
+        table[:, 2] = np.rint((one - f) * k).astype(np.int16)
+        table[:, 3] = np.rint(f * k).astype(np.int16)
+    else:
+        table[:, 2] = (one - f).astype(np.float32).view(np.int32)
+        table[:, 3] = f.view(np.int32)
+    return table
+
+
+def _resize_tables(hw_in, hw_out, mode, device):
+    """The (ytab, xtab) pair on the device, uploaded once per (n_src, n_dst, mode)."""
+    out = []
+    for n_src, n_dst in zip(hw_in, hw_out):
+        key = (int(n_src), int(n_dst), mode, device)
+        if key not in _RESIZE_TABLES:
+            _RESIZE_TABLES[key] = torch.from_numpy(resize_table(n_src, n_dst, mode)).to(device)
+        out.append(_RESIZE_TABLES[key])
+    return out
+
+
+def norm_table(device):
+    """(v / 255 - 0.5) * 2 for v = 0 .. 255, computed by torch on the host with the loaders' expression (waymo_data.py:117)."""
+    if device not in _NORM_TABLES:
+        _NORM_TABLES[device] = ((torch.arange(256, dtype=torch.uint8).float() / 255 - 0.5) * 2).to(device)
+    return _NORM_TABLES[device]
+
+
+def _hw_out(name, hw_out):
+    h, w = (int(v) for v in hw_out)
+    if h < 1 or w < 1:
+        raise hip.MudgError(f"{name}: output size {h} x {w}")
+    return h, w
+
+
+def resize_u8(src, hw_out, mode="linear", *, palette=False):
+    """(T, H0, W0, C) uint8, C = 1 or 3 -> (T, h, w, C) by the 8-bit linear rule or nearest.  palette: src is (T, H0, W0)
+    class ids and the result the resized colour-mapped map (T, h, w, 3), the colours looked up on the taps."""
+    _splat_tensor("resize_u8: src", src, torch.uint8)
+    if mode not in ("linear", "nearest"):
+        raise hip.MudgError(f"resize_u8: mode {mode!r} (linear | nearest)")
+    if src.dim() != (3 if palette else 4) or src.numel() == 0 or (not palette and src.shape[3] not in (1, 3)):
+        raise hip.MudgError(f"resize_u8: expected {'(frames, H, W) class ids' if palette else '(frames, H, W, 1 or 3) frames'}, got {tuple(src.shape)}")
+    if palette and mode != "linear":
+        raise hip.MudgError("resize_u8: the label palette goes with the linear rule")
+    h, w = _hw_out("resize_u8", hw_out)
+    t, h0, w0 = src.shape[:3]
+    c = 3 if palette else src.shape[3]
+    ytab, xtab = _resize_tables((h0, w0), (h, w), "linear_u8" if mode == "linear" else "nearest", src.device)
+    out = torch.empty((t, h, w, c), dtype=torch.uint8, device=src.device)
+    hip.check(hip.lib().mudg_resize_u8(src.data_ptr(), out.data_ptr(), t, h0, w0, c, h, w, 0 if mode == "linear" else 1, int(bool(palette)),
+                                       xtab.data_ptr(), ytab.data_ptr(), _stream()), "mudg_resize_u8")
+    return out
+
+
+def resize_f32(src, hw_out):
+    """(T, H0, W0) fp32 -> (T, h, w) by the fp32 linear rule: every multiply and add rounded on its own, in the rule's order."""
+    _splat_tensor("resize_f32: src", src, torch.float32)
+    if src.dim() != 3 or src.numel() == 0:
+        raise hip.MudgError(f"resize_f32: expected (frames, H, W) maps, got {tuple(src.shape)}")
+    h, w = _hw_out("resize_f32", hw_out)
+    t, h0, w0 = src.shape
+    ytab, xtab = _resize_tables((h0, w0), (h, w), "linear_f32", src.device)
+    out = torch.empty((t, h, w), dtype=torch.float32, device=src.device)
+    hip.check(hip.lib().mudg_resize_f32(src.data_ptr(), out.data_ptr(), t, h0, w0, h, w, xtab.data_ptr(), ytab.data_ptr(), _stream()), "mudg_resize_f32")
+    return out
+
+
+def dense_stream(kind, src, hw_out, out=None, *, slab=0, frame0=0, return_u8=False):
+    """One dense stream of a clip (DESIGN.md §16).  kind "color": src (T, H0, W0, 3) uint8; "semantic": (T, H0, W0) uint8 class ids;
+    "depth": (T, H0, W0) fp32 metres.  Writes (3, T, h, w) fp32 in [-1, 1]: into a new tensor, or into `out` — (3, T', h, w), or
+    (S, 3, T', h, w) at stream `slab` — at frames frame0 .. frame0 + T - 1, rows contiguous, any other strides.  return_u8 (not depth):
+    also the resized bytes (T, h, w, 3), what resize_u8 gives.  Returns out, or (out, bytes)."""
+    if kind not in STREAM_KINDS:
+        raise hip.MudgError(f"dense_stream: kind {kind!r} ({' | '.join(STREAM_KINDS)})")
+    _splat_tensor(f"dense_stream: the {kind} source", src, torch.float32 if kind == "depth" else torch.uint8)
+    if src.dim() != (4 if kind == "color" else 3) or src.numel() == 0 or (kind == "color" and src.shape[3] != 3):
+        raise hip.MudgError(f"dense_stream: a {kind} source is {'(frames, H, W, 3)' if kind == 'color' else '(frames, H, W)'}, got {tuple(src.shape)}")
+    if return_u8 and kind == "depth":
+        raise hip.MudgError("dense_stream: the depth stream has no uint8 frames")
+    h, w = _hw_out("dense_stream", hw_out)
+    t, h0, w0 = src.shape[:3]
+    slab, frame0 = int(slab), int(frame0)
+    if out is None:
+        out = torch.empty((3, t, h, w), dtype=torch.float32, device=src.device)
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != src.device or out.dim() not in (4, 5):
+        raise hip.MudgError("dense_stream: out is a (3, frames, h, w) or (streams, 3, frames, h, w) fp32 tensor on the source's device")
+    slabs = out.shape[0] if out.dim() == 5 else 1
+    if (tuple(out.shape[-4:-2]) != (3, out.shape[-3]) or tuple(out.shape[-2:]) != (h, w) or out.stride(-1) != 1 or out.stride(-2) != w
+            or not (0 <= slab < slabs and 0 <= frame0 and frame0 + t <= out.shape[-3]) or out.stride(-3) < h * w or out.stride(-4) <= 0):
+        raise hip.MudgError(f"dense_stream: {t} frames of {h} x {w} at stream {slab}, frame {frame0} of out {tuple(out.shape)} strides {out.stride()}")
+    ytab, xtab = _resize_tables((h0, w0), (h, w), "linear_f32" if kind == "depth" else "linear_u8", src.device)
+    norm = None if kind == "depth" else norm_table(src.device)
+    u8 = torch.empty((t, h, w, 3), dtype=torch.uint8, device=src.device) if return_u8 else None
+    hip.check(hip.lib().mudg_dense_stream(STREAM_KINDS[kind], src.data_ptr(), t, h0, w0, h, w, xtab.data_ptr(), ytab.data_ptr(), _ptr(norm),
+                                          out.data_ptr(), out.stride(0) if out.dim() == 5 else 0, out.stride(-4), out.stride(-3), slab, frame0,
+                                          _ptr(u8), _stream()), "mudg_dense_stream")
+    return (out, u8) if return_u8 else out
