@@ -453,6 +453,43 @@ int mudg_dense_stream(int kind, const void* src, int T, int H0, int W0, int H, i
                       const float* norm, float* dst, int64_t stream_stride, int64_t channel_stride, int64_t frame_stride, int slab,
                       int frame0, uint8_t* u8_out, void* stream);
 
+/* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
+ * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
+ * these entries are what it needs besides.
+ *
+ * short_attention: softmax(scale Q K^T) V over a short sequence, every key (then every value) of one (image, head) in LDS.
+ *   q, k and v are rounded once to operand storage while they are staged (the bits mudg_gemm would have stored with out_fp32 = 0);
+ *   scores accumulate in fp32; one pass with the exact row maximum m: p_j = 2^(c s_j - c m), c = scale log2(e), key columns >= N
+ *   masked; l = sum_j p_j in fp32; P passes through operand storage; O = (P V) / l, rounded once.  No atomics: a repeat run is
+ *   bit-equal.  16-bit builds: MFMA 32x32x16 (d = 80 is five K = 16 steps, no padding of d for the scores; the value rows of P V are
+ *   padded 80 -> 96); split builds: fp32 on the vector unit from the operand-rounded values. */
+typedef struct MudgShortAttnDesc {
+    const float* QKV;   /* fp32 rows [B N][ldqkv]: q of head h at columns [h d, h d + d), k at C + h d, v at 2 C + h d, C = heads d
+                           (the fused in_proj GEMM's output with out_fp32 = 1) */
+    void* O;            /* MFMA-operand rows [B N][ldo] in the build's operand layout, head h at [h d, h d + d) */
+    int B, heads, N, d;
+    int64_t ldqkv, ldo;
+    float scale;        /* d^-0.5 */
+} MudgShortAttnDesc;
+/* 1 when the call below would run, reading nothing: d = 64 or 80, 1 <= N <= 288, ldqkv >= 3 C, ldo a multiple of 8 * PLANES with
+ * ldo / PLANES >= C, B and heads positive (B <= 65535); else 0 with the reason as the error text.  The call itself also needs
+ * non-null pointers and a 16-byte aligned O, and returns MUDG_EINVAL before any launch otherwise. */
+int mudg_short_attention_ok(const MudgShortAttnDesc* d);
+int mudg_short_attention(const MudgShortAttnDesc* d, void* stream);
+/* LayerNorm over the last dim with an fp32 result (ln_pre: its output is the tower's residual stream): the arithmetic of
+ * mudg_layernorm on fp32 rows, without the operand rounding of the store.  Row strides in elements. */
+int mudg_layernorm_f32(const float* X, int64_t ldx, const float* gamma, const float* beta, float* Y, int64_t ldy, int rows, int C,
+                       float eps, void* stream);
+/* clip_preprocess: src (B, 3, H, W) fp32 in [-1, 1] -> the 224 x 224 CLIP input as the patch matrix of the 14 x 14 / stride 14
+ *   convolution: operand rows patches[B 256][ldp], row (b, 16 gy + gx), column c 196 + 14 py + px (conv1.weight.reshape(width, 588)'s
+ *   order), columns 588 .. 591 zero (ldp / PLANES >= 592); image (or NULL): the fp32 (B, 3, 224, 224) image itself.
+ *   Rule: optional separable Gaussian blur (taps gx[kx] along x first, then gy[ky] along y, reflect border without the
+ *   edge; ky = kx = 0: none), bicubic sample (xtab / ytab: per destination index four source indices and the fp32 bits of four
+ *   coefficients, 8 int32, x taps summed first), (v + 1) * 0.5, - mean_c, / std_c.  Every operation is a single rounded fp32 one,
+ *   sums run left to right from the first tap; the tables come from the host and every index is clamped before its load. */
+int mudg_clip_preprocess(const float* src, int B, int H, int W, const int32_t* ytab, const int32_t* xtab, const float* gy, int ky,
+                         const float* gx, int kx, void* patches, int64_t ldp, float* image, void* stream);
+
 /* ------------------------------------------------------------------ training step
  * Reference: lvdm/models/ddpm3d.py:741-802 (p_losses), :1267-1300 (configure_optimizers -> torch.optim.AdamW),
  * main/utils_train.py:126-137 (data-parallel strategy).  The contractions of the backward pass (dX = dY W, dW = dY^T X,

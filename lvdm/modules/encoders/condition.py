@@ -2,11 +2,12 @@
 
 MuDG's YAML configs name the OpenCLIP towers by this path (configs/stage2-1024_mdm_waymo_infer.yaml:82,88 ->
 reference lvdm/modules/encoders/condition.py: FrozenOpenCLIPEmbedder :174, FrozenOpenCLIPImageEmbedderV2 :295).  The
-towers are third-party models with downloaded weights and are OUTSIDE the denoising path (SURVEY §8 / DESIGN §8): this
-repo ships no CLIP code.  When this package's `lvdm/` is the one on the import path, the names below resolve lazily to
-the classes of an externally provided condition module:
+towers are third-party models with downloaded weights and are OUTSIDE the denoising path (SURVEY §8 / DESIGN §8): nothing
+is implemented in this file.  When this package's `lvdm/` is the one on the import path, the names below resolve lazily to
+the classes of a condition module named from outside:
 
-  * MUDG_CONDITION_MODULE=<dotted.module>   an importable module that defines them, or
+  * MUDG_CONDITION_MODULE=<dotted.module>   an importable module that defines them — `mudg_amd.towers` is this package's own
+    (the image tower on the HIP kernels and the text tower as a table of the run's prompts), or
   * MUDG_REFERENCE=<path to a MuDG checkout>  its lvdm/modules/encoders/condition.py is loaded under a private module
     name (it imports `lvdm.common.autocast` and `utils.utils.count_params`, which this overlay provides).
 

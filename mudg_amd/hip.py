@@ -114,6 +114,15 @@ class WgradDesc(C.Structure):
     ]
 
 
+class ShortAttnDesc(C.Structure):
+    _fields_ = [
+        ("QKV", C.c_void_p), ("O", C.c_void_p),
+        ("B", C.c_int), ("heads", C.c_int), ("N", C.c_int), ("d", C.c_int),
+        ("ldqkv", C.c_int64), ("ldo", C.c_int64),
+        ("scale", C.c_float),
+    ]
+
+
 # name -> (restype, argtypes); this table is also what tests check against include/mudg_hip.h
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
@@ -168,6 +177,10 @@ SIGNATURES = {
     "mudg_resize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mudg_resize_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mudg_dense_stream": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P]),
+    "mudg_short_attention_ok": (_I, [C.POINTER(ShortAttnDesc)]),
+    "mudg_short_attention": (_I, [C.POINTER(ShortAttnDesc), _P]),
+    "mudg_layernorm_f32": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P]),
+    "mudg_clip_preprocess": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _L, _P, _P]),
     "mudg_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_float), _P, _P]),
     "mudg_gaussian_sample": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "mudg_posterior_assemble": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _F, _P]),

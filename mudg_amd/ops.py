@@ -1102,3 +1102,111 @@ def dense_stream(kind, src, hw_out, out=None, *, slab=0, frame0=0, return_u8=Fal
                                           out.data_ptr(), out.stride(0) if out.dim() == 5 else 0, out.stride(-4), out.stride(-3), slab, frame0,
                                           _ptr(u8), _stream()), "mudg_dense_stream")
     return (out, u8) if return_u8 else out
+
+
+# ------------------------------------------------------------------------------------------------ the CLIP image tower
+CLIP_SIZE, CLIP_PATCH, CLIP_K, CLIP_KPAD = 224, 14, 588, 592
+_CLIP_TABLES = {}
+
+
+def clip_blur_taps(n_src, n_dst=CLIP_SIZE):
+    """The Gaussian taps of one axis of the antialiasing blur, host numpy fp32 (k,): f = n_src / n_dst, sigma = max((f - 1) / 2, 0.001),
+    k = int(max(4 sigma, 3)) made odd, exp(-(i - (k - 1) / 2)^2 / (2 sigma^2)) normalised to sum 1 — in float64, rounded once."""
+    import numpy as np
+    f = np.float64(n_src) / np.float64(n_dst)
+    sigma = max((f - 1.0) / 2.0, 0.001)
+    k = int(max(4.0 * sigma, 3.0))
+    k += 1 - k % 2
+    i = np.arange(k, dtype=np.float64) - (k - 1) / 2.0
+    g = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    return (g / g.sum()).astype(np.float32)
+
+
+def clip_cubic_table(n_src, n_dst=CLIP_SIZE):
+    """The bicubic sample table of one axis, host numpy (n_dst, 8) int32: four source indices floor(src) - 1 .. + 2 clamped to the image and
+    the fp32 bits of the four coefficients (A = -0.75), src = dst (n_src - 1) / (n_dst - 1) (align_corners) — in float64, rounded once."""
+    import numpy as np
+    n_src, n_dst = int(n_src), int(n_dst)
+    A = -0.75
+    d = np.arange(n_dst, dtype=np.float64)
+    src = d * (np.float64(n_src - 1) / np.float64(n_dst - 1)) if n_dst > 1 else np.zeros(1)
+    i0 = np.floor(src)
+    t = src - i0
+    near = lambda x: ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0
+    far = lambda x: ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A
+    coef = np.stack([far(t + 1.0), near(t), near(1.0 - t), far(2.0 - t)], 1).astype(np.float32)
+    idx = np.clip(i0.astype(np.int64)[:, None] + np.arange(-1, 3)[None, :], 0, n_src - 1)
+    table = np.empty((n_dst, 8), dtype=np.int32)
+    table[:, :4], table[:, 4:] = idx, coef.view(np.int32)
+    return table
+
+
+def _clip_tables(h, w, antialias, device):
+    """(ytab, xtab, gy, gx) on the device, uploaded once per (H, W, antialias, device); gy = gx = None without the blur."""
+    key = (int(h), int(w), bool(antialias), device)
+    if key not in _CLIP_TABLES:
+        blur = antialias and max(h, w) > CLIP_SIZE               # max(f_h, f_w) > 1
+        up = lambda a: torch.from_numpy(a).to(device)
+        _CLIP_TABLES[key] = (up(clip_cubic_table(h)), up(clip_cubic_table(w)), up(clip_blur_taps(h)) if blur else None,
+                             up(clip_blur_taps(w)) if blur else None)
+    return _CLIP_TABLES[key]
+
+
+def clip_preprocess(x, *, antialias=True, patches=None, image=None, return_image=False):
+    """(B, 3, H, W) fp32 in [-1, 1] -> the patch matrix of the 224 x 224 CLIP input, operand rows [B 256][592] (mudg_clip_preprocess).
+    patches / image: destinations inside larger buffers (a rows view; a contiguous (B, 3, 224, 224) fp32 view); return_image: also
+    return the fp32 image (tests and inspection)."""
+    _splat_tensor("clip_preprocess: images", x, torch.float32)
+    if x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise hip.MudgError(f"clip_preprocess: expected (B, 3, H, W) images, got {tuple(x.shape)}")
+    b, _, h, w = x.shape
+    if patches is None:
+        patches = empty_rows(b * 256, CLIP_KPAD, None, x.device)
+    _rows(patches)
+    if tuple(patches.shape) != (b * 256, CLIP_KPAD):
+        raise hip.MudgError(f"clip_preprocess: patches are operand rows [{b * 256}][{CLIP_KPAD}], got {tuple(patches.shape)}")
+    if image is None and return_image:
+        image = torch.empty((b, 3, CLIP_SIZE, CLIP_SIZE), dtype=torch.float32, device=x.device)
+    if image is not None:
+        _splat_tensor("clip_preprocess: image", image, torch.float32, (b, 3, CLIP_SIZE, CLIP_SIZE))
+    ytab, xtab, gy, gx = _clip_tables(h, w, antialias, x.device)
+    hip.check(hip.lib().mudg_clip_preprocess(x.data_ptr(), b, h, w, ytab.data_ptr(), xtab.data_ptr(), _ptr(gy), 0 if gy is None else gy.numel(),
+                                             _ptr(gx), 0 if gx is None else gx.numel(), patches.data_ptr(), patches.stride(0), _ptr(image),
+                                             _stream()), "mudg_clip_preprocess")
+    return (patches, image) if return_image else patches
+
+
+def short_attention_desc(qkv_ptr, o_ptr, *, batch, heads, n, d, ldqkv, ldo, scale=None):
+    desc = hip.ShortAttnDesc()
+    desc.QKV, desc.O, desc.B, desc.heads, desc.N, desc.d = qkv_ptr, o_ptr, batch, heads, n, d
+    desc.ldqkv, desc.ldo, desc.scale = ldqkv, ldo, float(d) ** -0.5 if scale is None else scale
+    return desc
+
+
+def short_attention(qkv, out=None, *, batch, heads, n, d, scale=None):
+    """Self-attention over n <= 288 tokens from the fp32 rows [batch n][>= 3 heads d] of a fused q | k | v projection
+    (mudg_short_attention): operand rows [batch n][heads d].  Head width 64 or 80; anything else raises."""
+    _rows(qkv, torch.float32)
+    if qkv.shape[0] != batch * n:
+        raise hip.MudgError(f"short_attention: qkv has {qkv.shape[0]} rows, batch {batch} x {n} tokens")
+    if out is None:
+        out = empty_rows(batch * n, heads * d, None, qkv.device)
+    _rows(out)
+    _drop_stats(out)
+    if qkv.shape[1] < 3 * heads * d or out.shape[0] != batch * n or out.shape[1] < heads * d:
+        raise hip.MudgError(f"short_attention: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} for {heads} heads of {d}")
+    desc = short_attention_desc(qkv.data_ptr(), out.data_ptr(), batch=batch, heads=heads, n=n, d=d, ldqkv=qkv.stride(0), ldo=out.stride(0),
+                                scale=scale)
+    hip.check(hip.lib().mudg_short_attention(C.byref(desc), _stream()), "mudg_short_attention")
+    return out
+
+
+def layernorm_f32(x, gamma, beta, *, eps=1e-5, out=None):
+    """LayerNorm of fp32 rows with an fp32 result (mudg_layernorm_f32)."""
+    _rows(x, torch.float32)
+    if out is None:
+        out = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+    _rows(out, torch.float32)
+    hip.check(hip.lib().mudg_layernorm_f32(x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), out.stride(0),
+                                           x.shape[0], x.shape[1], eps, _stream()), "mudg_layernorm_f32")
+    return out
