@@ -609,6 +609,24 @@ int mudg_swap_multi(const int64_t* table, int nchunks, void* stream);
  * scratch; out: float [2] = (total 2-norm, clip coefficient min(1, max_norm / (norm + 1e-6))); the gradients are scaled in place. */
 int mudg_clip_chunk(void);
 int mudg_clip_grad_norm(const int64_t* table, int nchunks, double* partial, float max_norm, float* out, void* stream);
+/* Loss scaling for fp16 training (torch.amp.GradScaler semantics) with no host round trip.  record: 16 bytes of device memory,
+ * 16-byte aligned: float scale, int32 growth tracker, int32 overflow flag of the current step, int32 count of steps actually taken.
+ * scaled_grad_norm: the tables of mudg_clip_grad_norm over the SCALED gradients; out[0] = the 2-norm of g * inv_scale
+ *   (inv_scale = float(1 / double(scale))), out[1] = min(1, max_norm / (norm + 1e-6)) or 1 when max_norm is 0 (no clipping); the
+ *   record's flag is set iff any gradient is inf or NaN.  The gradients are not written.
+ * unscale_multi, rows (address, count): g = g * inv_scale in place (for inspection; the optimiser does not need it).
+ * adamw_scaled_multi / adamw_scaled_ema_multi: mudg_adamw_multi / mudg_adamw_ema_multi on the gradient (g * inv_scale) * stat[1]
+ *   (stat: the `out` of scaled_grad_norm), bias corrections of step count + 1; flag set: parameters and moments are left alone
+ *   (the EMA form still averages the unchanged parameter).
+ * loss_scale_update: overflow: scale *= backoff, tracker = 0; else tracker += 1 and at growth_interval scale *= growth (if finite),
+ *   tracker = 0; then count += !flag, flag = 0. */
+int mudg_scaled_grad_norm(const int64_t* table, int nchunks, double* partial, float max_norm, float* out, void* record, void* stream);
+int mudg_unscale_multi(const int64_t* table, int nchunks, const void* record, void* stream);
+int mudg_adamw_scaled_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay,
+                            const void* record, const float* stat, void* stream);
+int mudg_adamw_scaled_ema_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                float one_minus_decay, const void* record, const float* stat, void* stream);
+int mudg_loss_scale_update(void* record, float growth_factor, float backoff_factor, int growth_interval, void* stream);
 /* Inverted dropout out[i] = keep(seed, i) ? x[i] / (1 - p) : 0 with a counter-based mask (the backward pass applies the same
  * call to the gradient: nothing is stored). */
 int mudg_dropout(const float* x, float* out, int64_t n, float p, uint64_t seed, void* stream);

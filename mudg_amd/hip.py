@@ -211,6 +211,11 @@ SIGNATURES = {
     "mudg_swap_multi": (_I, [_P, _I, _P]),
     "mudg_clip_chunk": (_I, []),
     "mudg_clip_grad_norm": (_I, [_P, _I, _P, _F, _P, _P]),
+    "mudg_scaled_grad_norm": (_I, [_P, _I, _P, _F, _P, _P, _P]),
+    "mudg_unscale_multi": (_I, [_P, _I, _P, _P]),
+    "mudg_adamw_scaled_multi": (_I, [_P, _I, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "mudg_adamw_scaled_ema_multi": (_I, [_P, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "mudg_loss_scale_update": (_I, [_P, _F, _F, _I, _P]),
     "mudg_gelu": (_I, [_P, _P, _P, _L, _P]),
     "mudg_silu": (_I, [_P, _P, _P, _L, _P]),
     "mudg_dropout": (_I, [_P, _P, _L, _F, C.c_uint64, _P]),

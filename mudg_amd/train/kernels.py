@@ -294,6 +294,39 @@ def adamw_ema_multi_(table, nchunks, *, lr, betas, eps, weight_decay, step, one_
               "mudg_adamw_ema_multi")
 
 
+def scaled_grad_norm(table, nchunks, partial, max_norm, record):
+    """The norm pass under a loss scale (mudg_scaled_grad_norm; table rows: address, count): returns the device tensor
+    [norm of the unscaled gradients, clip coefficient (1 when max_norm is None)] and sets the overflow flag of `record`; the
+    gradients are read only."""
+    out = torch.empty(2, dtype=torch.float32, device=table.device)
+    hip.check(hip.lib().mudg_scaled_grad_norm(table.data_ptr(), nchunks, partial.data_ptr(), 0.0 if max_norm is None else max_norm,
+                                              out.data_ptr(), record.data_ptr(), _s()), "mudg_scaled_grad_norm")
+    return out
+
+
+def unscale_multi_(table, nchunks, record):
+    """g <- g * float(1 / scale) in place over every tensor listed in `table` (rows: address, count)."""
+    hip.check(hip.lib().mudg_unscale_multi(table.data_ptr(), nchunks, record.data_ptr(), _s()), "mudg_unscale_multi")
+
+
+def adamw_scaled_multi_(table, nchunks, record, stat, *, lr, betas, eps, weight_decay):
+    """adamw_multi_ on the unscaled, clipped gradient; skipped on the device when the record's overflow flag is set; the step count
+    of the bias corrections is the record's."""
+    hip.check(hip.lib().mudg_adamw_scaled_multi(table.data_ptr(), nchunks, lr, betas[0], betas[1], eps, weight_decay, record.data_ptr(),
+                                                stat.data_ptr(), _s()), "mudg_adamw_scaled_multi")
+
+
+def adamw_scaled_ema_multi_(table, nchunks, record, stat, *, lr, betas, eps, weight_decay, one_minus_decay):
+    """adamw_ema_multi_ under a loss scale: a skipped step still moves the shadow towards the unchanged parameter."""
+    hip.check(hip.lib().mudg_adamw_scaled_ema_multi(table.data_ptr(), nchunks, lr, betas[0], betas[1], eps, weight_decay, one_minus_decay,
+                                                    record.data_ptr(), stat.data_ptr(), _s()), "mudg_adamw_scaled_ema_multi")
+
+
+def loss_scale_update_(record, growth_factor, backoff_factor, growth_interval):
+    """torch's _amp_update_scale_ on the record, then taken += !overflow and the flag is cleared."""
+    hip.check(hip.lib().mudg_loss_scale_update(record.data_ptr(), growth_factor, backoff_factor, growth_interval, _s()), "mudg_loss_scale_update")
+
+
 def ema_multi_(table, nchunks, one_minus_decay):
     """shadow <- shadow - one_minus_decay * (shadow - param) over every tensor listed in `table` (rows: shadow, param, count)."""
     hip.check(hip.lib().mudg_ema_multi(table.data_ptr(), nchunks, one_minus_decay, _s()), "mudg_ema_multi")

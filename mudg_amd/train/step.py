@@ -9,6 +9,19 @@ from . import functions as F_
 from . import kernels as K
 
 
+def _logvar_on(model, dev):
+    """model.logvar — a plain tensor on the host, as in the reference — on the device: uploaded once (a blocking copy) and again only
+    when it was replaced or written, so that a step does not wait for the device."""
+    src = model.logvar
+    if src.device == dev:
+        return src
+    hit = model.__dict__.get("_mudg_logvar")
+    if hit is None or hit[0] is not src or hit[1] != src._version or hit[2].device != dev:
+        hit = (src, src._version, src.to(dev))
+        model.__dict__["_mudg_logvar"] = hit
+    return hit[2]
+
+
 def p_losses(model, x_start, cond, t, noise=None, **kwargs):
     """LatentDiffusion.p_losses: q_sample -> UNet (with an autograd graph) -> target by parameterisation -> per-sample MSE ->
     loss = l_simple_weight * mean(mse / exp(logvar_t) + logvar_t) + original_elbo_weight * mean(lvlb_weights[t] * mse).
@@ -38,7 +51,7 @@ def p_losses(model, x_start, cond, t, noise=None, **kwargs):
         raise NotImplementedError(model.parameterization)
     dev = x_start.device
     b = x_start.shape[0]
-    logvar_t = model.logvar.to(dev)[t].float()
+    logvar_t = _logvar_on(model, dev)[t].float()
     lvlb_t = model.lvlb_weights.to(dev)[t].float()
     # per-sample coefficients of the mse (host-sized vectors of B numbers, like the DDIM step's coefficients)
     w = (model.l_simple_weight / torch.exp(logvar_t) + model.original_elbo_weight * lvlb_t) / b
@@ -62,12 +75,45 @@ class AdamW(torch.optim.Optimizer):
     once per step; parameters the average does not track take the plain launch, tracked parameters the optimiser did not step
     (no gradient) get their shadow moved by mudg_ema_multi: after the call every shadow has had exactly LitEma.forward's update.
     The average names its parameters by identity (those of the model it was built on): an optimiser that holds none of them is an
-    error, not a silent plain step."""
+    error, not a silent plain step.
+
+    step(scaler=LossScaler): the launches become mudg_adamw_scaled_multi / mudg_adamw_scaled_ema_multi.  They consume the SCALED
+    gradient as (g * inv_scale) * clip coefficient (the coefficient of the scaler's norm pass, which must have run), skip the
+    update on the device when that pass found an overflow, and take their bias corrections from the scaler record's count of
+    steps actually taken: the host makes no decision that depends on the flag and never waits for it.  state["step"] then counts
+    ATTEMPTS; state_dict() reports the taken count (one device read there) and load_state_dict() restores it, so a resumed run
+    has the same bias corrections.  One count serves the whole optimiser: parameters at different step counts (the per-tensor
+    fallback) raise NotImplementedError under a scaler.  Version counters are bumped on a skipped step too (a spurious refresh of
+    a weight cache is harmless; not bumping would need the flag)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._tables = {}                                 # group index -> (key, device table, chunk count)
         self._ema_tables = {}                             # group index -> (key, fused table, count, plain table, count)
+        self._scaler = None                               # the LossScaler whose record holds this optimiser's taken-step count
+
+    def _bind(self, scaler):
+        """Before the first scaled launch (and again after load_state_dict): every stepped parameter must be at the same step
+        count, and that count — all of them taken, as far as the host knows — becomes the record's."""
+        seen = {self.state[p].get("step", 0) for group in self.param_groups for p in group["params"] if p.grad is not None}
+        if len(seen) > 1:
+            raise NotImplementedError("AdamW.step(scaler=...): the parameters are at different step counts "
+                                      f"({sorted(seen)[:4]}); the scaler record holds ONE count of taken steps for the bias "
+                                      "corrections, so the per-tensor fallback cannot run under a loss scale")
+        if seen and self._scaler is not scaler:
+            scaler._set_taken(seen.pop(), next(p for group in self.param_groups for p in group["params"]).device)
+            self._scaler = scaler
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self._scaler is not None:                      # attempts -> steps taken (a device read: checkpoints only)
+            taken = self._scaler.taken_steps()
+            sd["state"] = {k: (dict(st, step=taken) if "step" in st else st) for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._scaler = None                               # the next scaled step writes the loaded count into the record
 
     def _table_ema(self, gi, ps, shadows):
         """Two tables for a group stepped with an average: rows (p, g, m, v, shadow, count) for the tracked parameters and the
@@ -104,8 +150,10 @@ class AdamW(torch.optim.Optimizer):
         return table, len(rows)
 
     @torch.no_grad()
-    def step(self, closure=None, ema=None):
+    def step(self, closure=None, ema=None, scaler=None):
         loss = None
+        if scaler is not None and not scaler.enabled:
+            scaler = None
         shadows, omd, averaged = None, None, set()
         if ema is not None:
             shadows = ema.shadow_map()
@@ -115,6 +163,9 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if scaler is not None:
+            scaler._check_step(self)
+            self._bind(scaler)
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -139,16 +190,23 @@ class AdamW(torch.optim.Optimizer):
                 step = steps.pop()
                 if omd is None:                           # after every check that can raise: a failed step leaves num_updates alone
                     omd = ema.begin_update()
-                if nf:
+                if nf and scaler is not None:
+                    K.adamw_scaled_ema_multi_(fused, nf, scaler._rec, scaler._stat, one_minus_decay=omd, **hyper)
+                elif nf:
                     K.adamw_ema_multi_(fused, nf, step=step, one_minus_decay=omd, **hyper)
-                if npl:
+                if npl and scaler is not None:
+                    K.adamw_scaled_multi_(plain, npl, scaler._rec, scaler._stat, **hyper)
+                elif npl:
                     K.adamw_multi_(plain, npl, step=step, **hyper)
                 for p in tracked:
                     averaged.add(id(p))
                     torch.autograd.graph.increment_version(shadows[id(p)])
             elif len(steps) == 1:
                 table, n = self._table(gi, ps)
-                K.adamw_multi_(table, n, step=steps.pop(), **hyper)
+                if scaler is not None:
+                    K.adamw_scaled_multi_(table, n, scaler._rec, scaler._stat, **hyper)
+                else:
+                    K.adamw_multi_(table, n, step=steps.pop(), **hyper)
             else:                                         # parameters that joined the group at different times: one launch each
                 for p in ps:
                     st = self.state[p]
@@ -197,6 +255,150 @@ class GradientClipper:
         return out
 
 
+class LossScaler:
+    """torch.amp.GradScaler for the fp16 operand build, on the device from end to end (the reference trains with precision: 16,
+    i.e. a GradScaler with its defaults: scale 2^16, x2 every 2000 good steps, x0.5 and a skipped optimiser step on overflow).
+    Why: an output gradient below 2^-25 becomes an exact zero as an fp16 MFMA operand and everything upstream of it gets no
+    gradient; multiplied by the scale it is in range, and the optimiser divides the scale out again in fp32.
+
+    The state is ONE 16-byte device record — fp32 scale, int32 growth tracker, the overflow flag of the current step, an int32
+    count of steps actually taken — that only kernels read and write:
+        scale(loss)        loss * scale, a device multiply that autograd carries
+        norm_pass(...)     mudg_scaled_grad_norm: [norm of the UNSCALED gradients, clip coefficient] and the overflow flag (set
+                           iff any gradient is inf or NaN); no write pass, the gradients STAY SCALED in .grad
+        optimizer.step(scaler=self)   unscales, clips, skips and counts on the device (AdamW above)
+        update()           mudg_loss_scale_update: back off on overflow, grow after growth_interval good steps
+    unscale_(tensors) is an explicit extra launch for callers who want to LOOK at unscaled gradients (pass copies: the
+    optimiser unscales by itself and refuses gradients that were already unscaled).  get_scale(), state_dict() and
+    taken_steps() read the device and are for logging and checkpoints.  state_dict() / load_state_dict() use torch's keys, so a
+    scaler state out of a Lightning checkpoint loads here and one made here loads into torch.  enabled=False makes every method
+    the identity (and step(scaler=...) the plain step): one training script serves all builds.
+
+    Several ranks: the norm pass runs after the gradient all-reduce, and a non-finite value on any rank is non-finite in the
+    averaged bucket on every rank, so all ranks skip together without a collective of their own."""
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True):
+        if enabled and not (growth_factor > 1.0 and 0.0 < backoff_factor < 1.0 and growth_interval > 0 and init_scale > 0.0):
+            raise ValueError("LossScaler: growth_factor > 1, 0 < backoff_factor < 1, growth_interval > 0, init_scale > 0")
+        self.enabled = bool(enabled)
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._init_scale, self._init_tracker, self._init_taken = float(init_scale), 0, 0
+        self._rec, self._scale = None, None               # the record as int32 [4]; its first word as an fp32 scalar view
+        self._stat = None                                 # [norm, coefficient] of this step's norm pass
+        self._key, self._table, self._partial = None, None, None
+        self._unscaled = set()                            # addresses unscale_() has written since the last update()
+
+    def _record(self, device):
+        if self._rec is None:
+            host = torch.zeros(4, dtype=torch.int32)
+            host.view(torch.float32)[0] = self._init_scale
+            host[1], host[3] = self._init_tracker, self._init_taken
+            self._rec = host.to(device)
+            self._scale = self._rec.view(torch.float32)[0]
+        elif self._rec.device != torch.device(device):
+            raise RuntimeError(f"LossScaler: the record lives on {self._rec.device}, got a tensor on {device}")
+        return self._rec
+
+    def _set_taken(self, n, device):
+        self._record(device)[3].fill_(int(n))
+
+    def scale(self, loss):
+        if not self.enabled:
+            return loss
+        self._record(loss.device)
+        return loss * self._scale
+
+    def _chunks(self, tensors):
+        """(key, device table of (address, count) rows) over `tensors`."""
+        from .. import hip
+        for g in tensors:
+            if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+                raise RuntimeError("LossScaler works on contiguous fp32 gradients on the GPU")
+        key = tuple((g.data_ptr(), g.numel()) for g in tensors)
+        chunk = hip.lib().mudg_clip_chunk()
+        rows = [(ptr + 4 * off, min(chunk, n - off)) for ptr, n in key for off in range(0, n, chunk)]
+        return key, torch.tensor(rows, dtype=torch.int64).to(tensors[0].device)
+
+    @torch.no_grad()
+    def norm_pass(self, params, max_norm=None):
+        """The scaled norm pass over the gradients of `params` (after backward and the all-reduce, once per optimiser step).
+        Returns the device tensor [unscaled norm, clip coefficient]; max_norm None: the coefficient is 1.  The chunk table is
+        rebuilt only when a gradient tensor moved."""
+        if not self.enabled:
+            return None
+        grads = [p.grad for p in params if p.grad is not None]
+        if not grads:
+            return None
+        rec = self._record(grads[0].device)
+        key = tuple((g.data_ptr(), g.numel()) for g in grads)
+        if key != self._key:
+            _, self._table = self._chunks(grads)
+            self._partial = torch.empty(self._table.shape[0], dtype=torch.float64, device=grads[0].device)
+            self._key = key
+        if max_norm is not None and not max_norm > 0:
+            raise ValueError("LossScaler.norm_pass: max_norm must be positive (None: no clipping)")
+        self._stat = K.scaled_grad_norm(self._table, self._table.shape[0], self._partial, None if max_norm is None else float(max_norm), rec)
+        return self._stat
+
+    @torch.no_grad()
+    def unscale_(self, tensors):
+        """g <- g * float(1 / scale) in place on every tensor (or parameter's .grad) given: one extra launch, for inspection."""
+        if not self.enabled:
+            return
+        grads = [t.grad if isinstance(t, torch.nn.Parameter) else t for t in tensors]
+        grads = [g for g in grads if g is not None]
+        if not grads:
+            return
+        rec = self._record(grads[0].device)
+        _, table = self._chunks(grads)
+        K.unscale_multi_(table, table.shape[0], rec)
+        self._unscaled.update(g.data_ptr() for g in grads)
+
+    def _check_step(self, optimizer):
+        if self._stat is None:
+            raise RuntimeError("optimizer.step(scaler=...): run scaler.norm_pass(params, max_norm) after backward first — it finds "
+                               "the overflow flag and the clip coefficient the step reads")
+        if self._unscaled and any(p.grad is not None and p.grad.data_ptr() in self._unscaled
+                                  for group in optimizer.param_groups for p in group["params"]):
+            raise RuntimeError("optimizer.step(scaler=...): these gradients were already unscaled by scaler.unscale_(); the step "
+                               "unscales by itself — call unscale_ on copies")
+
+    def update(self):
+        """After optimizer.step(scaler=...): the scale for the next step, the taken-step count, the flag cleared."""
+        if not self.enabled or self._rec is None:
+            return
+        K.loss_scale_update_(self._rec, self.growth_factor, self.backoff_factor, self.growth_interval)
+        self._stat = None
+        self._unscaled.clear()
+
+    # ------------------------------------------------------------------ host reads: logging and checkpoints only
+    def get_scale(self):
+        if not self.enabled:
+            return 1.0
+        return self._init_scale if self._rec is None else float(self._scale)
+
+    def taken_steps(self):
+        return self._init_taken if self._rec is None else int(self._rec[3])
+
+    def state_dict(self):
+        if not self.enabled:
+            return {}
+        return {"scale": self.get_scale(), "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": self._init_tracker if self._rec is None else int(self._rec[1])}
+
+    def load_state_dict(self, state_dict):
+        if not self.enabled:
+            return
+        if len(state_dict) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of GradScaler.")
+        self.growth_factor, self.backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self.growth_interval = int(state_dict["growth_interval"])
+        self._init_scale, self._init_tracker = float(state_dict["scale"]), int(state_dict["_growth_tracker"])
+        if self._rec is not None:
+            self._rec.view(torch.float32)[0].fill_(self._init_scale)
+            self._rec[1].fill_(self._init_tracker)
+
+
 class GradientAllReducer:
     """Data-parallel gradient averaging: the gradients of `params` are packed into flat fp32 buckets of about `bucket_mb` MiB (one
     collective per bucket instead of one per tensor: xGMI rings are per-link bound, large messages amortise their latency),
@@ -210,7 +412,18 @@ class GradientAllReducer:
     did not complete by itself (a parameter that received no gradient contributes zeros — and holds back its bucket and the ones
     after it until then: the launch order is fixed), waits, and unpacks.  With gradient
     accumulation (the reference's trainer: accumulate_grad_batches 2) set `.sync = False` for all but the last micro-batch: the
-    hooks then do nothing and the gradients keep accumulating locally, as under DDP's no_sync."""
+    hooks then do nothing and the gradients keep accumulating locally, as under DDP's no_sync.
+
+    Accumulation under a LossScaler: the scale is constant over the window; the norm pass, the step and update() run once, after
+    the last micro-batch:
+        reducer.zero_grad()
+        for i, micro in enumerate(window):
+            reducer.sync = i == len(window) - 1
+            scaler.scale(loss_of(micro) / len(window)).backward()
+        reducer()                                         # the all-reduce; the overflow check comes AFTER it: every rank sees the
+        scaler.norm_pass(params, max_norm)                # same averaged buckets, so every rank skips or steps together
+        optimizer.step(ema=ema, scaler=scaler)
+        scaler.update()"""
 
     def __init__(self, params, bucket_mb=64, group=None, always=False, overlap=False):
         self.params = [p for p in params if p.requires_grad]
@@ -341,13 +554,21 @@ class GradientAllReducer:
         self._hooks = []
 
 
-def training_step(model, x_start, cond=None, t=None, optimizer=None, reducer=None, noise=None, clipper=None, ema=None, **kwargs):
+def training_step(model, x_start, cond=None, t=None, optimizer=None, reducer=None, noise=None, clipper=None, ema=None, scaler=None,
+                  **kwargs):
     """One optimisation step as the reference's trainer runs it: zero_grad -> p_losses -> backward -> (gradient all-reduce) ->
     (gradient-norm clipping) -> AdamW.  Returns (loss, loss_dict); with a clipper, loss_dict["grad_norm"] is the device scalar.
     `x_start` may instead be a DATA batch (a dict of pixels, caption, class label, frame rate: LatentVisualDiffusion.get_batch_input);
     the loss then comes from model.shared_step(batch, random_uncond=model.classifier_free_guidance), `cond` and `t` stay None.
     `ema` (a lvdm.ema.LitEma, e.g. model.model_ema): the averaged weights are updated inside the optimiser's launch — what
-    on_train_batch_end() does in a loop that does not pass it; pass it OR call on_train_batch_end(), not both."""
+    on_train_batch_end() does in a loop that does not pass it; pass it OR call on_train_batch_end(), not both.
+    `scaler` (a LossScaler; the reference's precision: 16): zero_grad -> loss -> scaler.scale(loss).backward() -> (all-reduce) -> the
+    scaled norm pass (it replaces the clipper's own: same max_norm, no write pass) -> optimizer.step(ema=..., scaler=scaler) ->
+    scaler.update().  loss_dict gains "loss_scale" (the scale this step ran at, a device scalar) and "grad_norm" is the norm of the
+    UNSCALED gradients; .grad is left scaled.  The returned loss is the unscaled one.  Without a scaler (or with a disabled one)
+    nothing changes: the same launches, the same bits."""
+    if scaler is not None and not scaler.enabled:
+        scaler = None
     if optimizer is None:
         raise TypeError("training_step needs the optimizer")
     if reducer is not None:
@@ -360,9 +581,21 @@ def training_step(model, x_start, cond=None, t=None, optimizer=None, reducer=Non
         loss, info = model.shared_step(x_start, random_uncond=model.classifier_free_guidance, **kwargs)
     else:
         loss, info = p_losses(model, x_start, cond, t, noise=noise, **kwargs)
-    loss.backward()
+    if scaler is not None:
+        scaler.scale(loss).backward()
+    else:
+        loss.backward()
     if reducer is not None:
         reducer()
+    if scaler is not None:
+        params = clipper.params if clipper is not None else [p for group in optimizer.param_groups for p in group["params"]]
+        stat = scaler.norm_pass(params, clipper.max_norm if clipper is not None else None)
+        info = dict(info, loss_scale=scaler._scale.clone())           # (update() below rewrites the record in place)
+        if stat is not None:
+            info["grad_norm"] = stat[0]
+        optimizer.step(ema=ema, scaler=scaler)
+        scaler.update()
+        return loss.detach(), info
     if clipper is not None:
         stat = clipper()
         if stat is not None:

@@ -13,6 +13,12 @@ clip, whatever is frozen.  After the timed steps one more step runs with the con
 the plain step of the same run, together with the achieved TB/s of mudg_ema_multi (3 x 4 bytes per parameter) and mudg_swap_multi
 (4 x 4 bytes per parameter) on their own (the launches on their prebuilt tables, 20 repeats between two events).
 
+`--scaler` (anywhere after the step count; meant for MUDG_OPERAND=fp16): after the plain steps, `steps` pairs of (plain step, step under a
+mudg_amd.train.step.LossScaler: scaled loss, the scaled norm pass, AdamW.step(scaler=...), update()) run alternating in the same process; both
+lists of seconds are reported with their spread (max - min).  The pairs share one optimiser, so the plain steps in between advance the host's
+step count only: a timing run, not a training run.  `--scaler=1` starts at scale 1 instead of 2^16: the same launches on the plain step's own
+gradient values, which separates what the launches cost from what the larger operand values cost.
+
 `python tools/train_bench.py --log-images [512|1024]`: one LatentVisualDiffusion.log_images call from a pixel batch (B = 1, 50 DDIM
 steps, guidance 7.5, the towers' stand-ins of --from-pixels) in seconds, after a 2-step warm-up call, next to 100 sampler steps of the
 same model in the same process (two 50-step sample_log runs on the conditioning log_images built).
@@ -180,11 +186,19 @@ torch.cuda.reset_peak_memory_stats()
 times, losses = [], []
 EMA = "--ema" in sys.argv[3:]
 ema = None                                   # set for the second block of steps
+SCALER = next((a for a in sys.argv[3:] if a == "--scaler" or a.startswith("--scaler=")), None)
+scaler = None                                # set for every other step of the --scaler block
 def one_step():
     opt.zero_grad(set_to_none=False)         # multi-tensor fill; gradient tensors (and the pointer tables built on them) persist
     for _ in range(ACC):
         loss = model.training_step(batch)
-        (loss / ACC).backward()
+        ((loss if scaler is None else scaler.scale(loss)) / ACC).backward()
+    if scaler is not None:
+        norm = scaler.norm_pass(clip.params if clip is not None else [p for g in opt.param_groups for p in g["params"]],
+                                clip.max_norm if clip is not None else None)
+        opt.step(ema=ema, scaler=scaler)
+        scaler.update()
+        return loss, norm
     norm = clip() if clip is not None else None
     if ema is not None:
         opt.step(ema=ema)
@@ -234,6 +248,25 @@ if EMA:
                   "ema_multi_ms": ema_ms, "ema_multi_tb_per_s": ema_tbs, "swap_multi_ms": round(swap_ms / 2, 3), "swap_multi_tb_per_s": swap_tbs}
     print("averaged weights:", ema_report, flush=True)
     ema = None
+scaler_report = None
+if SCALER:
+    the_scaler = step.LossScaler(**({"init_scale": float(SCALER.split("=")[1])} if "=" in SCALER else {}))
+    pair = {"plain": [], "scaled": []}
+    for i in range(steps + 1):                                         # pair 0 warms the scaled path up (record, chunk table) and is not reported
+        for name in ("plain", "scaled"):
+            scaler = the_scaler if name == "scaled" else None
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            loss, norm = one_step()
+            torch.cuda.synchronize()
+            if i:
+                pair[name].append(time.perf_counter() - t0)
+            print(f"pair {i} {name}: loss {float(loss.detach()):.5f}  {time.perf_counter() - t0:.3f} s", flush=True)
+    scaler = None
+    scaler_report = {"plain_s": [round(v, 4) for v in pair["plain"]], "scaled_s": [round(v, 4) for v in pair["scaled"]],
+                     "plain_spread_s": round(max(pair["plain"]) - min(pair["plain"]), 4), "scaled_spread_s": round(max(pair["scaled"]) - min(pair["scaled"]), 4),
+                     "scaled_minus_plain_median_s": round(sorted(pair["scaled"])[len(pair["scaled"]) // 2] - sorted(pair["plain"])[len(pair["plain"]) // 2], 4),
+                     "loss_scale": the_scaler.get_scale(), "optimizer_steps_taken": the_scaler.taken_steps(), "operand": __import__("mudg_amd.hip").hip.operand_name()}
+    print("loss scaling:", scaler_report, flush=True)
 from mudg_amd import hip
 hip.prof_reset(); hip.prof_enable((1 << len(hip.FAM_NAMES)) - 1)
 one_step()
@@ -253,7 +286,7 @@ if "json" in sys.argv[3:]:
     print(json.dumps({"workload": f"MDM{res} training step: p_losses -> backward -> AdamW, full 1.44 B-parameter UNet, B = {B}, 16 frames"
                                   + (f", {ACC} micro-batches per optimiser step" if ACC > 1 else ""),
                       "s_per_step": round(best, 4), "steps": steps, "tflops_per_s": round(fl / best, 1), "tflop_per_step": round(fl, 1),
-                      "flop_accounting": "3 x the forward per clip", "batch": B, "accumulate": ACC, "roofline": roof, "checkpointing": ckpt, "stage2_settings": stage2, **({"averaged_weights": ema_report} if ema_report else {}),
+                      "flop_accounting": "3 x the forward per clip", "batch": B, "accumulate": ACC, "roofline": roof, "checkpointing": ckpt, "stage2_settings": stage2, **({"averaged_weights": ema_report} if ema_report else {}), **({"loss_scaling": scaler_report} if scaler_report else {}),
                       "peak_memory_gib": round(torch.cuda.max_memory_allocated() / 2**30, 1), "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)]}))
     sys.exit(0)
 print(f"MDM{res} training step (B = {B}" + (f" x {ACC} micro-batches" if ACC > 1 else "") + f", 16 frames, checkpointing {'on' if ckpt else 'off'}{', stage-2 settings' if stage2 else ''}): {best:.2f} s = {fl / best:.1f} TFLOP/s of the "
