@@ -453,6 +453,33 @@ int mudg_dense_stream(int kind, const void* src, int T, int H0, int W0, int H, i
                       const float* norm, float* dst, int64_t stream_stride, int64_t channel_stride, int64_t frame_stride, int slab,
                       int frame0, uint8_t* u8_out, void* stream);
 
+/* ------------------------------------------------------------------ surface normals (csrc/normals.hip)
+ * The fourth dense modality (lvdm/data/waymo_data.py:194-265, class_label 1000): made from depth, resized into clips, scored.  Every
+ * floating-point operation is a single correctly rounded one in the stated order and every sum an integer: results are bit-equal to
+ * tests/normals_reference.py and between runs.  OpenCV camera: x right, y down, z forward.
+ *
+ * depth_normals: depth (frames, H, W) fp32 metres, table[frame][4] doubles = fx, fy, cx, cy at (H, W).  Pixel (row j, column i) with
+ *   depth z is usable iff min_depth < z < max_depth and its label is not sky_label (labels NULL: no sky rule); its point is
+ *   P = (xn z, yn z, z), xn = ((i + 0.5) - cx) / fx, yn likewise, in fp64.  A neighbour counts iff it is in the frame and usable and, with
+ *   max_rel_step = r >= 0, |z_nb - z| <= r z (r < 0: no such test).  dx = P(i+1) - P(i-1) when both horizontal neighbours count, the
+ *   difference with P(i) when one does, else none; dy the same along j.  n = dy x dx (a surface seen from the origin has n . P < 0, a
+ *   wall facing the camera (0, 0, -1); no flip), len = sqrt((nx nx + ny ny) + nz nz), normals[frame][j][i] = fp32(n / len) and
+ *   valid[frame][j][i] = 1; a pixel that is not usable, lacks dx or dy, or has len 0 or not finite stores (0, 0, 0) and 0.
+ *   0 <= min_depth < max_depth.
+ * normal_stream: src (T, H0, W0, 3) fp32 -> three fp32 planes per frame, placed as dense_stream places them: resize_f32's rule on every
+ *   channel with the same tables, no normalisation and no renormalisation to unit length (the maps are "already in [-1, 1]").
+ * metric_normals: pred_u8 (frames, H, W, 3) bytes u of a generated stream, gt (frames, H, W, 3) fp32, valid (frames, H, W) bytes or NULL.
+ *   p = 2 u - 255 (integers), dot = (p0 g0 + p1 g1) + p2 g2, gg = (g0 g0 + g1 g1) + g2 g2, c = dot / sqrt(double(p . p) gg) in fp64,
+ *   clamped to [-1, 1].  A pixel counts iff its validity byte is nonzero, 0 < gg < inf and c is a number; it adds one to
+ *   hist[frame][k] (int64, 720 bins of a quarter degree; the caller zeroes them) with cosines[k + 1] < c <= cosines[k], c = -1 in bin
+ *   719.  cosines: the caller's 721 doubles cos(k / 4 degrees), descending from 1 to -1.  Integer LDS and 64-bit global atomics only. */
+int mudg_depth_normals(const float* depth, const int64_t* labels, int64_t sky_label, const double* table, int frames, int H, int W,
+                       double min_depth, double max_depth, double max_rel_step, float* normals, uint8_t* valid, void* stream);
+int mudg_normal_stream(const float* src, int T, int H0, int W0, int H, int W, const int32_t* xtab, const int32_t* ytab, float* dst,
+                       int64_t stream_stride, int64_t channel_stride, int64_t frame_stride, int slab, int frame0, void* stream);
+int mudg_metric_normals(const uint8_t* pred_u8, const float* gt, const uint8_t* valid, const double* cosines, int frames, int H, int W,
+                        int64_t* hist, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

@@ -11,17 +11,14 @@
 // output depends on the order of execution, and all of them are bit-equal to the numpy definition in tests/depth_reference.py.
 // PX = 4: a lane owns four consecutive pixels of a row — 12 bytes of uint8 frame, one 16-byte fp32 access; PX = 1 (W % 4 != 0 or
 // unaligned bases): one pixel per lane.  Per-frame tables are indexed by blockIdx.y alone: uniform addresses, scalar loads.
-#include "common.h"
+#include "depth_shared.h"
 
 namespace {
 
 constexpr double Q_SCALE = 1048576.0;          // LiDAR depths are summed on a 2^-20 m grid
 constexpr double K_FULL = 765.0;               // r + g + b of a white pixel: the stream's depth is k / 765
-constexpr int MAX_PIXELS = 1 << 24;            // per frame: keeps sum(k q) below 2^62
 constexpr int SUMS = 5;                        // n, sum k, sum k^2, sum q, sum k q
 constexpr int TABLE_DOUBLES = 16;              // c2w[12], fx, fy, cx, cy
-
-struct u32x3 { uint32_t x, y, z; };
 
 // matplotlib's Spectral, eleven triples (eval_tools.py:170-182), rounded to fp32
 __constant__ float SPECTRAL[11][3] = {{0.61960784313725492f, 0.003921568627450980f, 0.25882352941176473f},
@@ -60,32 +57,6 @@ __device__ __forceinline__ void load_k(const uint8_t* __restrict__ src, int (&k)
         for (int e = 0; e < PX; ++e) k[e] = (int)(b[3 * e] + b[3 * e + 1] + b[3 * e + 2]);
     } else {
         k[0] = (int)src[0] + (int)src[1] + (int)src[2];
-    }
-}
-
-template <int PX>
-__device__ __forceinline__ void load_f32(const float* __restrict__ src, float (&v)[PX]) {
-    if (PX == 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(src);
-#pragma unroll
-        for (int e = 0; e < PX; ++e) v[e] = t[e];
-    } else {
-        v[0] = src[0];
-    }
-}
-
-template <int PX>
-__device__ __forceinline__ void load_sky(const int64_t* __restrict__ labels, int64_t at, long long sky_label, bool (&sky)[PX]) {
-#pragma unroll
-    for (int e = 0; e < PX; ++e) sky[e] = false;
-    if (!labels) return;
-    if (PX == 4) {
-        const u32x4 a = ld16(labels + at), b = ld16(labels + at + 2);
-        const uint32_t lo = (uint32_t)sky_label, hi = (uint32_t)((unsigned long long)sky_label >> 32);
-        sky[0] = a.x == lo && a.y == hi; sky[1] = a.z == lo && a.w == hi;
-        sky[2] = b.x == lo && b.y == hi; sky[3] = b.z == lo && b.w == hi;
-    } else {
-        sky[0] = labels[at] == sky_label;
     }
 }
 
@@ -270,10 +241,6 @@ __global__ __launch_bounds__(256) void depth_unproject_kernel(const float* __res
     if (PX == 4) *reinterpret_cast<uint32_t*>(valid + at) = ok[0] | (ok[1] << 8) | (ok[2] << 16) | (ok[3] << 24);
     else valid[at] = (uint8_t)ok[0];
 }
-
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-inline bool shape_ok(int frames, int H, int W) { return frames > 0 && frames <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= MAX_PIXELS; }
-inline dim3 frame_grid(int frames, int hw, int px) { return dim3((unsigned)((hw / px + 255) / 256), (unsigned)frames); }
 
 }  // namespace
 

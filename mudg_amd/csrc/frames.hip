@@ -9,7 +9,7 @@
 // aligned bases, 16-byte stores of the fp32 planes (12 / 4-byte stores of the bytes); otherwise one bounds-checked store per value.
 // Every floating-point operation is a single correctly rounded one in a stated order and the 8-bit rule is integer: results are bit-equal
 // to tests/frames_reference.py and between runs.  No MFMA operand is touched: the same code in every library build.
-#include "common.h"
+#include "frames_shared.h"
 
 namespace {
 
@@ -23,9 +23,6 @@ __constant__ int PAL21[PAL_COLOURS + 1][3] = {{255, 120, 50}, {255, 192, 203}, {
                                               {255, 0, 0}, {255, 240, 150}, {135, 60, 0}, {160, 32, 240}, {255, 0, 255}, {139, 137, 137},
                                               {75, 0, 75}, {150, 240, 80}, {230, 230, 250}, {0, 175, 0}, {0, 255, 127}, {222, 155, 161},
                                               {140, 62, 69}, {227, 164, 30}, {0, 128, 0}, {0, 0, 0}};
-
-// One output sample of an axis: the two source indices and their coefficients — int32 (8-bit rule, sum 2048) or fp32 bits (fp32 rule)
-struct Tap { int s0, s1, c0, c1; };
 
 enum { OP_U8_LINEAR = 0, OP_U8_NEAREST = 1, OP_F32 = 2, OP_STREAM_U8 = 3, OP_STREAM_DEPTH = 4 };
 
@@ -43,8 +40,6 @@ struct FramesArgs {
 
 struct u32x3 { uint32_t x, y, z; };
 
-__device__ __forceinline__ int inside(int s, int n) { return min(max(s, 0), n - 1); }     // a table cannot send a load out of the source
-
 // the C values (three with the palette) of source pixel x of a row
 __device__ __forceinline__ void load_px(const uint8_t* __restrict__ row, int x, int CS, int palette, int (&p)[3]) {
     if (palette) {
@@ -61,13 +56,6 @@ __device__ __forceinline__ void load_px(const uint8_t* __restrict__ row, int x, 
 __device__ __forceinline__ int linear_u8(int s00, int s01, int s10, int s11, const Tap& tx, const Tap& ty) {
     const int r0 = s00 * tx.c0 + s01 * tx.c1, r1 = s10 * tx.c0 + s11 * tx.c1;
     return (((ty.c0 * (r0 >> 4)) >> 16) + ((ty.c1 * (r1 >> 4)) >> 16) + 2) >> 2;
-}
-
-__device__ __forceinline__ float linear_f32(float s00, float s01, float s10, float s11, const Tap& tx, const Tap& ty) {
-    const float w0 = __int_as_float(tx.c0), w1 = __int_as_float(tx.c1), v0 = __int_as_float(ty.c0), v1 = __int_as_float(ty.c1);
-    const float r0 = __fadd_rn(__fmul_rn(s00, w0), __fmul_rn(s01, w1));
-    const float r1 = __fadd_rn(__fmul_rn(s10, w0), __fmul_rn(s11, w1));
-    return __fadd_rn(__fmul_rn(r0, v0), __fmul_rn(r1, v1));
 }
 
 // clamp(0, 100) / 100, - 0.5, * 2 (waymo_data.py:328-329); a NaN stays one, as in torch.clamp
@@ -188,11 +176,6 @@ int launch(const FramesArgs& a, int T, bool wide, void* stream, const char* what
 bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 }  // namespace
-
-#define FRAMES_REQUIRE_SIZES(name)                                                                                                      \
-    MUDG_REQUIRE(T > 0 && T <= 65535 && H > 0 && H <= 65535 && W > 0 && H0 > 0 && W0 > 0,                                               \
-                 name ": %d frames of %d x %d to %d x %d (every size positive, at most 65535 frames and output rows)", T, H0, W0, H, W); \
-    MUDG_REQUIRE((int64_t)H0 * W0 <= (1 << 28) && (int64_t)H * W <= (1 << 28), name ": a frame of more than 2^28 pixels")
 
 extern "C" int mudg_resize_u8(const uint8_t* src, uint8_t* dst, int T, int H0, int W0, int C, int H, int W, int mode, int palette,
                               const int32_t* xtab, const int32_t* ytab, void* stream) {

@@ -58,6 +58,27 @@ def camera_table(intr, c2w, hw_native, hw_out):
     return np.stack([np.concatenate([c2w[t, :3].reshape(12), render.scaled_intrinsics(intr[t], hw_native, hw_out)]) for t in range(c2w.shape[0])])
 
 
+def normals_from_depth(depth, intr, hw_native, labels=None, *, sky_label=SKY_LABEL, min_depth=0.0, max_depth=MAX_DEPTH, max_rel_step=None):
+    """Camera-space surface normals of depth maps (OpenCV camera: x right, y down, z forward).  depth: (F, H, W) fp32
+    metres (metric_depth's, or a dense depth map); intr: (3, 3) or (F, 3, 3) at hw_native; labels: (F, H, W) int64 or None.  A pixel is
+    usable iff min_depth < depth < max_depth and it is not sky; the normal is dy x dx over central differences of the unprojected points,
+    one-sided where only one neighbour is usable — and, with max_rel_step = r, only where |z_nb - z| <= r z, so that a depth edge takes
+    the side that lies on the surface.  A surface seen from the camera has n . P < 0 (a wall facing it: (0, 0, -1)); no flip is applied.
+    Returns (normals (F, H, W, 3) fp32 of unit length, valid (F, H, W) uint8); a pixel that is not valid holds (0, 0, 0)."""
+    depth = _on_gpu("normals_from_depth", "the depth", depth, torch.float32)
+    if depth.dim() != 3:
+        raise hip.MudgError(f"normals_from_depth: expected (F, H, W) depths, got {tuple(depth.shape)}")
+    if labels is not None:
+        labels = _on_gpu("normals_from_depth", "the label image", labels, torch.int64, depth.shape)
+    intr = np.asarray(intr, dtype=np.float64)
+    if intr.shape not in ((3, 3), (depth.shape[0], 3, 3)):
+        raise hip.MudgError(f"normals_from_depth: intrinsics {intr.shape} for {depth.shape[0]} frames, expected (3, 3) or (F, 3, 3)")
+    intr = np.broadcast_to(intr, (depth.shape[0], 3, 3))
+    table = np.stack([render.scaled_intrinsics(k, hw_native, depth.shape[1:]) for k in intr])
+    return ops.depth_normals(depth, torch.from_numpy(table).to(depth.device), labels, sky_label=sky_label, min_depth=min_depth,
+                             max_depth=max_depth, max_rel_step=max_rel_step)
+
+
 def lift_views(depth, rgb, intr, c2w, hw_native, labels=None, *, min_depth=0.0, max_depth=MAX_DEPTH, sky_label=SKY_LABEL):
     """Generated views as coloured world-space points in the renderer's packed format.  depth: (T, H, W) fp32 metres; rgb: (T, H, W, 3)
     uint8; intr: (3, 3) or (T, 3, 3) at hw_native; c2w: (T, 4, 4), the poses the views were generated at (OpenCV convention);

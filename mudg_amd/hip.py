@@ -177,6 +177,9 @@ SIGNATURES = {
     "mudg_resize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mudg_resize_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mudg_dense_stream": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P]),
+    "mudg_depth_normals": (_I, [_P, _P, _L, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P]),
+    "mudg_normal_stream": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _I, _I, _P]),
+    "mudg_metric_normals": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "mudg_short_attention_ok": (_I, [C.POINTER(ShortAttnDesc)]),
     "mudg_short_attention": (_I, [C.POINTER(ShortAttnDesc), _P]),
     "mudg_layernorm_f32": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P]),

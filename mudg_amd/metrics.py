@@ -1,5 +1,5 @@
 """Scores of generated views against the truths that are already on the GPU: PSNR and SSIM for colour, depth errors against the rendered
-LiDAR depth, class IoU for the semantic stream.
+LiDAR depth, class IoU for the semantic stream, angular errors for the normal stream.
 
 The reference has no scoring code (its eval_tools.py writes files, its validation_step logs the loss); its paper reports these
 numbers.  The rules here are this project's own and DESIGN.md §15 states them: every kernel of csrc/metrics.hip reduces a frame to a
@@ -71,6 +71,30 @@ def segmentation_scores(pred_labels, gt_labels, *, classes=CLASSES):
     defined = ~torch.isnan(iou)
     miou = torch.where(defined, iou, torch.zeros_like(iou)).sum(1) / defined.sum(1).to(_D)
     return {"confusion": confusion, "iou": iou, "miou": miou, "pixel_acc": diag.sum(1) / (c.sum((1, 2)) + bad.to(_D)), "bad": bad}
+
+
+def normal_errors(pred_u8, gt_normals, valid=None):
+    """pred_u8: (F, H, W, 3) uint8, a generated normal stream as ops.frames_to_uint8 returns it; gt_normals: (F, H, W, 3) fp32
+    (normals_from_depth's, or loaded maps); valid: (F, H, W) uint8 or None.  The angle between 2 u - 255 and the truth, binned per frame
+    into quarter degrees by its cosine, over the pixels whose validity byte is nonzero and whose truth has a finite
+    positive length.  Per frame: {"n" (int64), "mean" (over bin centres: within 0.125 degrees of the mean angle), "median" (the centre of
+    the bin that holds the lower median), "a11", "a22", "a30" (the shares below 11.25, 22.5 and 30 degrees, which are bin edges: exact),
+    "hist": (F, 720) int64}, degrees in float64; a frame with nothing counted scores nan."""
+    pred = _on_gpu("normal_errors", "the normal stream", pred_u8, torch.uint8)
+    if pred.dim() != 4 or pred.shape[3] != 3:
+        raise hip.MudgError(f"normal_errors: expected (F, H, W, 3) frames, got {tuple(pred.shape)}")
+    gt = _on_gpu("normal_errors", "the true normals", gt_normals, torch.float32, pred.shape)
+    if valid is not None:
+        valid = _on_gpu("normal_errors", "the validity bytes", valid, torch.uint8, pred.shape[:3])
+    hist = ops.metric_normals(pred, gt, valid)
+    below = hist.cumsum(1)                                                   # integers: the pixels of bins 0 .. k
+    counted = below[:, -1]
+    n = counted.to(_D)                                                       # 0 / 0 = nan: a frame with nothing counted
+    odd = 2 * torch.arange(ops.NORMAL_BINS, device=hist.device) + 1         # bin k's centre is (2 k + 1) / 8 degrees
+    middle = (2 * below >= counted[:, None]).to(torch.uint8).argmax(1)      # the first bin at which half the pixels are reached
+    nan = torch.full_like(n, float("nan"))
+    return {"n": counted, "mean": (hist * odd).sum(1).to(_D) / (8.0 * n), "median": torch.where(counted > 0, (2 * middle + 1).to(_D) / 8.0, nan),
+            "a11": below[:, 44].to(_D) / n, "a22": below[:, 89].to(_D) / n, "a30": below[:, 119].to(_D) / n, "hist": hist}
 
 
 def score_window(outputs, *, color=None, lidar_depth=None, labels=None, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH, classes=CLASSES):

@@ -1072,6 +1072,20 @@ def resize_f32(src, hw_out):
     return out
 
 
+def _stream_out(name, out, device, t, h, w, slab, frame0):
+    """Where a stream of t frames goes: a new (3, t, h, w) tensor, or the caller's `out` checked against stream `slab`, frames frame0 ..."""
+    slab, frame0 = int(slab), int(frame0)
+    if out is None:
+        out = torch.empty((3, t, h, w), dtype=torch.float32, device=device)
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != device or out.dim() not in (4, 5):
+        raise hip.MudgError(f"{name}: out is a (3, frames, h, w) or (streams, 3, frames, h, w) fp32 tensor on the source's device")
+    slabs = out.shape[0] if out.dim() == 5 else 1
+    if (tuple(out.shape[-4:-2]) != (3, out.shape[-3]) or tuple(out.shape[-2:]) != (h, w) or out.stride(-1) != 1 or out.stride(-2) != w
+            or not (0 <= slab < slabs and 0 <= frame0 and frame0 + t <= out.shape[-3]) or out.stride(-3) < h * w or out.stride(-4) <= 0):
+        raise hip.MudgError(f"{name}: {t} frames of {h} x {w} at stream {slab}, frame {frame0} of out {tuple(out.shape)} strides {out.stride()}")
+    return out, slab, frame0
+
+
 def dense_stream(kind, src, hw_out, out=None, *, slab=0, frame0=0, return_u8=False):
     """One dense stream of a clip (DESIGN.md §16).  kind "color": src (T, H0, W0, 3) uint8; "semantic": (T, H0, W0) uint8 class ids;
     "depth": (T, H0, W0) fp32 metres.  Writes (3, T, h, w) fp32 in [-1, 1]: into a new tensor, or into `out` — (3, T', h, w), or
@@ -1086,15 +1100,7 @@ def dense_stream(kind, src, hw_out, out=None, *, slab=0, frame0=0, return_u8=Fal
         raise hip.MudgError("dense_stream: the depth stream has no uint8 frames")
     h, w = _hw_out("dense_stream", hw_out)
     t, h0, w0 = src.shape[:3]
-    slab, frame0 = int(slab), int(frame0)
-    if out is None:
-        out = torch.empty((3, t, h, w), dtype=torch.float32, device=src.device)
-    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != src.device or out.dim() not in (4, 5):
-        raise hip.MudgError("dense_stream: out is a (3, frames, h, w) or (streams, 3, frames, h, w) fp32 tensor on the source's device")
-    slabs = out.shape[0] if out.dim() == 5 else 1
-    if (tuple(out.shape[-4:-2]) != (3, out.shape[-3]) or tuple(out.shape[-2:]) != (h, w) or out.stride(-1) != 1 or out.stride(-2) != w
-            or not (0 <= slab < slabs and 0 <= frame0 and frame0 + t <= out.shape[-3]) or out.stride(-3) < h * w or out.stride(-4) <= 0):
-        raise hip.MudgError(f"dense_stream: {t} frames of {h} x {w} at stream {slab}, frame {frame0} of out {tuple(out.shape)} strides {out.stride()}")
+    out, slab, frame0 = _stream_out("dense_stream", out, src.device, t, h, w, slab, frame0)
     ytab, xtab = _resize_tables((h0, w0), (h, w), "linear_f32" if kind == "depth" else "linear_u8", src.device)
     norm = None if kind == "depth" else norm_table(src.device)
     u8 = torch.empty((t, h, w, 3), dtype=torch.uint8, device=src.device) if return_u8 else None
@@ -1102,6 +1108,75 @@ def dense_stream(kind, src, hw_out, out=None, *, slab=0, frame0=0, return_u8=Fal
                                           out.data_ptr(), out.stride(0) if out.dim() == 5 else 0, out.stride(-4), out.stride(-3), slab, frame0,
                                           _ptr(u8), _stream()), "mudg_dense_stream")
     return (out, u8) if return_u8 else out
+
+
+# ------------------------------------------------------------------------------------------------ surface normals
+NORMAL_BINS = 720                                               # mudg_metric_normals: quarter degrees of [0, 180]
+_COS_TABLES = {}
+
+
+def depth_normals(depth, table, labels=None, *, sky_label=10, min_depth=0.0, max_depth=100.0, max_rel_step=None):
+    """depth (f, h, w) fp32 metres and table (f, 4) float64 (fx, fy, cx, cy at (h, w)) -> camera-space unit normals (f, h, w, 3) fp32 and
+    valid (f, h, w) uint8.  A pixel is usable iff min_depth < depth < max_depth and its label is not sky_label; the normal is dy x dx over
+    central (or one-sided) differences of the unprojected points of usable neighbours, under max_rel_step = r also |z_nb - z| <= r z.
+    What is not valid stores (0, 0, 0) and 0."""
+    _splat_tensor("depth_normals: depth", depth, torch.float32)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise hip.MudgError(f"depth_normals: expected (frames, h, w) depths, got {tuple(depth.shape)}")
+    f, h, w = depth.shape
+    _splat_tensor("depth_normals: table", table, torch.float64, (f, 4))
+    if labels is not None:
+        _splat_tensor("depth_normals: labels", labels, torch.int64, (f, h, w))
+    step = -1.0 if max_rel_step is None else float(max_rel_step)
+    if max_rel_step is not None and not step >= 0.0:
+        raise hip.MudgError(f"depth_normals: max_rel_step {max_rel_step} (None, or a number that is not negative)")
+    normals = torch.empty((f, h, w, 3), dtype=torch.float32, device=depth.device)
+    valid = torch.empty((f, h, w), dtype=torch.uint8, device=depth.device)
+    hip.check(hip.lib().mudg_depth_normals(depth.data_ptr(), _ptr(labels), int(sky_label), table.data_ptr(), f, h, w, float(min_depth),
+                                           float(max_depth), step, normals.data_ptr(), valid.data_ptr(), _stream()), "mudg_depth_normals")
+    return normals, valid
+
+
+def normal_stream(src, hw_out, out=None, *, slab=0, frame0=0):
+    """(T, H0, W0, 3) fp32 normal maps -> the normal stream (3, T, h, w): the fp32 linear rule on every channel, nothing else (the maps
+    are already in [-1, 1]; a NaN stays one).  out / slab / frame0 place it as dense_stream does."""
+    _splat_tensor("normal_stream: the source", src, torch.float32)
+    if src.dim() != 4 or src.shape[3] != 3 or src.numel() == 0:
+        raise hip.MudgError(f"normal_stream: a source is (frames, H, W, 3), got {tuple(src.shape)}")
+    h, w = _hw_out("normal_stream", hw_out)
+    t, h0, w0 = src.shape[:3]
+    out, slab, frame0 = _stream_out("normal_stream", out, src.device, t, h, w, slab, frame0)
+    ytab, xtab = _resize_tables((h0, w0), (h, w), "linear_f32", src.device)
+    hip.check(hip.lib().mudg_normal_stream(src.data_ptr(), t, h0, w0, h, w, xtab.data_ptr(), ytab.data_ptr(), out.data_ptr(),
+                                           out.stride(0) if out.dim() == 5 else 0, out.stride(-4), out.stride(-3), slab, frame0, _stream()),
+              "mudg_normal_stream")
+    return out
+
+
+def normal_cos_table():
+    """Host, float64: T[k] = cos((k * 0.25) * (pi / 180)), k = 0 .. 720, the bin edges of mudg_metric_normals as cosines: strictly
+    descending from 1 to -1."""
+    import numpy as np
+    table = np.cos((np.arange(NORMAL_BINS + 1, dtype=np.float64) * 0.25) * (np.pi / 180.0))
+    if table[0] != 1.0 or table[-1] != -1.0 or not np.all(np.diff(table) < 0):
+        raise hip.MudgError("normal_cos_table: the cosines do not descend from 1 to -1")
+    return table
+
+
+def metric_normals(pred, gt, valid=None):
+    """pred (f, h, w, 3) uint8, gt (f, h, w, 3) fp32, valid (f, h, w) uint8 or None -> (f, 720) int64: per frame the counts of the angle
+    between 2 pred - 255 and gt in quarter-degree bins, over the pixels whose validity byte is nonzero and whose gt has a finite
+    positive length."""
+    f, h, w = _depth_frames("metric_normals", pred)
+    _splat_tensor("metric_normals: gt", gt, torch.float32, (f, h, w, 3))
+    if valid is not None:
+        _splat_tensor("metric_normals: valid", valid, torch.uint8, (f, h, w))
+    if pred.device not in _COS_TABLES:
+        _COS_TABLES[pred.device] = torch.from_numpy(normal_cos_table()).to(pred.device)
+    hist = torch.zeros((f, NORMAL_BINS), dtype=torch.int64, device=pred.device)
+    hip.check(hip.lib().mudg_metric_normals(pred.data_ptr(), gt.data_ptr(), _ptr(valid), _COS_TABLES[pred.device].data_ptr(), f, h, w,
+                                            hist.data_ptr(), _stream()), "mudg_metric_normals")
+    return hist
 
 
 # ------------------------------------------------------------------------------------------------ the CLIP image tower (DESIGN.md §17)
