@@ -480,6 +480,41 @@ int mudg_normal_stream(const float* src, int T, int H0, int W0, int H, int W, co
 int mudg_metric_normals(const uint8_t* pred_u8, const float* gt, const uint8_t* valid, const double* cosines, int frames, int H, int W,
                         int64_t* hist, void* stream);
 
+/* ------------------------------------------------------------------ LiDAR depth maps and dense completion (csrc/lidar_depth.hip)
+ * The reference's "six_frames_depth" (data_process/pipeline_depth.py:63-152) without Open3D, and the dense depth labels without a learned
+ * model.  Results are bit-equal to tests/lidar_depth_reference.py and between runs: the depth test is a 64-bit integer minimum, every
+ * other store is a plain one.
+ *
+ * lidar_splat_visible: the candidates are `nseg` (1 .. 8) runs of a cloud of 16-byte points, segments[2 s] the first point and
+ *   segments[2 s + 1] > 0 the length of run s (host memory, read before the call returns).  Each goes through mats[nmat][12] (one pose;
+ *   ids as in splat_points, read at the point's place in the cloud) and §12's projection, culling and cover at point_size.  With
+ *   occluder_keys (a key image drawn by splat_points from the same candidates, or NULL: no test): home = (floor(v), floor(u)),
+ *   near(q) iff q is in the image, its occluder key is not all ones and its depth < fmul(zc, rel_keep), rel_keep = fp32(1 - rel_tol);
+ *   the point is hidden iff for one of the directions (0,1), (1,0), (1,1), (1,-1) some pixel home + k d and some pixel home - k' d,
+ *   k, k' in 1 .. reach (<= 16), are near.  A hidden point writes nothing; every other one takes the unsigned 64-bit minimum of
+ *   (bits(zc) << 32 | index_base + candidate number) in keys[H][W] over its cover.
+ * lidar_depth_resolve: depth = the key's high word as fp32, 0 where the key is all ones; keys, and occluder_keys unless NULL, are
+ *   all ones afterwards.
+ * depth_complete: depth (frames, H, W) fp32 metres -> out, the same shape.  M = max_depth; a value is empty iff it is < 0.1f.
+ *   1  x = M - d where d > 0.1f, else 0; a result that is empty (d within 0.1 of M or beyond, not a number) is 0
+ *   2  x = max over the 13 pixels |dj| + |di| <= 2        3  x = max over 5 x 5, then x = min over 5 x 5 (outside the image: empty
+ *   for the maxima, absent from the minimum)               4  empty pixels = max over 7 x 7
+ *   5  (extrapolate != 0) per column, the rows above the first filled one take its value; then empty pixels = max over 31 x 31
+ *   6  x = the 13th smallest of the 5 x 5, border replicated
+ *   7  filled pixels = sum(w x) / sum(w) over the filled pixels of the 5 x 5 in the image, w = outer(1 4 6 4 1), exact fp64 sums,
+ *      one fp64 division rounded to fp32                   8  out = M - x where filled, else 0
+ *   9  labels (frames, H, W) int64 or NULL: out = M where the label is sky_label
+ *   source (frames, H, W) bytes or NULL: 4 sky, else 0 where out is empty, else 1 filled after step 1, 2 after step 4, 3 later.
+ *   scratch: depth_complete_scratch's bytes (-1: bad shape), 16-byte aligned.  1 .. 65535 frames and rows, H W <= 2^24,
+ *   0.1 < max_depth <= 65536. */
+int mudg_lidar_splat_visible(const void* points, const int32_t* ids, const int64_t* segments, int nseg, const float* mats, int nmat,
+                             const uint64_t* occluder_keys, uint64_t* keys, int H, int W, float fx, float fy, float cx, float cy,
+                             float znear, float zfar, float point_size, int reach, float rel_keep, int64_t index_base, void* stream);
+int mudg_lidar_depth_resolve(uint64_t* keys, uint64_t* occluder_keys, float* depth, int64_t pixels, void* stream);
+int64_t mudg_depth_complete_scratch(int frames, int H, int W);
+int mudg_depth_complete(const float* depth, const int64_t* labels, int64_t sky_label, int frames, int H, int W, float max_depth,
+                        int extrapolate, float* out, uint8_t* source, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

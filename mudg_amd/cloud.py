@@ -171,19 +171,55 @@ def build_scene_clouds(scenario, load_lidar, load_image, *, frames=None, cameras
 
     Objects first, with the moving Vehicle / Pedestrian objects; one with fewer than 100 points is dropped, and the background is
     what no surviving object's box holds.  A point in two boxes belongs to the lower-numbered object (a stated deviation)."""
+    return _build_scene(scenario, load_lidar, load_image, frames=frames, cameras=cameras, voxel_size=voxel_size, object_voxel_size=object_voxel_size,
+                       frames_per_launch=frames_per_launch, device=device)[:3]
+
+
+def _batches(scenario, frames, cameras, frames_per_launch, load_lidar, load_image, device):
+    step = len(frames) if not frames_per_launch or frames_per_launch < 0 else int(frames_per_launch)
+    for s in range(0, len(frames), step):
+        yield _Batch(scenario, frames[s:s + step], list(range(s, min(s + step, len(frames)))), cameras, load_lidar, load_image, device)
+
+
+def _split_frames(points, labels, batches):
+    """The label-0 points of a pass in (frame, ray) order as render.FrameSweeps: a prefix count of the labels read at the frames' ends."""
+    ends = torch.cat([b.offsets[1:] + base for b, base in zip(batches, np.cumsum([0] + [int(b.ranges.numel()) for b in batches[:-1]]).tolist())])
+    count = torch.cumsum(labels == 0, dim=0)                              # ends >= 1: _Batch refuses a frame without rays, so ends - 1 never wraps
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), count[ends - 1].cpu()])
+    return render.FrameSweeps(points[labels == 0], offsets)
+
+
+def frame_sweeps(scenario, load_lidar, load_image, obj_info, *, frames=None, cameras=CAMERAS, frames_per_launch=FRAMES_PER_LAUNCH, device="cuda"):
+    """The reference's load_lidar_data (data_process/pipeline_depth.py:16-60) on arrays: per frame, the returns a camera sees that lie
+    in no box of obj_info's objects (build_scene_clouds' third result, whose tables are indexed by position in `frames`), in ray order.
+    Concatenated they are build_scene_clouds' background at voxel_size = -1.  Returns a render.FrameSweeps."""
+    device, frames = _checked(scenario, frames, device, "frame_sweeps")
+    batches = list(_batches(scenario, frames, cameras, frames_per_launch, load_lidar, load_image, device))
+    out = [b.run(obj_info) for b in batches]
+    return _split_frames(torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out]), batches)
+
+
+def _checked(scenario, frames, device, name):
     device = torch.device(device)
     if device.type != "cuda":
-        raise hip.MudgError("build_scene_clouds: the clouds are built on the GPU (there is no CPU path)")
+        raise hip.MudgError(f"{name}: the clouds are built on the GPU (there is no CPU path)")
     n_frames = scenario["observers"]["lidar_TOP"]["n_frames"]
     frames = list(range(n_frames)) if frames is None else [int(f) for f in frames]
     if not frames or min(frames) < 0 or max(frames) >= n_frames:
-        raise hip.MudgError(f"build_scene_clouds: frames {frames} of a scenario with {n_frames}")
-    step = len(frames) if not frames_per_launch or frames_per_launch < 0 else int(frames_per_launch)
+        raise hip.MudgError(f"{name}: frames {frames} of a scenario with {n_frames}")
+    return device, frames
+
+
+def _build_scene(scenario, load_lidar, load_image, *, frames=None, cameras=CAMERAS, voxel_size=-1, object_voxel_size=-1,
+                frames_per_launch=FRAMES_PER_LAUNCH, device="cuda", keep_sweeps=False):
+    """build_scene_clouds with a fourth result: with keep_sweeps the background pass frame by frame (a render.FrameSweeps, what
+    frame_sweeps returns for the third result), taken from the pass that made the background — the rays are not walked again."""
+    device, frames = _checked(scenario, frames, device, "build_scene_clouds")
     candidates = moving_objects(scenario, frames)
     batches, points, labels = [], [], []
-    for s in range(0, len(frames), step):
-        batches.append(_Batch(scenario, frames[s:s + step], list(range(s, min(s + step, len(frames)))), cameras, load_lidar, load_image, device))
-        p, l = batches[-1].run(candidates)
+    for batch in _batches(scenario, frames, cameras, frames_per_launch, load_lidar, load_image, device):
+        batches.append(batch)
+        p, l = batch.run(candidates)
         points.append(p)
         labels.append(l)
     points, labels = torch.cat(points), torch.cat(labels)
@@ -200,11 +236,12 @@ def build_scene_clouds(scenario, load_lidar, load_image, *, frames=None, cameras
     if len(obj_info) != len(candidates):                                # the background pass sees only the objects that survived
         out = [b.run(obj_info) for b in batches]
         points, labels = torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
-    ground = points[labels == 0]
+    sweeps = _split_frames(points, labels, batches) if keep_sweeps else None
+    ground = sweeps.points if sweeps is not None else points[labels == 0]
     if len(ground) == 0:
         raise hip.MudgError("build_scene_clouds: no LiDAR return is seen by a camera outside the objects' boxes")
     background = render.PointCloud(ground)
     if voxel_size > 0:
         background = voxel_downsample(background, voxel_size)
     objects = render.ObjectSet.from_obj_info(obj_info, device) if obj_info else None
-    return background, objects, obj_info
+    return background, objects, obj_info, sweeps

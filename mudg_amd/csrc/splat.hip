@@ -6,23 +6,11 @@
 //                  written into (3, T, H, W) tensors at frame t                       generate_sparse.py:208-223, data_tools.py:53-54, 93-94
 // Everything is fp32 in a fixed order with correctly rounded operations, and the depth test is an integer minimum: the images do not
 // depend on the order in which the points arrive and are bit-equal to the numpy definition in tests/splat_reference.py.
-#include "common.h"
+#include "splat_shared.h"
 
 namespace {
 
-constexpr uint64_t EMPTY = ~0ull;
-constexpr int MAX_SPRITE = 8;                          // a sprite covers at most this many pixels a side (point size <= 8)
-
-struct SplatCam { float fx, fy, cx, cy, znear, zfar, half; };      // half = point size / 2
-
-// The pixel columns (rows) i with lo <= i + 0.5 < hi, clipped to [0, n): the comparison is the rule's own, in fp32; floorf only
-// proposes a range one pixel too wide on either side.  lo < n and hi > 0 hold on entry.
-__device__ __forceinline__ void cover(float lo, float hi, int n, int& a, int& b) {
-    a = max((int)floorf(lo) - 1, 0);
-    b = min((int)floorf(hi) + 1, n - 1);
-    while (a <= b && !(__fadd_rn((float)a, 0.5f) >= lo)) ++a;
-    while (b >= a && !(__fadd_rn((float)b, 0.5f) < hi)) --b;
-}
+constexpr uint64_t EMPTY = SPLAT_EMPTY;
 
 // OBJ = false: one matrix per pose, the same for every lane (uniform addresses: the matrices sit in scalar registers).
 // OBJ = true: matrix (pose, id[point]) of `nmat` per pose.  STATS: count covered pixels and issued atomics (tools only).
@@ -41,20 +29,9 @@ __global__ __launch_bounds__(256) void splat_points_kernel(const u32x4* __restri
         const int64_t plane = (int64_t)H * W;
         for (int p = 0; p < P; ++p) {
             const float* m = mats + ((int64_t)p * nmat + id) * 12;
-            const float xc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], x), __fmul_rn(m[1], y)), __fmul_rn(m[2], z)), m[3]);
-            const float yc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[4], x), __fmul_rn(m[5], y)), __fmul_rn(m[6], z)), m[7]);
-            const float zc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[8], x), __fmul_rn(m[9], y)), __fmul_rn(m[10], z)), m[11]);
-            if (!(zc > cam.znear && zc < cam.zfar)) continue;
-            const float u = __fadd_rn(__fmul_rn(cam.fx, __fdiv_rn(xc, zc)), cam.cx);
-            const float v = __fadd_rn(__fmul_rn(cam.fy, __fdiv_rn(yc, zc)), cam.cy);
-            const float ulo = __fsub_rn(u, cam.half), uhi = __fadd_rn(u, cam.half);
-            const float vlo = __fsub_rn(v, cam.half), vhi = __fadd_rn(v, cam.half);
-            if (!(uhi > 0.0f && ulo < (float)W && vhi > 0.0f && vlo < (float)H)) continue;      // off the image (or not a number)
+            float zc, u, v;
             int i0, i1, j0, j1;
-            cover(ulo, uhi, W, i0, i1);
-            cover(vlo, vhi, H, j0, j1);
-            i1 = min(i1, i0 + MAX_SPRITE - 1);
-            j1 = min(j1, j0 + MAX_SPRITE - 1);
+            if (!splat_project(m, x, y, z, cam, H, W, zc, u, v, i0, i1, j0, j1)) continue;
             const unsigned long long key = ((unsigned long long)__float_as_uint(zc) << 32) | (unsigned long long)(uint32_t)idx;
             unsigned long long* img = keys + p * plane;
             for (int j = j0; j <= j1; ++j)

@@ -79,6 +79,137 @@ def normals_from_depth(depth, intr, hw_native, labels=None, *, sky_label=SKY_LAB
                              max_depth=max_depth, max_rel_step=max_rel_step)
 
 
+def window_frames(frame, n_frames, window=(-2, 3)):
+    """The sweeps pooled for a frame (get_6frames_lidar, data_process/pipeline_depth.py:63-67, restated): frame + window[0] ..
+    frame + window[1], each replaced by the frame itself when it falls outside [0, n_frames)."""
+    return [f if 0 <= f < n_frames else frame for f in range(frame + window[0], frame + window[1] + 1)]
+
+
+def lidar_depth_maps(sweeps, objects, intr, c2w, hw_native, hw_out=None, *, frame_ids=None, window=(-2, 3), point_size=2.0, occlusion=True,
+                     reach=4, rel_tol=0.05, occluder_size=1.0, znear=render.ZNEAR, zfar=render.ZFAR):
+    """The reference's "six_frames_depth" (data_process/pipeline_depth.py:63-152).  sweeps: a render.FrameSweeps
+    (cloud.frame_sweeps); objects: a render.ObjectSet or None; intr (3, 3) or (T, 3, 3) at hw_native; c2w (T, 4, 4), the camera in the
+    T frames asked for; frame_ids: their numbers in the sweeps and the objects' tables (default 0 .. T-1); hw_out: None for native.
+
+    A frame's candidates are the sweeps of window_frames (a frame that occurs twice counts once: the result cannot differ) and the
+    points of the objects visible at the frame.  They are projected, culled and drawn by §12's rule at point_size, except those the
+    occlusion test hides: all candidates are first drawn at occluder_size into a buffer Z, and a point with camera depth zc and home
+    pixel (floor(v), floor(u)) is hidden iff along one of the four lines through the home pixel (row, column, both diagonals) there is
+    on BOTH sides, within `reach` pixels, a pixel whose Z depth is below zc (1 - rel_tol).  This image-space rule stands in for the
+    reference's Open3D hidden_point_removal and is this project's own.  Returns (T, H, W) fp32 metres, 0 where nothing landed."""
+    depth, passes = _lidar_depth_passes(sweeps, objects, intr, c2w, hw_native, hw_out, frame_ids=frame_ids, window=window, point_size=point_size,
+                                       occlusion=occlusion, reach=reach, rel_tol=rel_tol, occluder_size=occluder_size, znear=znear, zfar=zfar)
+    for occluders, visible in passes:
+        occluders()
+        visible()
+    return depth
+
+
+def _lidar_depth_passes(sweeps, objects, intr, c2w, hw_native, hw_out=None, *, frame_ids=None, window=(-2, 3), point_size=2.0, occlusion=True,
+                       reach=4, rel_tol=0.05, occluder_size=1.0, znear=render.ZNEAR, zfar=render.ZFAR):
+    """lidar_depth_maps' arguments, checked, and its work laid out: (depth (T, H, W), [(occluders, visible)] per frame) — calling every
+    pair in order fills depth.  occluders() draws the frame's candidates into Z (nothing without occlusion); visible() draws those Z does
+    not hide and resolves into depth[t], which leaves both key images empty.  tools/lidar_depth_bench.py times the two apart."""
+    if not isinstance(sweeps, render.FrameSweeps) or (objects is not None and not isinstance(objects, render.ObjectSet)):
+        raise hip.MudgError("lidar_depth_maps: the sweeps are a render.FrameSweeps and the objects a render.ObjectSet (on the GPU; there is no CPU path)")
+    c2w = np.asarray(c2w, dtype=np.float64)
+    if c2w.ndim != 3 or c2w.shape[1:] != (4, 4) or c2w.shape[0] == 0:
+        raise hip.MudgError(f"lidar_depth_maps: cameras {c2w.shape}, expected (T > 0, 4, 4)")
+    T = c2w.shape[0]
+    frame_ids = list(range(T)) if frame_ids is None else [int(f) for f in frame_ids]
+    n_frames = sweeps.frames
+    if len(frame_ids) != T or min(frame_ids) < 0 or max(frame_ids) >= n_frames or (objects is not None and objects.frames != n_frames):
+        raise hip.MudgError(f"lidar_depth_maps: frames {frame_ids} for {T} cameras, sweeps of {n_frames} frames"
+                            + (f" and objects of {objects.frames}" if objects is not None else ""))
+    intr = np.asarray(intr, dtype=np.float64)
+    if intr.shape not in ((3, 3), (T, 3, 3)):
+        raise hip.MudgError(f"lidar_depth_maps: intrinsics {intr.shape} for {T} frames, expected (3, 3) or (T, 3, 3)")
+    intr = np.broadcast_to(intr, (T, 3, 3))
+    window = tuple(int(v) for v in window)
+    if len(window) != 2 or window[0] > window[1] or window[1] - window[0] >= ops.LIDAR_MAX_SEGMENTS:
+        raise hip.MudgError(f"lidar_depth_maps: window {window} (first <= last, at most {ops.LIDAR_MAX_SEGMENTS} frames)")
+    if not (isinstance(reach, int) and 1 <= reach <= ops.LIDAR_MAX_REACH) or not 0.0 <= float(rel_tol) < 1.0:
+        raise hip.MudgError(f"lidar_depth_maps: reach {reach} (an integer, 1 .. {ops.LIDAR_MAX_REACH}) and rel_tol {rel_tol} (0 <= rel_tol < 1)")
+    hw_out = hw_native if hw_out is None else hw_out
+    H, W = (int(v) for v in hw_out)
+    if H <= 0 or W <= 0:
+        raise hip.MudgError(f"lidar_depth_maps: size {hw_out}")
+    dev = sweeps.points.device
+
+    w2c = np.linalg.inv(c2w)                                                              # host, float64; one upload for the call
+    bg_mats = torch.from_numpy(np.ascontiguousarray(w2c[:, :3, :].reshape(T, 1, 12)).astype(np.float32)).to(dev)
+    obj_mats = None
+    if objects is not None:
+        obj_mats = np.stack([objects.matrices(w2c[t:t + 1], frame_ids[t])[0] for t in range(T)]).reshape(T, -1, 12)
+        obj_mats = torch.from_numpy(obj_mats.astype(np.float32)).to(dev)
+    offsets = sweeps.offsets.tolist()
+    depth = torch.empty((T, H, W), dtype=torch.float32, device=dev)
+    keys = ops.splat_keys(1, H, W, dev)
+    Z = ops.splat_keys(1, H, W, dev) if occlusion else None
+    kw = dict(znear=znear, zfar=zfar)
+    def frame(t):
+        cam = render.scaled_intrinsics(intr[t], hw_native, hw_out).astype(np.float32)
+        runs = []                                                                         # neighbouring frames are one run of the cloud
+        for f in sorted(set(window_frames(frame_ids[t], n_frames, window))):
+            if offsets[f + 1] > offsets[f]:
+                if runs and runs[-1][0] + runs[-1][1] == offsets[f]:
+                    runs[-1] = (runs[-1][0], runs[-1][1] + offsets[f + 1] - offsets[f])
+                else:
+                    runs.append((offsets[f], offsets[f + 1] - offsets[f]))
+        total = sum(r[1] for r in runs)
+        with_objects = objects is not None and bool(objects.visible(frame_ids[t]))
+
+        def occluders():
+            if not occlusion:
+                return
+            for a, n in runs:
+                ops.splat_points(sweeps.points[a:a + n], bg_mats[t:t + 1], Z, cam, occluder_size, **kw)
+            if with_objects:
+                ops.splat_points(objects.cloud.points, obj_mats[t:t + 1], Z, cam, occluder_size, ids=objects.ids, **kw)
+
+        def visible():
+            test = dict(occluder_keys=Z[0] if occlusion else None, reach=reach, rel_tol=rel_tol, **kw)
+            if runs:
+                ops.lidar_splat_visible(sweeps.points, runs, bg_mats[t], keys[0], cam, point_size, **test)
+            if with_objects:
+                ops.lidar_splat_visible(objects.cloud.points, [(0, len(objects.cloud))], obj_mats[t], keys[0], cam, point_size, ids=objects.ids,
+                                        index_base=total, **test)
+            ops.lidar_depth_resolve(keys[0], depth[t], Z[0] if occlusion else None)
+        return occluders, visible
+    return depth, [frame(t) for t in range(T)]
+
+
+def complete_depth(lidar_depth, labels=None, *, max_depth=MAX_DEPTH, extrapolate=True, sky_label=SKY_LABEL, return_source=False):
+    """A sparse depth map made dense: the classical morphological completion of Ku et al. 2018 with this project's
+    border rules, in place of the reference's learned inpainting model (DepthLab) — parity with either is not claimed.  lidar_depth:
+    (T, H, W) fp32 metres, 0 where there is none (lidar_depth_maps'); labels: (T, H, W) int64 or None (no sky rule).  Inverted depths are
+    dilated by a 13-pixel diamond, closed by 5 x 5, filled from 7 x 7, with extrapolate extended to the top of every column and filled
+    from 31 x 31, then the 5 x 5 median and a 5 x 5 binomial blur over the filled pixels; the sky is max_depth.
+    Returns (T, H, W) fp32 metres, 0 where nothing reached — with return_source also (T, H, W) uint8: 0 empty, 1 measured, 2 filled by
+    the closing, 3 by the extension, 4 sky."""
+    depth = _on_gpu("complete_depth", "the LiDAR depth", lidar_depth, torch.float32)
+    if depth.dim() != 3:
+        raise hip.MudgError(f"complete_depth: expected (T, H, W) depths, got {tuple(depth.shape)}")
+    if labels is not None:
+        labels = _on_gpu("complete_depth", "the label image", labels, torch.int64, depth.shape)
+    return ops.depth_complete(depth, labels, max_depth=max_depth, extrapolate=extrapolate, sky_label=sky_label, return_source=return_source)
+
+
+def depth_labels_from_lidar(scene, frame_ids, hw_out=None, labels=None, **kw):
+    """The scene's own depth labels: lidar_depth_maps on scene.sweeps / scene.objects at the scene's camera, then complete_depth.
+    scene: a render.Scene made with keep_sweeps=True; frame_ids: positions in the scene's frames; **kw goes to whichever of the two
+    takes it.  Returns (lidar_depth, dense_depth, source); the dense map at native size is what frames.SceneFrames(images, depth=) takes."""
+    if getattr(scene, "sweeps", None) is None:
+        raise hip.MudgError("depth_labels_from_lidar: the scene has no sweeps (render.Scene.from_scenario(..., keep_sweeps=True) keeps them)")
+    rows = [int(f) for f in frame_ids]
+    dense_kw = {k: kw.pop(k) for k in ("max_depth", "extrapolate", "sky_label") if k in kw}
+    intr = np.asarray(scene.intr, dtype=np.float64)
+    lidar = lidar_depth_maps(scene.sweeps, scene.objects, intr if intr.ndim == 2 else intr[rows], np.asarray(scene.c2w)[rows], scene.hw_native, hw_out,
+                             frame_ids=rows, **kw)
+    dense, source = complete_depth(lidar, labels, return_source=True, **dense_kw)
+    return lidar, dense, source
+
+
 def lift_views(depth, rgb, intr, c2w, hw_native, labels=None, *, min_depth=0.0, max_depth=MAX_DEPTH, sky_label=SKY_LABEL):
     """Generated views as coloured world-space points in the renderer's packed format.  depth: (T, H, W) fp32 metres; rgb: (T, H, W, 3)
     uint8; intr: (3, 3) or (T, 3, 3) at hw_native; c2w: (T, 4, 4), the poses the views were generated at (OpenCV convention);

@@ -180,6 +180,10 @@ SIGNATURES = {
     "mudg_depth_normals": (_I, [_P, _P, _L, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P]),
     "mudg_normal_stream": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _I, _I, _P]),
     "mudg_metric_normals": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "mudg_lidar_splat_visible": (_I, [_P, _P, C.POINTER(C.c_int64), _I, _P, _I, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _F, _L, _P]),
+    "mudg_lidar_depth_resolve": (_I, [_P, _P, _P, _L, _P]),
+    "mudg_depth_complete_scratch": (_L, [_I, _I, _I]),
+    "mudg_depth_complete": (_I, [_P, _P, _L, _I, _I, _I, _F, _I, _P, _P, _P, _L, _P]),
     "mudg_short_attention_ok": (_I, [C.POINTER(ShortAttnDesc)]),
     "mudg_short_attention": (_I, [C.POINTER(ShortAttnDesc), _P]),
     "mudg_layernorm_f32": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P]),

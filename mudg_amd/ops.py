@@ -1179,6 +1179,81 @@ def metric_normals(pred, gt, valid=None):
     return hist
 
 
+# ------------------------------------------------------------------------------------------------ LiDAR depth maps
+LIDAR_MAX_SEGMENTS, LIDAR_MAX_REACH = 8, 16
+
+
+def lidar_splat_visible(points, segments, mats, keys, intr, point_size, *, occluder_keys=None, ids=None, reach=4, rel_tol=0.05, znear=1e-4,
+                        zfar=200.0, index_base=0):
+    """The candidates — runs [(first point, length > 0)] (at most 8) of a packed cloud (n, 4) int32 — through mats (nmat, 12) fp32 (ids (n,)
+    int32 choose among nmat > 1) and intr = (fx, fy, cx, cy) into keys (h, w) int64 by §12's rule, except the hidden ones: against
+    occluder_keys (h, w) int64, drawn by splat_points from the same candidates, a point with camera depth zc is hidden iff along one of
+    the four lines through its home pixel both sides hold, within `reach` pixels, a depth below fp32(zc * fp32(1 - rel_tol)).
+    occluder_keys None: no test."""
+    _splat_tensor("lidar_splat_visible: points", points, torch.int32)
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
+        raise hip.MudgError(f"lidar_splat_visible: expected packed points (n > 0, 4), got {tuple(points.shape)}")
+    n = points.shape[0]
+    segments = [(int(a), int(b)) for a, b in segments]
+    if not 1 <= len(segments) <= LIDAR_MAX_SEGMENTS or any(a < 0 or b <= 0 or a + b > n for a, b in segments):
+        raise hip.MudgError(f"lidar_splat_visible: segments {segments} of a cloud of {n} points (1 .. {LIDAR_MAX_SEGMENTS} runs inside it)")
+    _splat_tensor("lidar_splat_visible: mats", mats, torch.float32)
+    _splat_tensor("lidar_splat_visible: keys", keys, torch.int64)
+    if mats.dim() != 2 or mats.shape[1] != 12 or keys.dim() != 2:
+        raise hip.MudgError(f"lidar_splat_visible: matrices {tuple(mats.shape)} and a key image {tuple(keys.shape)}, expected (nmat, 12) and (h, w)")
+    if ids is not None:
+        _splat_tensor("lidar_splat_visible: ids", ids, torch.int32, (n,))
+    elif mats.shape[0] != 1:
+        raise hip.MudgError(f"lidar_splat_visible: {mats.shape[0]} matrices need per-point ids")
+    keep = 1.0
+    if occluder_keys is not None:
+        _splat_tensor("lidar_splat_visible: occluder keys", occluder_keys, torch.int64, keys.shape)
+        if not (isinstance(reach, int) and 1 <= reach <= LIDAR_MAX_REACH) or not 0.0 <= float(rel_tol) < 1.0:
+            raise hip.MudgError(f"lidar_splat_visible: reach {reach} (an integer, 1 .. {LIDAR_MAX_REACH}) and rel_tol {rel_tol} (0 <= rel_tol < 1)")
+        keep = 1.0 - float(rel_tol)
+    table = (C.c_int64 * (2 * len(segments)))(*[v for s in segments for v in s])
+    fx, fy, cx, cy = (float(v) for v in intr)
+    hip.check(hip.lib().mudg_lidar_splat_visible(points.data_ptr(), _ptr(ids), table, len(segments), mats.data_ptr(), mats.shape[0],
+                                                 _ptr(occluder_keys), keys.data_ptr(), keys.shape[0], keys.shape[1], fx, fy, cx, cy, float(znear),
+                                                 float(zfar), float(point_size), int(reach), keep, int(index_base), _stream()),
+              "mudg_lidar_splat_visible")
+    return keys
+
+
+def lidar_depth_resolve(keys, depth, occluder_keys=None):
+    """keys (h, w) int64 -> depth (h, w) fp32 (written in place: a frame of a larger tensor): the winner's camera depth, 0 where nothing
+    landed; keys, and occluder_keys if given, are empty again afterwards."""
+    _splat_tensor("lidar_depth_resolve: keys", keys, torch.int64)
+    _splat_tensor("lidar_depth_resolve: depth", depth, torch.float32, keys.shape)
+    if occluder_keys is not None:
+        _splat_tensor("lidar_depth_resolve: occluder keys", occluder_keys, torch.int64, keys.shape)
+    hip.check(hip.lib().mudg_lidar_depth_resolve(keys.data_ptr(), _ptr(occluder_keys), depth.data_ptr(), keys.numel(), _stream()),
+              "mudg_lidar_depth_resolve")
+    return depth
+
+
+def depth_complete(depth, labels=None, *, max_depth=100.0, extrapolate=True, sky_label=10, return_source=False):
+    """depth (f, h, w) fp32 metres, 0 where there is none -> the dense map (f, h, w) fp32 by the nine steps of DESIGN.md §20 (and the
+    uint8 source map: 0 empty, 1 measured, 2 closed, 3 extended, 4 sky).  labels (f, h, w) int64 or None."""
+    _splat_tensor("depth_complete: depth", depth, torch.float32)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise hip.MudgError(f"depth_complete: expected (frames, h, w) depths, got {tuple(depth.shape)}")
+    f, h, w = depth.shape
+    if labels is not None:
+        _splat_tensor("depth_complete: labels", labels, torch.int64, (f, h, w))
+    if not 0.1 < float(max_depth) <= 65536.0:
+        raise hip.MudgError(f"depth_complete: max_depth {max_depth} (0.1 < max_depth <= 65536)")
+    need = hip.lib().mudg_depth_complete_scratch(f, h, w)
+    if need < 0:
+        raise hip.MudgError(f"depth_complete: {f} frames of {h} x {w} (1 .. 65535 frames and rows, at most 2^24 pixels each)")
+    scratch = torch.empty((need,), dtype=torch.uint8, device=depth.device)
+    out = torch.empty_like(depth)
+    source = torch.empty((f, h, w), dtype=torch.uint8, device=depth.device) if return_source else None
+    hip.check(hip.lib().mudg_depth_complete(depth.data_ptr(), _ptr(labels), int(sky_label), f, h, w, float(max_depth), 1 if extrapolate else 0,
+                                            out.data_ptr(), _ptr(source), scratch.data_ptr(), need, _stream()), "mudg_depth_complete")
+    return (out, source) if return_source else out
+
+
 # ------------------------------------------------------------------------------------------------ the CLIP image tower (DESIGN.md §17)
 CLIP_SIZE, CLIP_PATCH, CLIP_K, CLIP_KPAD = 224, 14, 588, 592
 _CLIP_TABLES = {}

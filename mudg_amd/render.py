@@ -62,6 +62,28 @@ class PointCloud:
         return self.points.shape[0]
 
 
+class FrameSweeps:
+    """The background returns of a scene frame by frame (cloud.frame_sweeps): `points` packed like PointCloud.points, frame f owning
+    points[offsets[f]:offsets[f + 1]] in ray order; `offsets` (frames + 1,) int64 on the host.  What the reference's load_lidar_data
+    (data_process/pipeline_depth.py:16-60) returns as lists."""
+
+    def __init__(self, points: torch.Tensor, offsets):
+        if not torch.is_tensor(points) or not points.is_cuda or points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 4:
+            raise hip.MudgError("FrameSweeps: expected packed (n, 4) int32 points on the GPU (there is no CPU path)")
+        offsets = torch.as_tensor(offsets, dtype=torch.int64).cpu()
+        if offsets.dim() != 1 or offsets.numel() < 2 or int(offsets[0]) != 0 or int(offsets[-1]) != points.shape[0] or bool((offsets[1:] < offsets[:-1]).any()):
+            raise hip.MudgError(f"FrameSweeps: offsets {offsets.tolist()} do not cut {points.shape[0]} points into frames")
+        self.points = points.contiguous()
+        self.offsets = offsets
+
+    @property
+    def frames(self):
+        return self.offsets.numel() - 1
+
+    def frame(self, f):
+        return self.points[int(self.offsets[f]):int(self.offsets[f + 1])]
+
+
 class ObjectSet:
     """The moving objects of a scene (the reference's objects_info.pkl): per object a cloud, `transform_obj` (frames, 4, 4) taking it
     to the world and `visibility` (frames,).  All clouds sit in one concatenated device buffer with a per-point object id; a frame
@@ -215,14 +237,16 @@ class Scene:
     intr: np.ndarray            # (3, 3) or (frames, 3, 3)
     c2w: np.ndarray             # (frames, 4, 4)
     hw_native: tuple            # (H0, W0) the intrinsics refer to
+    sweeps: Optional[FrameSweeps] = None      # the background frame by frame (depth.lidar_depth_maps), kept on request
 
     @classmethod
-    def from_scenario(cls, scenario, load_lidar, load_image, camera="camera_FRONT", *, frames=None, **kwargs):
+    def from_scenario(cls, scenario, load_lidar, load_image, camera="camera_FRONT", *, frames=None, keep_sweeps=False, **kwargs):
         """Build the clouds from the scenario's LiDAR sweeps (cloud.build_scene_clouds, which takes **kwargs) and take `camera`'s
-        intrinsics, poses and size for the frames used."""
+        intrinsics, poses and size for the frames used.  keep_sweeps: also keep the background pass frame by frame, before any voxel
+        thinning, for the LiDAR depth maps."""
         from . import cloud
-        background, objects, _ = cloud.build_scene_clouds(scenario, load_lidar, load_image, frames=frames, **kwargs)
+        background, objects, _, sweeps = cloud._build_scene(scenario, load_lidar, load_image, frames=frames, keep_sweeps=keep_sweeps, **kwargs)
         data = scenario["observers"][camera]["data"]
         rows = list(range(scenario["observers"]["lidar_TOP"]["n_frames"])) if frames is None else [int(f) for f in frames]
         return cls(background, objects, np.asarray(data["intr"], dtype=np.float64)[rows], np.asarray(data["c2w"], dtype=np.float64)[rows],
-                   tuple(int(v) for v in data["hw"][rows[0]]))
+                   tuple(int(v) for v in data["hw"][rows[0]]), sweeps)
