@@ -15,7 +15,8 @@ contractions map onto the forward GEMM kernel (mudg_gemm: Y[m][n] = sum_k X[m][k
                 never leave registers; split-operand builds: per head, fp32 scores in memory, batched GEMMs
 
 Reference semantics: lvdm/modules/attention.py, lvdm/modules/networks/openaimodel3d.py (forward), torch.autograd (backward);
-checked against autograd of the CPU oracle in tests/test_training_gpu.py."""
+every Function on its own against fp64 autograd in tests/test_train_functions_gpu.py, the whole UNet against autograd of the CPU
+oracle in tests/test_training_gpu.py."""
 import collections
 import weakref
 
@@ -215,9 +216,10 @@ class Linear(torch.autograd.Function):
             dyo, db = grad_rows(dy, True, want_b)
         elif _need(ctx, 1):
             dyt, dyo, db = grad_forms(dy, n, k, _need(ctx, 0), want_b)
-        else:
-            dyo = op(_pad_cols(dy, _pad8(n))) if _need(ctx, 0) else None
-            db = K.group_colsum(dy)[0] if want_b else None
+        else:                   # frozen weight: the column sums in the order of the branches above (db: the same bits either way)
+            dyo, db = grad_rows(dy, _need(ctx, 0) and n % 8 == 0, want_b)
+            if dyo is None and _need(ctx, 0):
+                dyo = op(_pad_cols(dy, _pad8(n)))
         if _need(ctx, 0):
             wt = K.transpose_gather(w2)                                  # [K][N padded]
             dx = ops.gemm(dyo, wt, out_fp32=True, frame_rows=ctx.hint)
@@ -225,7 +227,7 @@ class Linear(torch.autograd.Function):
             dw = K.wgrad(dyo, x, positions=x.shape[0], m=n, c=k).reshape(ctx.wshape)
         elif _need(ctx, 1):
             dw = wgrad_gemm(dyt, transposed(x, n, k), n, k, x.shape[0]).reshape(ctx.wshape)
-        return dx, dw, db, (dy if ctx.has_r else None)
+        return dx, dw, db, (dy if ctx.has_r and _need(ctx, 3) else None)
 
 
 # ------------------------------------------------------------------------------------------------ 3x3 conv
@@ -277,8 +279,8 @@ class Conv3x3(torch.autograd.Function):
             dyo, db = grad_rows(dy, True, want_b)
         elif _need(ctx, 1):
             dyt, dyo, db = grad_forms(dy, co, 9 * ci, _need(ctx, 0) and stride == 1, want_b)       # [Cout][P padded], rows, sums
-        elif want_b:
-            db = K.group_colsum(dy)[0]
+        elif want_b:            # frozen weight: the column sums in the order of the branches above
+            db = grad_rows(dy, False, True)[1]
         if _need(ctx, 0):
             copad = _pad8(co)
             src = dyo
@@ -296,7 +298,7 @@ class Conv3x3(torch.autograd.Function):
             dw = wgrad_gemm(dyt, xt, co, 9 * ci, p).reshape(co, 3, 3, ci).permute(0, 3, 1, 2).contiguous()
         if has_g and _need(ctx, 3):
             dg = K.group_colsum(dy, rows_per_group=ctx.rpg)
-        return dx, dw, db, dg, (dy if has_r else None), None, None
+        return dx, dw, db, dg, (dy if has_r and _need(ctx, 4) else None), None, None
 
 
 class TConv3(torch.autograd.Function):
@@ -327,9 +329,8 @@ class TConv3(torch.autograd.Function):
             dyo, db = grad_rows(dy, True, want_b)
         elif _need(ctx, 1):
             dyt, dyo, db = grad_forms(dy, co, 3 * ci, _need(ctx, 0), want_b)
-        else:
-            dyo = op(dy) if _need(ctx, 0) else None
-            db = K.group_colsum(dy)[0] if want_b else None
+        else:                   # frozen weight: the column sums in the order of the branches above
+            dyo, db = grad_rows(dy, _need(ctx, 0), want_b)
         if _need(ctx, 0):
             wf = w[:, :, :, 0, 0].flip(2).permute(1, 2, 0).reshape(ci, 3 * co).contiguous()        # [Cin][tap'][Cout]
             dx = ops.tconv3(dyo, op(wf), clips=clips, t=t, hw=hw, cin=co, out_fp32=True)
@@ -340,7 +341,7 @@ class TConv3(torch.autograd.Function):
             p = x.shape[0]
             xt = transposed_taps(x, co, ci, p, [dict(dt=d) for d in range(3)], 2, dict(T=t, HW=hw))
             dw = wgrad_gemm(dyt, xt, co, 3 * ci, p).reshape(co, 3, ci).permute(0, 2, 1).reshape(co, ci, 3, 1, 1).contiguous()
-        return dx, dw, db, (dy if has_r else None), None
+        return dx, dw, db, (dy if has_r and _need(ctx, 3) else None), None
 
 
 # ------------------------------------------------------------------------------------------------ normalisations, activations

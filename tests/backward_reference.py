@@ -99,11 +99,14 @@ def attention_bwd(q, k, v, do, *, frames, heads, nq, nk, kv_div, scale, round_to
     """(dQ, dK, dV) of O = softmax(scale Q K^T) V per (frame, head), head width 64: q, do [frames nq][heads 64]; k, v
     [(frames / kv_div) nk][heads 64], kv_div consecutive frames sharing one key / value batch.
         P = softmax(S), dP = dO V^T, D = rowsum(P dP), dS = scale P (dP - D), dV = P^T dO, dQ = dS K, dK = dS^T Q.
-    round_to (a 16-bit dtype): P and dS — and nothing else — pass through that type before the three products that consume them:
-    the one deliberate loss of mudg_attention_bwd, whose MFMAs take P and dS as operands."""
+    round_to (a 16-bit dtype, or (dtype, pieces) for the operand storage of a split-operand build): P and dS — and nothing else —
+    pass through that type before the three products that consume them: the one deliberate loss of mudg_attention_bwd, whose MFMAs take P and dS as operands."""
     q, k, v, do = (t.to(dtype) for t in (q, k, v, do))
     dq, dk, dv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
-    rt = (lambda t: t.to(round_to).to(dtype)) if round_to is not None else (lambda t: t)
+    if isinstance(round_to, tuple):          # (dtype, pieces): the operand storage of a split-operand build
+        rt = lambda t: sum(p.to(dtype) for p in operand_planes(t, *round_to))
+    else:
+        rt = (lambda t: t.to(round_to).to(dtype)) if round_to is not None else (lambda t: t)
     nqg = kv_div * nq
     for g in range(frames // kv_div):
         qs, ks = slice(g * nqg, (g + 1) * nqg), slice(g * nk, (g + 1) * nk)
