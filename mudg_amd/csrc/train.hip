@@ -1,7 +1,7 @@
 // train.hip — the kernels only the TRAINING step needs (reference: lvdm/models/ddpm3d.py:741-802 p_losses,
 // :1267-1300 configure_optimizers -> AdamW): backward passes of the normalisations, of GEGLU, of the softmax inside attention
 // and of the temporal attention, the transposed / gathered operand copies the weight-gradient GEMMs contract over, the
-// column sums behind bias gradients, the weighted MSE and its gradient, nearest-2x resampling both ways, and AdamW.
+// column sums behind bias gradients, the weighted MSE and its gradient, nearest-2x resampling both ways (the optimiser: optim.hip).
 // The contractions of the backward pass themselves (dX = dY W, dW = dY^T X, conv / temporal-conv input gradients) run on
 // the forward GEMM kernels (gemm.hip) — see mudg_amd/train/functions.py for how each one is expressed.
 // Gradients and the training stream are fp32 rows matrices; operands for the MFMA kernels are made by mudg_cast_rows /
@@ -529,431 +529,6 @@ __global__ void dilate2x_kernel(const float* __restrict__ src, float* __restrict
     dst[i] = v;
 }
 
-// AdamW (torch.optim.AdamW semantics, decoupled weight decay): fp32 parameters, gradients and moments, in place.
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                             float lr, float b1, float b2, float eps, float wd, float bc1, float bc2) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float gi = g[i];
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p[i] = pi - (lr / bc1) * (mi / denom);
-}
-
-// The same update over MANY parameter tensors in one launch (the UNet has 1520: one launch each was 2.4 % of a training step).
-// `table` lists chunks of at most CLIP_CHUNK values as rows (p, g, m, v, count); one workgroup per chunk.
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2, float eps, float wd,
-                                                           float bc1, float bc2) {
-    const int64_t* row = table + 5 * (int64_t)blockIdx.x;
-    float* p = reinterpret_cast<float*>(row[0]);
-    const float* g = reinterpret_cast<const float*>(row[1]);
-    float* m = reinterpret_cast<float*>(row[2]);
-    float* v = reinterpret_cast<float*>(row[3]);
-    const int n = (int)row[4];
-    const float step = lr / bc1, decay = 1.0f - lr * wd;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float gi = g[i];
-        const float pi = p[i] * decay;
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-        p[i] = pi - step * (mi / denom);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------- averaged weights
-// The exponential moving average of the weights (lvdm/ema.py LitEma.forward) and the weight exchange of ema_scope
-// (ddpm3d.py:188-201), over MANY tensors in one launch with the chunk-table scheme of adamw_multi_kernel.  Pure streaming:
-// a chunk is walked in pieces of 256 x 16 bytes per operand, MT_U pieces at a time, every load of the pieces issued before the
-// first use (the updates are in place, so the compiler may not move a load above a store by itself); a chunk whose addresses are
-// not all 16-byte aligned (a view into a flat bucket) and the last count % 4 values take the scalar loop.
-//   shadow <- shadow - one_minus_decay * (shadow - param), each operation rounded on its own: the bits of the reference on the CPU
-constexpr int MT_U = 2;
-// The addresses come out of the table as integers: typed as global memory, so that the accesses are global_* and not flat_* ones.
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) f32x4 gf32x4;
-__device__ __forceinline__ float ema_elem(float s, float p, float omd) { return __fsub_rn(s, __fmul_rn(omd, __fsub_rn(s, p))); }
-
-__global__ __launch_bounds__(256) void ema_multi_kernel(const int64_t* __restrict__ table, float omd) {
-    const int64_t* row = table + 3 * (int64_t)blockIdx.x;
-    gfloat* s = reinterpret_cast<gfloat*>(row[0]);
-    const gfloat* p = reinterpret_cast<const gfloat*>(row[1]);
-    const int n = (int)row[2];
-    int done = 0;
-    if (((row[0] | row[1]) & 15) == 0) {
-        gf32x4* s4 = reinterpret_cast<gf32x4*>(s);
-        const gf32x4* p4 = reinterpret_cast<const gf32x4*>(p);
-        const int n4 = n >> 2;
-        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
-            f32x4 a[MT_U] = {}, b[MT_U] = {};
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) { a[u] = s4[i0 + 256 * u]; b[u] = p4[i0 + 256 * u]; }
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[u][e] = ema_elem(a[u][e], b[u][e], omd);
-                s4[i0 + 256 * u] = a[u];
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int i = done + threadIdx.x; i < n; i += 256) s[i] = ema_elem(s[i], p[i], omd);
-}
-
-// rows (a, b, count): the two tensors change places; nothing else is held.
-__global__ __launch_bounds__(256) void swap_multi_kernel(const int64_t* __restrict__ table) {
-    const int64_t* row = table + 3 * (int64_t)blockIdx.x;
-    gfloat* a = reinterpret_cast<gfloat*>(row[0]);
-    gfloat* b = reinterpret_cast<gfloat*>(row[1]);
-    const int n = (int)row[2];
-    int done = 0;
-    if (((row[0] | row[1]) & 15) == 0) {
-        gf32x4* a4 = reinterpret_cast<gf32x4*>(a);
-        gf32x4* b4 = reinterpret_cast<gf32x4*>(b);
-        const int n4 = n >> 2;
-        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
-            f32x4 x[MT_U] = {}, y[MT_U] = {};
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) { x[u] = a4[i0 + 256 * u]; y[u] = b4[i0 + 256 * u]; }
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) { a4[i0 + 256 * u] = y[u]; b4[i0 + 256 * u] = x[u]; }
-        }
-        done = n4 << 2;
-    }
-    for (int i = done + threadIdx.x; i < n; i += 256) { const float x = a[i], y = b[i]; a[i] = y; b[i] = x; }
-}
-
-// adamw_multi_kernel's update and the average of the same element in one pass, rows (p, g, m, v, shadow, count): the average reads
-// the new parameter value out of the register it was just computed in — one read and one write of the shadow on top of the AdamW
-// traffic, no second read of the parameter.  The AdamW expressions are those of adamw_multi_kernel, term for term.
-__device__ __forceinline__ void adamw_ema_elem(float& p, float g, float& m, float& v, float& s, float b1, float b2, float eps, float bc2,
-                                               float step, float decay, float omd) {
-    const float gi = g;
-    const float pi = p * decay;
-    const float mi = b1 * m + (1.0f - b1) * gi;
-    const float vi = b2 * v + (1.0f - b2) * gi * gi;
-    m = mi; v = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p = pi - step * (mi / denom);
-    s = ema_elem(s, p, omd);
-}
-
-__global__ __launch_bounds__(256) void adamw_ema_multi_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2, float eps,
-                                                               float wd, float bc1, float bc2, float omd) {
-    const int64_t* row = table + 6 * (int64_t)blockIdx.x;
-    gfloat* p = reinterpret_cast<gfloat*>(row[0]);
-    const gfloat* g = reinterpret_cast<const gfloat*>(row[1]);
-    gfloat* m = reinterpret_cast<gfloat*>(row[2]);
-    gfloat* v = reinterpret_cast<gfloat*>(row[3]);
-    gfloat* s = reinterpret_cast<gfloat*>(row[4]);
-    const int n = (int)row[5];
-    const float step = lr / bc1, decay = 1.0f - lr * wd;
-    int done = 0;
-    if (((row[0] | row[1] | row[2] | row[3] | row[4]) & 15) == 0) {
-        gf32x4* p4 = reinterpret_cast<gf32x4*>(p);
-        const gf32x4* g4 = reinterpret_cast<const gf32x4*>(g);
-        gf32x4* m4 = reinterpret_cast<gf32x4*>(m);
-        gf32x4* v4 = reinterpret_cast<gf32x4*>(v);
-        gf32x4* s4 = reinterpret_cast<gf32x4*>(s);
-        const int n4 = n >> 2;
-        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
-            f32x4 pp[MT_U] = {}, gg[MT_U] = {}, mm[MT_U] = {}, vv[MT_U] = {}, ss[MT_U] = {};
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-                const int i = i0 + 256 * u;
-                pp[u] = p4[i]; gg[u] = g4[i]; mm[u] = m4[i]; vv[u] = v4[i]; ss[u] = s4[i];
-            }
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-                const int i = i0 + 256 * u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float pe = pp[u][e], me = mm[u][e], ve = vv[u][e], se = ss[u][e];
-                    adamw_ema_elem(pe, gg[u][e], me, ve, se, b1, b2, eps, bc2, step, decay, omd);
-                    pp[u][e] = pe; mm[u][e] = me; vv[u][e] = ve; ss[u][e] = se;
-                }
-                p4[i] = pp[u]; m4[i] = mm[u]; v4[i] = vv[u]; s4[i] = ss[u];
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int i = done + threadIdx.x; i < n; i += 256) {
-        float pe = p[i], me = m[i], ve = v[i], se = s[i];
-        adamw_ema_elem(pe, g[i], me, ve, se, b1, b2, eps, bc2, step, decay, omd);
-        p[i] = pe; m[i] = me; v[i] = ve; s[i] = se;
-    }
-}
-
-// Global gradient norm and clipping over many tensors without a host round trip (torch.nn.utils.clip_grad_norm_ semantics: the
-// reference's trainer clips to norm 0.5).  `table` lists chunks of at most CLIP_CHUNK fp32 values as (address, count) pairs; one
-// workgroup sums the squares of a chunk in fp64 (fixed order), one workgroup then folds the chunk sums in order and writes
-// out[0] = the norm, out[1] = min(1, max_norm / (norm + 1e-6)); the scale pass multiplies every chunk by out[1].
-constexpr int CLIP_CHUNK = 16384;
-__global__ __launch_bounds__(256) void chunk_sumsq_kernel(const int64_t* __restrict__ table, double* __restrict__ partial) {
-    __shared__ double red[256];
-    const float* x = reinterpret_cast<const float*>(table[2 * blockIdx.x]);
-    const int n = (int)table[2 * blockIdx.x + 1];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) { const double v = (double)x[i]; s += v * v; }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void norm_fold_kernel(const double* __restrict__ partial, int nchunks, float max_norm, float* __restrict__ out) {
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nchunks; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float norm = (float)sqrt(red[0]);
-        out[0] = norm;
-        const float coef = max_norm / (norm + 1e-6f);
-        out[1] = coef < 1.0f ? coef : 1.0f;
-    }
-}
-__global__ __launch_bounds__(256) void chunk_scale_kernel(const int64_t* __restrict__ table, const float* __restrict__ out) {
-    const float coef = out[1];
-    if (coef == 1.0f) return;
-    float* x = reinterpret_cast<float*>(table[2 * blockIdx.x]);
-    const int n = (int)table[2 * blockIdx.x + 1];
-    for (int i = threadIdx.x; i < n; i += 256) x[i] *= coef;
-}
-
-// ------------------------------------------------------------------------------------------------- loss scaling
-// torch.amp.GradScaler on the device (fp16 training: the loss is multiplied by `scale` before backward, so that output gradients
-// below the operand type's range survive the operand rounding).  The state is one 16-byte record
-//   [0] float scale   [1] int growth tracker   [2] int overflow flag of the current step   [3] int count of steps actually taken
-// which only kernels read and write: nothing in a step depends on a value the host would have to fetch.
-//   scaled_sumsq / scaled_fold   the norm pass of the SCALED gradients: per chunk the fp64 sum of (double)(g * inv_scale)^2 with
-//                    inv_scale = float(1 / double(scale)) (torch's unscale_); the fold writes out[0] = the unscaled norm,
-//                    out[1] = the clip coefficient (1 when max_norm <= 0: no clipping asked for) and the overflow flag: the sum of
-//                    squares of finite fp32 values cannot overflow fp64, so the step has overflowed iff the folded sum is not
-//                    finite (any +-inf or NaN gradient makes it so).  The gradients are NOT written.
-//   adamw_scaled_*   adamw_multi_kernel / adamw_ema_multi_kernel on the gradient (g * inv_scale) * coef, each product rounded on its
-//                    own (the bits of unscale_ followed by clip_grad_norm_); flag set: parameter and moments are neither changed
-//                    nor rewritten (the EMA form still averages the unchanged parameter, as LitEma.forward does after a skipped
-//                    step); the bias corrections use n = count + 1.
-//   loss_scale_update   torch's _amp_update_scale_, then count += !flag and the flag is cleared.
-struct ScaleRecord { float scale; int tracker; int overflow; int taken; };
-__device__ __forceinline__ float inv_scale_of(float scale) { return (float)(1.0 / (double)scale); }
-
-__global__ __launch_bounds__(256) void scaled_sumsq_kernel(const int64_t* __restrict__ table, double* __restrict__ partial,
-                                                            const ScaleRecord* __restrict__ rec) {
-    __shared__ double red[256];
-    const float inv = inv_scale_of(rec->scale);
-    const float* x = reinterpret_cast<const float*>(table[2 * blockIdx.x]);
-    const int n = (int)table[2 * blockIdx.x + 1];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) { const double v = (double)__fmul_rn(x[i], inv); s += v * v; }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void scaled_fold_kernel(const double* __restrict__ partial, int nchunks, float max_norm, float* __restrict__ out,
-                                                           ScaleRecord* __restrict__ rec) {
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nchunks; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double total = red[0];
-        const float norm = (float)sqrt(total);
-        out[0] = norm;
-        const float coef = max_norm / (norm + 1e-6f);
-        out[1] = (max_norm > 0.f && coef < 1.0f) ? coef : 1.0f;
-        rec->overflow = __builtin_isfinite(total) ? 0 : 1;
-    }
-}
-// scaler.unscale_: g <- g * inv_scale in place, for callers who want to look at the gradients (the optimiser does not need it).
-__global__ __launch_bounds__(256) void unscale_kernel(const int64_t* __restrict__ table, const ScaleRecord* __restrict__ rec) {
-    const float inv = inv_scale_of(rec->scale);
-    float* x = reinterpret_cast<float*>(table[2 * blockIdx.x]);
-    const int n = (int)table[2 * blockIdx.x + 1];
-    for (int i = threadIdx.x; i < n; i += 256) x[i] = __fmul_rn(x[i], inv);
-}
-
-// What a workgroup of the scaled optimiser reads once (uniform addresses of read-only memory: scalar loads).
-struct ScaledStep { float inv, coef, bc2, step; bool skip; };
-__device__ __forceinline__ ScaledStep scaled_step(const ScaleRecord* __restrict__ rec, const float* __restrict__ stat, float lr, float b1, float b2) {
-    ScaledStep s;
-    s.inv = inv_scale_of(rec->scale);
-    s.coef = stat[1];
-    s.skip = rec->overflow != 0;
-    const float n = (float)(rec->taken + 1);
-    s.bc2 = 1.0f - powf(b2, n);
-    s.step = lr / (1.0f - powf(b1, n));
-    return s;
-}
-__device__ __forceinline__ float scaled_grad(float g, const ScaledStep& s) { return __fmul_rn(__fmul_rn(g, s.inv), s.coef); }
-__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float b1, float b2, float eps, float bc2, float step, float decay) {
-    const float gi = g;
-    const float pi = p * decay;
-    const float mi = b1 * m + (1.0f - b1) * gi;
-    const float vi = b2 * v + (1.0f - b2) * gi * gi;
-    m = mi; v = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p = pi - step * (mi / denom);
-}
-
-// rows (p, g, m, v, count), as adamw_multi_kernel.
-__global__ __launch_bounds__(256) void adamw_scaled_multi_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2, float eps,
-                                                                  float wd, const ScaleRecord* __restrict__ rec, const float* __restrict__ stat) {
-    const ScaledStep sc = scaled_step(rec, stat, lr, b1, b2);
-    if (sc.skip) return;                                               // overflow: nothing is rewritten
-    const int64_t* row = table + 5 * (int64_t)blockIdx.x;
-    gfloat* p = reinterpret_cast<gfloat*>(row[0]);
-    const gfloat* g = reinterpret_cast<const gfloat*>(row[1]);
-    gfloat* m = reinterpret_cast<gfloat*>(row[2]);
-    gfloat* v = reinterpret_cast<gfloat*>(row[3]);
-    const int n = (int)row[4];
-    const float decay = 1.0f - lr * wd;
-    int done = 0;
-    if (((row[0] | row[1] | row[2] | row[3]) & 15) == 0) {
-        gf32x4* p4 = reinterpret_cast<gf32x4*>(p);
-        const gf32x4* g4 = reinterpret_cast<const gf32x4*>(g);
-        gf32x4* m4 = reinterpret_cast<gf32x4*>(m);
-        gf32x4* v4 = reinterpret_cast<gf32x4*>(v);
-        const int n4 = n >> 2;
-        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
-            f32x4 pp[MT_U] = {}, gg[MT_U] = {}, mm[MT_U] = {}, vv[MT_U] = {};
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-                const int i = i0 + 256 * u;
-                pp[u] = p4[i]; gg[u] = g4[i]; mm[u] = m4[i]; vv[u] = v4[i];
-            }
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-                const int i = i0 + 256 * u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float pe = pp[u][e], me = mm[u][e], ve = vv[u][e];
-                    adamw_elem(pe, scaled_grad(gg[u][e], sc), me, ve, b1, b2, eps, sc.bc2, sc.step, decay);
-                    pp[u][e] = pe; mm[u][e] = me; vv[u][e] = ve;
-                }
-                p4[i] = pp[u]; m4[i] = mm[u]; v4[i] = vv[u];
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int i = done + threadIdx.x; i < n; i += 256) {
-        float pe = p[i], me = m[i], ve = v[i];
-        adamw_elem(pe, scaled_grad(g[i], sc), me, ve, b1, b2, eps, sc.bc2, sc.step, decay);
-        p[i] = pe; m[i] = me; v[i] = ve;
-    }
-}
-
-// rows (p, g, m, v, shadow, count), as adamw_ema_multi_kernel.  A skipped step moves the shadow towards the unchanged parameter.
-__global__ __launch_bounds__(256) void adamw_scaled_ema_multi_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2, float eps,
-                                                                      float wd, float omd, const ScaleRecord* __restrict__ rec,
-                                                                      const float* __restrict__ stat) {
-    const ScaledStep sc = scaled_step(rec, stat, lr, b1, b2);
-    const int64_t* row = table + 6 * (int64_t)blockIdx.x;
-    gfloat* p = reinterpret_cast<gfloat*>(row[0]);
-    const gfloat* g = reinterpret_cast<const gfloat*>(row[1]);
-    gfloat* m = reinterpret_cast<gfloat*>(row[2]);
-    gfloat* v = reinterpret_cast<gfloat*>(row[3]);
-    gfloat* s = reinterpret_cast<gfloat*>(row[4]);
-    const int n = (int)row[5];
-    const float decay = 1.0f - lr * wd;
-    int done = 0;
-    if (sc.skip) {
-        if (((row[0] | row[4]) & 15) == 0) {
-            const gf32x4* p4 = reinterpret_cast<const gf32x4*>(p);
-            gf32x4* s4 = reinterpret_cast<gf32x4*>(s);
-            const int n4 = n >> 2;
-            for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
-                f32x4 a[MT_U] = {}, b[MT_U] = {};
-#pragma unroll
-                for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) { a[u] = s4[i0 + 256 * u]; b[u] = p4[i0 + 256 * u]; }
-#pragma unroll
-                for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a[u][e] = ema_elem(a[u][e], b[u][e], omd);
-                    s4[i0 + 256 * u] = a[u];
-                }
-            }
-            done = n4 << 2;
-        }
-        for (int i = done + threadIdx.x; i < n; i += 256) s[i] = ema_elem(s[i], p[i], omd);
-        return;
-    }
-    if (((row[0] | row[1] | row[2] | row[3] | row[4]) & 15) == 0) {
-        gf32x4* p4 = reinterpret_cast<gf32x4*>(p);
-        const gf32x4* g4 = reinterpret_cast<const gf32x4*>(g);
-        gf32x4* m4 = reinterpret_cast<gf32x4*>(m);
-        gf32x4* v4 = reinterpret_cast<gf32x4*>(v);
-        gf32x4* s4 = reinterpret_cast<gf32x4*>(s);
-        const int n4 = n >> 2;
-        for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * MT_U) {
-            f32x4 pp[MT_U] = {}, gg[MT_U] = {}, mm[MT_U] = {}, vv[MT_U] = {}, ss[MT_U] = {};
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-                const int i = i0 + 256 * u;
-                pp[u] = p4[i]; gg[u] = g4[i]; mm[u] = m4[i]; vv[u] = v4[i]; ss[u] = s4[i];
-            }
-#pragma unroll
-            for (int u = 0; u < MT_U; ++u) if (i0 + 256 * u < n4) {
-                const int i = i0 + 256 * u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float pe = pp[u][e], me = mm[u][e], ve = vv[u][e], se = ss[u][e];
-                    adamw_ema_elem(pe, scaled_grad(gg[u][e], sc), me, ve, se, b1, b2, eps, sc.bc2, sc.step, decay, omd);
-                    pp[u][e] = pe; mm[u][e] = me; vv[u][e] = ve; ss[u][e] = se;
-                }
-                p4[i] = pp[u]; m4[i] = mm[u]; v4[i] = vv[u]; s4[i] = ss[u];
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int i = done + threadIdx.x; i < n; i += 256) {
-        float pe = p[i], me = m[i], ve = v[i], se = s[i];
-        adamw_ema_elem(pe, scaled_grad(g[i], sc), me, ve, se, b1, b2, eps, sc.bc2, sc.step, decay, omd);
-        p[i] = pe; m[i] = me; v[i] = ve; s[i] = se;
-    }
-}
-
-__global__ void loss_scale_update_kernel(ScaleRecord* __restrict__ rec, float growth, float backoff, int interval) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int flag = rec->overflow;
-    if (flag) {
-        rec->scale = __fmul_rn(rec->scale, backoff);
-        rec->tracker = 0;
-    } else {
-        const int good = rec->tracker + 1;
-        if (good == interval) {
-            const float grown = __fmul_rn(rec->scale, growth);
-            if (__builtin_isfinite(grown)) rec->scale = grown;               // a growth that would leave fp32 is refused
-            rec->tracker = 0;
-        } else {
-            rec->tracker = good;
-        }
-    }
-    rec->taken += flag ? 0 : 1;
-    rec->overflow = 0;
-}
-
 // Exact (erf) GELU of the Perceiver feed-forward (resampler.py:27-34) and its derivative Phi(x) + x phi(x).
 __global__ void gelu_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1184,100 +759,6 @@ int mudg_dilate2x(const float* src, float* dst, int F, int ho, int wo, int hi, i
     hipLaunchKernelGGL(dilate2x_kernel, dim3(blocks_for((int64_t)F * hi * wi * C)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, dst, F, ho,
                        wo, hi, wi, C);
     return mudg_check_launch("mudg_dilate2x");
-}
-
-int mudg_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-               void* stream) {
-    MUDG_REQUIRE(p && g && m && v && n > 0 && step > 0, "mudg_adamw: bad arguments");
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, n, lr, beta1, beta2, eps,
-                       weight_decay, bc1, bc2);
-    return mudg_check_launch("mudg_adamw");
-}
-
-int mudg_adamw_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
-    MUDG_REQUIRE(table && nchunks > 0 && step > 0, "mudg_adamw_multi: bad arguments");
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, lr, beta1, beta2, eps,
-                       weight_decay, bc1, bc2);
-    return mudg_check_launch("mudg_adamw_multi");
-}
-
-int mudg_adamw_ema_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                         float one_minus_decay, void* stream) {
-    MUDG_REQUIRE(table && nchunks > 0 && step > 0, "mudg_adamw_ema_multi: bad arguments");
-    MUDG_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "mudg_adamw_ema_multi: one_minus_decay=%g outside [0, 1]", (double)one_minus_decay);
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_ema_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, lr, beta1, beta2,
-                       eps, weight_decay, bc1, bc2, one_minus_decay);
-    return mudg_check_launch("mudg_adamw_ema_multi");
-}
-
-int mudg_ema_multi(const int64_t* table, int nchunks, float one_minus_decay, void* stream) {
-    MUDG_REQUIRE(table && nchunks > 0, "mudg_ema_multi: bad arguments");
-    MUDG_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "mudg_ema_multi: one_minus_decay=%g outside [0, 1]", (double)one_minus_decay);
-    hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, one_minus_decay);
-    return mudg_check_launch("mudg_ema_multi");
-}
-
-int mudg_swap_multi(const int64_t* table, int nchunks, void* stream) {
-    MUDG_REQUIRE(table && nchunks > 0, "mudg_swap_multi: bad arguments");
-    hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table);
-    return mudg_check_launch("mudg_swap_multi");
-}
-
-int mudg_clip_chunk(void) { return CLIP_CHUNK; }
-
-int mudg_clip_grad_norm(const int64_t* table, int nchunks, double* partial, float max_norm, float* out, void* stream) {
-    MUDG_REQUIRE(table && partial && out && nchunks > 0 && max_norm > 0.f, "mudg_clip_grad_norm: bad arguments");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(chunk_sumsq_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, table, partial);
-    hipLaunchKernelGGL(norm_fold_kernel, dim3(1), dim3(256), 0, s, partial, nchunks, max_norm, out);
-    hipLaunchKernelGGL(chunk_scale_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, table, out);
-    return mudg_check_launch("mudg_clip_grad_norm");
-}
-
-int mudg_scaled_grad_norm(const int64_t* table, int nchunks, double* partial, float max_norm, float* out, void* record, void* stream) {
-    MUDG_REQUIRE(table && partial && out && record && nchunks > 0 && max_norm >= 0.f, "mudg_scaled_grad_norm: bad arguments");
-    MUDG_REQUIRE((reinterpret_cast<uintptr_t>(record) & 15u) == 0, "mudg_scaled_grad_norm: the scaler record must be 16-byte aligned");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    ScaleRecord* rec = reinterpret_cast<ScaleRecord*>(record);
-    hipLaunchKernelGGL(scaled_sumsq_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, table, partial, rec);
-    hipLaunchKernelGGL(scaled_fold_kernel, dim3(1), dim3(256), 0, s, partial, nchunks, max_norm, out, rec);
-    return mudg_check_launch("mudg_scaled_grad_norm");
-}
-
-int mudg_unscale_multi(const int64_t* table, int nchunks, const void* record, void* stream) {
-    MUDG_REQUIRE(table && record && nchunks > 0, "mudg_unscale_multi: bad arguments");
-    hipLaunchKernelGGL(unscale_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table,
-                       reinterpret_cast<const ScaleRecord*>(record));
-    return mudg_check_launch("mudg_unscale_multi");
-}
-
-int mudg_adamw_scaled_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay, const void* record,
-                            const float* stat, void* stream) {
-    MUDG_REQUIRE(table && record && stat && nchunks > 0, "mudg_adamw_scaled_multi: bad arguments");
-    hipLaunchKernelGGL(adamw_scaled_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, lr, beta1,
-                       beta2, eps, weight_decay, reinterpret_cast<const ScaleRecord*>(record), stat);
-    return mudg_check_launch("mudg_adamw_scaled_multi");
-}
-
-int mudg_adamw_scaled_ema_multi(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                float one_minus_decay, const void* record, const float* stat, void* stream) {
-    MUDG_REQUIRE(table && record && stat && nchunks > 0, "mudg_adamw_scaled_ema_multi: bad arguments");
-    MUDG_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "mudg_adamw_scaled_ema_multi: one_minus_decay=%g outside [0, 1]",
-                 (double)one_minus_decay);
-    hipLaunchKernelGGL(adamw_scaled_ema_multi_kernel, dim3((unsigned)nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, lr, beta1,
-                       beta2, eps, weight_decay, one_minus_decay, reinterpret_cast<const ScaleRecord*>(record), stat);
-    return mudg_check_launch("mudg_adamw_scaled_ema_multi");
-}
-
-int mudg_loss_scale_update(void* record, float growth_factor, float backoff_factor, int growth_interval, void* stream) {
-    MUDG_REQUIRE(record && growth_factor > 1.f && backoff_factor > 0.f && backoff_factor < 1.f && growth_interval > 0,
-                 "mudg_loss_scale_update: bad arguments");
-    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<ScaleRecord*>(record),
-                       growth_factor, backoff_factor, growth_interval);
-    return mudg_check_launch("mudg_loss_scale_update");
 }
 
 int mudg_dropout(const float* x, float* out, int64_t n, float p, uint64_t seed, void* stream) {

@@ -1,4 +1,4 @@
-"""Tensor-level wrappers over the training entries of the C-ABI (csrc/train.hip).  fp32 rows matrices in, fp32 rows (or MFMA
+"""Tensor-level wrappers over the training entries of the C-ABI (csrc/train.hip; the optimiser's: csrc/optim.hip).  fp32 rows matrices in, fp32 rows (or MFMA
 operand matrices) out; nothing here computes."""
 import ctypes as C
 

@@ -131,23 +131,15 @@ class AdamW(torch.optim.Optimizer):
         return hit[1:]
 
     def _table(self, gi, ps):
-        from .. import hip
         # the table bakes in the addresses of the moments too: load_state_dict (or any reassignment of state[p][...]) replaces them
         key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
                      p.numel()) for p in ps)
         hit = self._tables.get(gi)
         if hit is not None and hit[0] == key:
             return hit[1], hit[2]
-        chunk = hip.lib().mudg_clip_chunk()
-        rows = []
-        for p in ps:
-            st = self.state[p]
-            base = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr())
-            n = p.numel()
-            rows.extend((*(a + 4 * off for a in base), min(chunk, n - off)) for off in range(0, n, chunk))
-        table = torch.tensor(rows, dtype=torch.int64).to(ps[0].device)
-        self._tables[gi] = (key, table, len(rows))
-        return table, len(rows)
+        table, n = K.chunk_table([(p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in ps])
+        self._tables[gi] = (key, table, n)
+        return table, n
 
     @torch.no_grad()
     def step(self, closure=None, ema=None, scaler=None):
@@ -244,10 +236,8 @@ class GradientClipper:
         key = tuple((g.data_ptr(), g.numel()) for g in grads)
         dev = grads[0].device
         if key != self._key:
-            chunk = hip.lib().mudg_clip_chunk()
-            rows = [(ptr + 4 * off, min(chunk, n - off)) for ptr, n in key for off in range(0, n, chunk)]
-            self._table = torch.tensor(rows, dtype=torch.int64).to(dev)
-            self._partial = torch.empty(len(rows), dtype=torch.float64, device=dev)
+            self._table, n = K.chunk_table([(g,) for g in grads])
+            self._partial = torch.empty(n, dtype=torch.float64, device=dev)
             self._key = key
         out = torch.empty(2, dtype=torch.float32, device=dev)
         hip.check(hip.lib().mudg_clip_grad_norm(self._table.data_ptr(), self._table.shape[0], self._partial.data_ptr(), self.max_norm,
@@ -310,14 +300,10 @@ class LossScaler:
 
     def _chunks(self, tensors):
         """(key, device table of (address, count) rows) over `tensors`."""
-        from .. import hip
         for g in tensors:
             if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
                 raise RuntimeError("LossScaler works on contiguous fp32 gradients on the GPU")
-        key = tuple((g.data_ptr(), g.numel()) for g in tensors)
-        chunk = hip.lib().mudg_clip_chunk()
-        rows = [(ptr + 4 * off, min(chunk, n - off)) for ptr, n in key for off in range(0, n, chunk)]
-        return key, torch.tensor(rows, dtype=torch.int64).to(tensors[0].device)
+        return tuple((g.data_ptr(), g.numel()) for g in tensors), K.chunk_table([(g,) for g in tensors])[0]
 
     @torch.no_grad()
     def norm_pass(self, params, max_norm=None):

@@ -1,4 +1,4 @@
-"""Every backward kernel of the training step (csrc/wgrad.hip, attention_bwd.hip, train.hip) called through its own C-ABI entry
+"""Every backward kernel of the training step (csrc/wgrad.hip, attention_bwd.hip, train.hip, optim.hip) called through its own C-ABI entry
 and held to the plain fp64 definition in tests/backward_reference.py — evaluated on the very operands the kernel reads (made on the
 CPU, rounded to the operand type once, the same values widened to fp64 for the reference), at shapes read off each kernel's dispatch
 and tiling code.
@@ -591,6 +591,81 @@ def test_multi_tensor_optimiser_kernels_against_their_definitions(cuda):
     for x, y, x0, y0 in zip(a, b, p0, sh0):
         assert torch.equal(x.cpu(), y0) and torch.equal(y.cpu(), x0)
     print(f"[backward {hip.operand_name()}] multi-tensor optimiser kernels: bit-equal to the single-tensor kernels and to their definitions")
+
+
+def test_the_multi_tensor_walk_at_its_edges_aligned_and_off_by_one_float(cuda):
+    """Every kernel on csrc/optim.hip's multi_walk, at the sizes where the walk changes course (a piece = 256 lanes x 4 floats, two
+    pieces per pass): 3 has no vector part; 1024 fills exactly the first piece and leaves the second empty; 1203 = 300 vectors + 3
+    has lanes 0..43 live in the second piece; 2053 = 513 vectors + 1 runs a second pass with one live lane.  Every tensor is a
+    view into its own sentinel-filled flat buffer: 16 bytes in (the vector branch), one float in (the scalar loop), and with the
+    gradient alone one float in (one unaligned operand turns the whole row scalar).  The four AdamW forms equal mudg_adamw per
+    tensor bit for bit — the scaled ones at scale 1 and coefficient 1, where (g * 1) * 1 is g —, the shadows equal the fp32
+    expression on the CPU, mudg_swap_multi exchanges bits, a set overflow flag leaves parameters and moments alone and moves the
+    shadows, and no sentinel changes.
+    The step is 1: the scaled forms take b^n from powf on the device, the others from powf on the host, and b^1 = b is the
+    exponent at which the two cannot differ."""
+    sizes, sentinel = [3, 1024, 1203, 2053], -12345.0
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    hp = dict(lr=f32(1e-3), betas=(f32(0.9), f32(0.999)), eps=f32(1e-8), weight_decay=f32(0.01))
+    omd = 0.0123
+    mk = lambda seed, scale=1.0: [rnd(n, seed=seed + i, scale=scale) for i, n in enumerate(sizes)]
+    p0, g0, m0, v0, sh0 = mk(1700), mk(1710, 0.1), mk(1720, 0.05), [t.abs() for t in mk(1730, 0.01)], mk(1740)
+    ref = [[t.to(cuda) for t in ts] for ts in (p0, g0, m0, v0)]                   # the yardstick: one tensor at a time, once
+    for t in zip(*ref):
+        K.adamw_(*t, step=1, **hp)
+    p1, _, m1, v1 = [[t.cpu() for t in ts] for ts in ref]
+    ema_of = lambda shadows, params: [s - torch.tensor(omd, dtype=torch.float32) * (s - p) for s, p in zip(shadows, params)]
+    stat = torch.tensor([0.25, 1.0], dtype=torch.float32).to(cuda)              # [norm, clip coefficient]
+    record = lambda flag: torch.tensor([0x3F800000, 0, flag, 0], dtype=torch.int32).to(cuda)      # scale 1.0, no step taken yet
+
+    def lay(operands, off_of):
+        """views[k][i]: tensor i of operand k, off_of(k) floats into a flat buffer of sentinels; and the check that they are intact."""
+        flats, views = [], []
+        for k, ts in enumerate(operands):
+            off = off_of(k)
+            row = []
+            for t in ts:
+                flat = torch.full((t.numel() + 8,), sentinel)
+                flat[off:off + t.numel()] = t
+                flats.append((flat.to(cuda), off, t.numel()))
+                row.append(flats[-1][0][off:off + t.numel()])
+                assert row[-1].data_ptr() % 16 == 4 * off % 16
+            views.append(row)
+
+        def intact():
+            for flat, off, n in flats:
+                flat = flat.cpu()
+                assert bool((flat[:off] == sentinel).all()) and bool((flat[off + n:] == sentinel).all()), "a sentinel was overwritten"
+        return views, intact
+
+    def run(what, off_of, launch, want, shadow=False):
+        views, intact = lay([p0, g0, m0, v0] + ([sh0] if shadow else []), off_of)
+        table, n = K.chunk_table(list(zip(*views)))
+        launch(table, n)
+        for k, (got, exp) in enumerate(zip(views, want)):
+            for i, (a, b) in enumerate(zip(got, exp)):
+                assert torch.equal(a.cpu(), b), (what, f"operand {k}", sizes[i])
+        intact()
+
+    for where, off_of in (("aligned", lambda k: 4), ("one float off", lambda k: 1), ("gradient alone off", lambda k: 1 if k == 1 else 4)):
+        run(f"mudg_adamw_multi, {where}", off_of, lambda t, n: K.adamw_multi_(t, n, step=1, **hp), (p1, g0, m1, v1))
+        run(f"mudg_adamw_ema_multi, {where}", off_of, lambda t, n: K.adamw_ema_multi_(t, n, step=1, one_minus_decay=omd, **hp),
+            (p1, g0, m1, v1, ema_of(sh0, p1)), shadow=True)
+        for flag, (p, m, v) in ((0, (p1, m1, v1)), (1, (p0, m0, v0))):
+            rec = record(flag)
+            run(f"mudg_adamw_scaled_multi, flag {flag}, {where}", off_of, lambda t, n: K.adamw_scaled_multi_(t, n, rec, stat, **hp), (p, g0, m, v))
+            moved = ema_of(sh0, p)
+            assert not any(torch.equal(a, b) for a, b in zip(moved, sh0))
+            run(f"mudg_adamw_scaled_ema_multi, flag {flag}, {where}", off_of,
+                lambda t, n: K.adamw_scaled_ema_multi_(t, n, rec, stat, one_minus_decay=omd, **hp), (p, g0, m, v, moved), shadow=True)
+            assert rec.cpu().tolist() == [0x3F800000, 0, flag, 0]
+        views, intact = lay([p0, sh0], off_of)
+        table, n = K.chunk_table(list(zip(*views)))
+        K.swap_multi_(table, n)
+        for a, b, a0, b0 in zip(*views, p0, sh0):
+            assert torch.equal(a.cpu(), b0) and torch.equal(b.cpu(), a0), ("mudg_swap_multi", where)
+        intact()
+    print(f"[backward {hip.operand_name()}] the multi-tensor walk at sizes {sizes}, aligned and off by one float: bit-equal, sentinels intact")
 
 
 # ================================================================================================ refusals

@@ -1,4 +1,4 @@
-"""Loss scaling on the GPU (mudg_amd.train.step.LossScaler; csrc/train.hip: mudg_scaled_grad_norm, mudg_adamw_scaled_multi,
+"""Loss scaling on the GPU (mudg_amd.train.step.LossScaler; csrc/optim.hip: mudg_scaled_grad_norm, mudg_adamw_scaled_multi,
 mudg_adamw_scaled_ema_multi, mudg_loss_scale_update) against the definition in tests/scaler_reference.py and the torch sequence it
 is held to on the CPU.  The file runs in the loaded build directly and once more in a child process in the fp16 build, the build the
 feature is for (the operand type is fixed per process).

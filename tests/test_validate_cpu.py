@@ -379,7 +379,7 @@ def test_new_entry_points_are_declared_and_bound():
 
 
 def test_multi_tensor_kernels_use_no_scratch_no_lds_and_16_byte_accesses(tmp_path):
-    """Facts about the generated gfx950 code that do not depend on the compiler's scheduling: the three streaming kernels and the
+    """Facts about the generated gfx950 code that do not depend on the compiler's scheduling: the six multi-tensor kernels and the
     sheet kernel use neither private memory nor LDS, and the multi-tensor ones address global memory (no flat_* access: the table's
     integers are typed as global pointers) with 16-byte loads and stores."""
     import shutil
@@ -388,7 +388,9 @@ def test_multi_tensor_kernels_use_no_scratch_no_lds_and_16_byte_accesses(tmp_pat
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    for src, kernels in (("train.hip", ("ema_multi_kernel", "swap_multi_kernel", "adamw_ema_multi_kernel")), ("post.hip", ("log_sheet_kernel",))):
+    multi = ("ema_multi_kernel", "swap_multi_kernel", "adamw_multi_kernel", "adamw_ema_multi_kernel", "adamw_scaled_multi_kernel",
+             "adamw_scaled_ema_multi_kernel")
+    for src, kernels in (("optim.hip", multi), ("post.hip", ("log_sheet_kernel",))):
         out = tmp_path / (src + ".s")
         subprocess.run([hipcc, *build.FLAGS, "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), "-S",
                         os.path.join(ROOT, "mudg_amd", "csrc", src), "-o", str(out)], check=True, capture_output=True, timeout=600)
@@ -401,7 +403,7 @@ def test_multi_tensor_kernels_use_no_scratch_no_lds_and_16_byte_accesses(tmp_pat
                     seen.add(family)
                     assert int(m.group(1)) == 0 and int(m.group(3)) == 0, m.groups()
         assert seen == set(kernels), seen
-        if src != "train.hip":
+        if src != "optim.hip":
             continue
         for family in kernels:
             (name,) = set(re.findall(r"^(_Z\S*\d%s\S*):" % family, s, re.M))
