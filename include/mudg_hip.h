@@ -515,6 +515,29 @@ int64_t mudg_depth_complete_scratch(int frames, int H, int W);
 int mudg_depth_complete(const float* depth, const int64_t* labels, int64_t sky_label, int frames, int H, int W, float max_depth,
                         int extrapolate, float* out, uint8_t* source, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ cross-view depth consistency (csrc/consistency.hip)
+ * (This project's own rule; the reference merges clouds by concatenation.)  A view is a depth map (H, W) fp32 metres with its camera;
+ * 1 .. 65535 views, H W <= 2^24.  fp64 operations in a stated order and integer sums: no output depends on execution order.
+ * view_flags: flags[view][H][W] bytes.  Bit 0 (usable) iff min_depth < z < max_depth and the label is not sky_label; bit 1 (dynamic) iff
+ *   0 <= label < 64 and bit `label` of dynamic_mask is set.  labels (views, H, W) int64 or NULL: nothing is sky, nothing is dynamic.
+ * view_consistency: src_table[view][16] doubles = the top three rows of camera-to-world, then fx, fy, cx, cy at (H, W) (depth_unproject's
+ *   table); wit_table[view][16] = the top three rows of world-to-camera, then the same four; times[view] int32; witnesses[view][N]
+ *   int32, N in 1 .. 64: -1 is empty, the view itself is skipped, the caller rejects anything else outside 0 .. views - 1 (the kernel
+ *   ignores it).  A usable pixel's world point P is depth_unproject's, kept in fp64.  Per witness w in order, skipped when the pixel is
+ *   dynamic and times differ: q = w2c_w P by rows ((m0 x + m1 y) + m2 z) + m3; no evidence unless qz > 1e-4; u = fx (qx / qz) + cx,
+ *   v likewise; no evidence unless 0 <= u < W and 0 <= v < H (on doubles); over the pixels within r (0 .. 2) of ((int)v, (int)u),
+ *   clipped to the image, that are usable (and not dynamic when times differ): d = qz - zw, tol = abs_tol + rel_tol qz; the witness
+ *   agrees if some |d| <= tol, violates if at least one pixel counts and every one has d < -tol, else gives no evidence.
+ *   agree, violate, keep [view][H][W] bytes: the witnesses with each verdict, and usable && agree >= min_agree && violate <=
+ *   max_violate; a pixel that is not usable stores 0, 0, 0.  stats[view][6] uint64 (zero on entry) receives the sums of: usable,
+ *   agree + violate > 0, keep, agree, violate, violate > 0. */
+int mudg_view_flags(const float* depth, const int64_t* labels, int64_t sky_label, uint64_t dynamic_mask, int views, int H, int W,
+                    double min_depth, double max_depth, uint8_t* flags, void* stream);
+int mudg_view_consistency(const float* depth, const uint8_t* flags, const double* src_table, const double* wit_table,
+                          const int32_t* times, const int32_t* witnesses, int views, int N, int H, int W, int r, int min_agree,
+                          int max_violate, double rel_tol, double abs_tol, uint8_t* agree, uint8_t* violate, uint8_t* keep,
+                          uint64_t* stats, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

@@ -190,11 +190,6 @@ __global__ __launch_bounds__(256) void colormap_spectral_kernel(const float* __r
     }
 }
 
-// ((m0 x + m1 y) + m2 z) + m3, as §13's row
-__device__ __forceinline__ double row4(const double* m, double x, double y, double z) {
-    return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m[0], x), __dmul_rn(m[1], y)), __dmul_rn(m[2], z)), m[3]);
-}
-
 template <int PX>
 __global__ __launch_bounds__(256) void depth_unproject_kernel(const float* __restrict__ depth, const uint8_t* __restrict__ rgb,
                                                                const int64_t* __restrict__ labels, long long sky_label,

@@ -1,5 +1,6 @@
-// depth_shared.h — what the per-pixel kernels over (frames, H, W) maps share (depth.hip, normals.hip): the four-pixel and one-pixel
-// loads of a lane, the frame limits of their entries and the grid that puts the frame in blockIdx.y.
+// depth_shared.h — what the per-pixel kernels over (frames, H, W) maps share (depth.hip, normals.hip, consistency.hip): the four-pixel
+// and one-pixel loads of a lane, the row of a rigid transform, the frame limits of their entries and the grid that puts the frame in
+// blockIdx.y.
 #pragma once
 #include "common.h"
 
@@ -31,6 +32,11 @@ __device__ __forceinline__ void load_sky(const int64_t* __restrict__ labels, int
     } else {
         sky[0] = labels[at] == sky_label;
     }
+}
+
+// ((m0 x + m1 y) + m2 z) + m3, as §13's row
+__device__ __forceinline__ double row4(const double* m, double x, double y, double z) {
+    return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m[0], x), __dmul_rn(m[1], y)), __dmul_rn(m[2], z)), m[3]);
 }
 
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }

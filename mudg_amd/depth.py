@@ -210,11 +210,12 @@ def depth_labels_from_lidar(scene, frame_ids, hw_out=None, labels=None, **kw):
     return lidar, dense, source
 
 
-def lift_views(depth, rgb, intr, c2w, hw_native, labels=None, *, min_depth=0.0, max_depth=MAX_DEPTH, sky_label=SKY_LABEL):
+def lift_views(depth, rgb, intr, c2w, hw_native, labels=None, *, min_depth=0.0, max_depth=MAX_DEPTH, sky_label=SKY_LABEL, keep=None):
     """Generated views as coloured world-space points in the renderer's packed format.  depth: (T, H, W) fp32 metres; rgb: (T, H, W, 3)
     uint8; intr: (3, 3) or (T, 3, 3) at hw_native; c2w: (T, 4, 4), the poses the views were generated at (OpenCV convention);
     labels: (T, H, W) int64 or None.  A pixel becomes a point iff min_depth < depth < max_depth and it is not sky — with the defaults
-    the sky's 100 m is out.  Returns a render.PointCloud in (frame, row, column) order."""
+    the sky's 100 m is out — and, with keep ((T, H, W) uint8: consistent_views' "keep"), keep is non-zero there.  Returns a render.PointCloud in
+    (frame, row, column) order."""
     rgb = _on_gpu("lift_views", "the colour stream", rgb, torch.uint8)
     if rgb.dim() != 4 or rgb.shape[3] != 3:
         raise hip.MudgError(f"lift_views: expected (T, H, W, 3) colours, got {tuple(rgb.shape)}")
@@ -222,9 +223,101 @@ def lift_views(depth, rgb, intr, c2w, hw_native, labels=None, *, min_depth=0.0, 
     depth = _on_gpu("lift_views", "the depth", depth, torch.float32, shape)
     if labels is not None:
         labels = _on_gpu("lift_views", "the label image", labels, torch.int64, shape)
+    if keep is not None:
+        keep = _on_gpu("lift_views", "the keep bytes", keep, torch.uint8, shape)
     table = camera_table(intr, c2w, hw_native, shape[1:])
     if table.shape[0] != shape[0]:
         raise hip.MudgError(f"lift_views: {table.shape[0]} cameras for {shape[0]} frames")
     points, valid = ops.depth_unproject(depth, rgb, torch.from_numpy(table).to(rgb.device), labels, sky_label=sky_label, min_depth=min_depth,
                                         max_depth=max_depth)
-    return render.PointCloud(points[valid.bool()])                           # stable: (frame, row, column) order
+    chosen = valid.bool() if keep is None else valid.bool() & (keep.reshape(-1) != 0)
+    return render.PointCloud(points[chosen])                                 # stable: (frame, row, column) order
+
+
+# ------------------------------------------------------------------------------------------------ cross-view consistency
+def witness_table(c2w, source_table=None):
+    """Host, float64: the top three rows of every view's world-to-camera matrix (cloud.inverse_rigid of c2w (V, 4, 4)), (V, 12) — with
+    source_table (camera_table's (V, 16)) followed by its fx, fy, cx, cy: (V, 16), the witness rows of ops.view_consistency."""
+    from . import cloud
+    c2w = np.asarray(c2w, dtype=np.float64)
+    if c2w.ndim != 3 or c2w.shape[1:] != (4, 4):
+        raise hip.MudgError(f"witness_table: cameras {c2w.shape}, expected (V, 4, 4)")
+    rows = np.stack([cloud.inverse_rigid(m).reshape(12) for m in c2w]) if len(c2w) else np.zeros((0, 12))
+    if source_table is None:
+        return rows
+    source_table = np.asarray(source_table, dtype=np.float64)
+    if source_table.shape != (c2w.shape[0], 16):
+        raise hip.MudgError(f"witness_table: source table {source_table.shape} for {c2w.shape[0]} cameras")
+    return np.concatenate([rows, source_table[:, 12:]], axis=1)
+
+
+def default_witnesses(times, poses=None, reach=2):
+    """Host: the witness lists of a view set, (V, N) int32.  times (V,): the frame each view shows; poses (V,): its pose's number, or
+    None: every view is a pose of its own, so that views of one frame always witness each other.  View v's list holds the other poses
+    of its own frame first, then every view (of any pose, its own included) whose frame is 1 .. reach frames away — each group in
+    ascending view number — and is padded with -1 to the longest list (at least one column)."""
+    times = np.asarray(times)
+    poses = np.arange(times.size).reshape(times.shape) if poses is None else np.asarray(poses)
+    if times.ndim != 1 or times.shape != poses.shape or times.dtype.kind not in "iu" or poses.dtype.kind not in "iu" or int(reach) < 0:
+        raise hip.MudgError(f"default_witnesses: times {times.shape} {times.dtype} and poses {poses.shape} {poses.dtype} (two integer vectors of one "
+                            f"length), reach {reach}")
+    times = times.astype(np.int64)
+    lists = []
+    for v in range(len(times)):
+        gap = np.abs(times - times[v])
+        same = [w for w in range(len(times)) if w != v and gap[w] == 0 and poses[w] != poses[v]]
+        near = [w for w in range(len(times)) if 0 < gap[w] <= int(reach)]
+        lists.append(same + near)
+    n = max([len(l) for l in lists] + [1])
+    if n > ops.VIEW_MAX_WITNESSES:
+        raise hip.MudgError(f"default_witnesses: {n} witnesses for a view, at most {ops.VIEW_MAX_WITNESSES}")
+    out = np.full((len(lists), n), -1, dtype=np.int32)
+    for v, l in enumerate(lists):
+        out[v, :len(l)] = l
+    return out
+
+
+def consistent_views(depth, intr, c2w, hw_native, labels=None, *, times=None, witnesses=None, reach=None, min_depth=0.0, max_depth=MAX_DEPTH,
+                     sky_label=SKY_LABEL, dynamic_mask=ops.VIEW_DYNAMIC_MASK, r=1, min_agree=2, max_violate=0, rel_tol=0.02, abs_tol=0.2):
+    """Which pixels of a set of views the other views confirm (a rule of this project's own).  depth: (V, H, W) fp32
+    metres, a window's frames x poses flattened; intr: (3, 3) or (V, 3, 3) at hw_native; c2w: (V, 4, 4); labels: (V, H, W) int64 or None
+    (nothing is sky, nothing is dynamic); times: (V,) host integers, the frame each view shows (default 0 .. V-1: every view its own
+    frame); witnesses: (V, N <= 64) host integers, -1 for empty (default: default_witnesses(times, None, reach) — every other view whose
+    frame is at most reach frames away, those of the view's own frame first; reach defaults to 2 and is refused beside witnesses).  A usable pixel (lift_views' validity) is lifted to its world point and projected into each witness; a witness agrees
+    if a usable pixel within r of the projection has a depth within abs_tol + rel_tol z of the point's, violates if every such pixel
+    lies farther — it saw through the point — and otherwise says nothing; a pixel tagged dynamic (dynamic_mask: a bit per class) is
+    tested against, and counted by, views of its own time only.  keep = usable, agree >= min_agree and violate <= max_violate.
+    Returns {"agree", "violate", "keep", "flags": (V, H, W) uint8, "stats": (V, 6) int64 — usable, tested, kept, sum agree, sum violate,
+    pixels with a violation}; metrics.view_consistency turns the stats into scores."""
+    depth = _on_gpu("consistent_views", "the depth", depth, torch.float32)
+    if depth.dim() != 3:
+        raise hip.MudgError(f"consistent_views: expected (V, H, W) depths, got {tuple(depth.shape)}")
+    if labels is not None:
+        labels = _on_gpu("consistent_views", "the label image", labels, torch.int64, depth.shape)
+    V = depth.shape[0]
+    source = camera_table(intr, c2w, hw_native, depth.shape[1:])
+    if source.shape[0] != V:
+        raise hip.MudgError(f"consistent_views: {source.shape[0]} cameras for {V} views")
+    times = np.arange(V, dtype=np.int32) if times is None else np.asarray(times)
+    if witnesses is not None and reach is not None:
+        raise hip.MudgError("consistent_views: reach makes the default witness lists; with witnesses given it would be ignored — give one of the two")
+    if witnesses is None:
+        witnesses = default_witnesses(times, None, 2 if reach is None else reach)
+    flags = ops.view_flags(depth, labels, sky_label=sky_label, dynamic_mask=dynamic_mask, min_depth=min_depth, max_depth=max_depth)
+    tables = torch.from_numpy(np.stack([source, witness_table(c2w, source)])).to(depth.device)
+    agree, violate, keep, stats = ops.view_consistency(depth, flags, tables[0], tables[1], times, witnesses, r=r, min_agree=min_agree,
+                                                       max_violate=max_violate, rel_tol=rel_tol, abs_tol=abs_tol)
+    return {"agree": agree, "violate": violate, "keep": keep, "stats": stats, "flags": flags}
+
+
+def fuse_views(depth, rgb, intr, c2w, hw_native, labels=None, *, voxel_size=-1, **rule):
+    """consistent_views, then lift_views of the pixels it keeps, then (voxel_size > 0) cloud.voxel_downsample: generated views as one
+    filtered cloud.  **rule: consistent_views' keywords (times, witnesses or reach — not both —, the bounds and the tolerances).  Returns
+    (render.PointCloud, consistent_views' result)."""
+    from . import cloud
+    result = consistent_views(depth, intr, c2w, hw_native, labels, **rule)
+    bounds = {k: rule[k] for k in ("min_depth", "max_depth", "sky_label") if k in rule}
+    points = lift_views(depth, rgb, intr, c2w, hw_native, labels, keep=result["keep"], **bounds)
+    if voxel_size > 0 and len(points):
+        points = cloud.voxel_downsample(points, voxel_size)
+    return points, result

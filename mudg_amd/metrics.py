@@ -1,5 +1,6 @@
 """Scores of generated views against the truths that are already on the GPU: PSNR and SSIM for colour, depth errors against the rendered
-LiDAR depth, class IoU for the semantic stream, angular errors for the normal stream.
+LiDAR depth, class IoU for the semantic stream, angular errors for the normal stream — and, against no truth at all, how far the views
+of a window agree with one another (view_consistency).
 
 The reference has no scoring code (its eval_tools.py writes files, its validation_step logs the loss); its paper reports these
 numbers.  The rules here are this project's own and DESIGN.md §15 states them: every kernel of csrc/metrics.hip reduces a frame to a
@@ -95,6 +96,25 @@ def normal_errors(pred_u8, gt_normals, valid=None):
     nan = torch.full_like(n, float("nan"))
     return {"n": counted, "mean": (hist * odd).sum(1).to(_D) / (8.0 * n), "median": torch.where(counted > 0, (2 * middle + 1).to(_D) / 8.0, nan),
             "a11": below[:, 44].to(_D) / n, "a22": below[:, 89].to(_D) / n, "a30": below[:, 119].to(_D) / n, "hist": hist}
+
+
+def view_consistency(result):
+    """result: depth.consistent_views' dict (or its "stats", (V, 6) int64).  The one score of a generated window that needs no truth
+    (DESIGN.md §21), from the integer counts, as Python floats: {"tested": the share of each view's usable pixels that some witness gave
+    a verdict on, "kept": the share kept, "violated": the share a witness saw through, "mean_agree": agreeing witnesses per tested
+    pixel — each a list of V floats — and "overall": the same four over all views}; nan where nothing was usable (or tested).  Brings
+    V x 6 integers to the host."""
+    stats = result["stats"] if isinstance(result, dict) else result
+    stats = _on_gpu("view_consistency", "the statistics", stats, torch.int64)
+    if stats.dim() != 2 or stats.shape[1] != 6:
+        raise hip.MudgError(f"view_consistency: expected (V, 6) statistics, got {tuple(stats.shape)}")
+    rows = stats.cpu().tolist()
+    share = lambda a, b: a / b if b else float("nan")
+    one = lambda s: {"tested": share(s[1], s[0]), "kept": share(s[2], s[0]), "violated": share(s[5], s[0]), "mean_agree": share(s[3], s[1])}
+    views = [one(s) for s in rows]
+    scores = {k: [v[k] for v in views] for k in ("tested", "kept", "violated", "mean_agree")}
+    scores["overall"] = one([sum(s[k] for s in rows) for k in range(6)])
+    return scores
 
 
 def score_window(outputs, *, color=None, lidar_depth=None, labels=None, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH, classes=CLASSES):

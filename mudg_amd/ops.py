@@ -908,6 +908,76 @@ def depth_unproject(depth, rgb, table, labels=None, *, sky_label=10, min_depth=0
     return points, valid
 
 
+# ------------------------------------------------------------------------------------------------ cross-view depth consistency
+VIEW_MAX_WITNESSES = 64          # per view (csrc/consistency.hip): the verdict counts fit a byte
+VIEW_MAX_RADIUS = 2
+VIEW_DYNAMIC_MASK = sum(1 << c for c in range(11, 19))      # the movable classes of semantic_nearest's 19: person .. bicycle
+
+
+def _view_depths(name, depth):
+    _splat_tensor(f"{name}: depth", depth, torch.float32)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise hip.MudgError(f"{name}: expected (views, h, w) fp32 depths, got {tuple(depth.shape)}")
+    return tuple(depth.shape)
+
+
+def view_flags(depth, labels=None, *, sky_label=10, dynamic_mask=VIEW_DYNAMIC_MASK, min_depth=0.0, max_depth=100.0):
+    """depth (v, h, w) fp32 metres and labels (v, h, w) int64 or None -> flags (v, h, w) uint8: bit 0 usable iff
+    min_depth < depth < max_depth and the label is not sky_label, bit 1 dynamic iff 0 <= label < 64 and that bit of dynamic_mask is set."""
+    v, h, w = _view_depths("view_flags", depth)
+    if labels is not None:
+        _splat_tensor("view_flags: labels", labels, torch.int64, (v, h, w))
+    mask = int(dynamic_mask)
+    if not 0 <= mask < 1 << 64:
+        raise hip.MudgError(f"view_flags: dynamic_mask {dynamic_mask} (64 bits, one per class)")
+    flags = torch.empty((v, h, w), dtype=torch.uint8, device=depth.device)
+    hip.check(hip.lib().mudg_view_flags(depth.data_ptr(), _ptr(labels), int(sky_label), mask, v, h, w, float(min_depth), float(max_depth),
+                                        flags.data_ptr(), _stream()), "mudg_view_flags")
+    return flags
+
+
+def view_witness_lists(times, witnesses, views):
+    """The host side of view_consistency's argument check, which the entry point cannot make on device memory: times (views,) and
+    witnesses (views, 1 .. 64) integer host arrays, every witness id -1 (empty) or 0 .. views - 1.  Returns both as contiguous int32."""
+    import numpy as np
+    if torch.is_tensor(times) or torch.is_tensor(witnesses):
+        raise hip.MudgError("view_consistency: times and witnesses are host arrays (their ids are checked before the launch)")
+    times, witnesses = np.asarray(times), np.asarray(witnesses)
+    if times.shape != (views,) or witnesses.ndim != 2 or witnesses.shape[0] != views or not 1 <= witnesses.shape[1] <= VIEW_MAX_WITNESSES \
+            or times.dtype.kind not in "iu" or witnesses.dtype.kind not in "iu":
+        raise hip.MudgError(f"view_consistency: times {times.shape} {times.dtype} and witnesses {witnesses.shape} {witnesses.dtype} for {views} views "
+                            f"(integers, (views,) and (views, 1 .. {VIEW_MAX_WITNESSES}))")
+    if int(witnesses.min()) < -1 or int(witnesses.max()) >= views:
+        raise hip.MudgError(f"view_consistency: witness ids in [{int(witnesses.min())}, {int(witnesses.max())}] for {views} views (-1: empty, else 0 .. {views - 1})")
+    if int(times.min()) < -2 ** 31 or int(times.max()) >= 2 ** 31:
+        raise hip.MudgError("view_consistency: time ids are 32-bit integers")
+    return np.ascontiguousarray(times, dtype=np.int32), np.ascontiguousarray(witnesses, dtype=np.int32)
+
+
+def view_consistency(depth, flags, src_table, wit_table, times, witnesses, *, r=1, min_agree=2, max_violate=0, rel_tol=0.02, abs_tol=0.2):
+    """depth (v, h, w) fp32, flags (v, h, w) uint8 of view_flags, src_table and wit_table (v, 16) float64 on the GPU (camera-to-world and
+    world-to-camera rows, each followed by fx, fy, cx, cy); times (v,) and witnesses (v, n) integers on the HOST (view_witness_lists checks
+    them before anything is launched).  Returns (agree, violate, keep (v, h, w) uint8, stats (v, 6) int64: usable, tested, kept, sum
+    agree, sum violate, pixels with a violation) by DESIGN.md §21's rule."""
+    v, h, w = _view_depths("view_consistency", depth)
+    _splat_tensor("view_consistency: flags", flags, torch.uint8, (v, h, w))
+    _splat_tensor("view_consistency: src_table", src_table, torch.float64, (v, 16))
+    _splat_tensor("view_consistency: wit_table", wit_table, torch.float64, (v, 16))
+    times, witnesses = view_witness_lists(times, witnesses, v)
+    if r not in range(VIEW_MAX_RADIUS + 1) or int(min_agree) < 0 or int(max_violate) < 0 or not (float(rel_tol) >= 0.0 and float(abs_tol) >= 0.0):
+        raise hip.MudgError(f"view_consistency: r {r} (0 .. {VIEW_MAX_RADIUS}), min_agree {min_agree}, max_violate {max_violate}, rel_tol {rel_tol}, "
+                            f"abs_tol {abs_tol} (none negative)")
+    dev = depth.device
+    times_d, wit_d = torch.from_numpy(times).to(dev), torch.from_numpy(witnesses).to(dev)
+    agree, violate, keep = (torch.empty((v, h, w), dtype=torch.uint8, device=dev) for _ in range(3))
+    stats = torch.zeros((v, 6), dtype=torch.int64, device=dev)
+    hip.check(hip.lib().mudg_view_consistency(depth.data_ptr(), flags.data_ptr(), src_table.data_ptr(), wit_table.data_ptr(), times_d.data_ptr(),
+                                              wit_d.data_ptr(), v, witnesses.shape[1], h, w, int(r), int(min_agree), int(max_violate), float(rel_tol),
+                                              float(abs_tol), agree.data_ptr(), violate.data_ptr(), keep.data_ptr(), stats.data_ptr(), _stream()),
+              "mudg_view_consistency")
+    return agree, violate, keep, stats
+
+
 # ------------------------------------------------------------------------------------------------ scores of generated views
 SSIM_WINDOW = (67, 498, 2359, 7167, 13960, 17434, 13960, 7167, 2359, 498, 67)     # DESIGN.md §15: the taps sum to 2^16
 SSIM_TILE = 32                   # outputs per side of one workgroup of mudg_metric_ssim

@@ -170,3 +170,37 @@ def window_outputs(samples, window_conditions, variant=0):
     metric = depth.metric_depth(u8[1], lidar[0], labels, visualise=True)
     return {"color": u8[0], "semantic_labels": labels, "semantic": torch.stack(vis).permute(0, 2, 3, 1).contiguous(),
             "depth": metric["depth"], "depth_vis": metric["vis"], "coef": metric["coef"], "fitted": metric["fitted"]}
+
+
+def fuse_window_outputs(outputs_by_pose, scene, frame_ids, poses, **rule):
+    """One window generated at several poses -> one filtered cloud and the window's consistency scores.
+
+    outputs_by_pose: window_outputs' dicts of the same window, one per entry of poses; scene: the mudg_amd.render.Scene the window was
+    rendered from; frame_ids: the window's frames, positions in the scene's cameras; poses: as render_windows takes them, 0 / 1 / 2 or
+    a (4, 4) camera-from-virtual-camera matrix each.  The views are stacked pose by pose, a view's time id is its frame and its
+    witnesses are mudg_amd.depth.default_witnesses' — the other poses of its frame, then every view within `reach` frames — so a pixel
+    tagged as a movable class is compared across poses of its own frame only.  **rule: mudg_amd.depth.fuse_views' keywords
+    (voxel_size, r, min_agree, max_violate, rel_tol, abs_tol, ..., and either reach or witnesses, not both).  Returns (mudg_amd.render.PointCloud of the kept pixels,
+    mudg_amd.metrics.view_consistency's scores with the device result under "result")."""
+    import numpy as np
+    from mudg_amd import depth, metrics, render
+    frame_ids = [int(f) for f in frame_ids]
+    if len(outputs_by_pose) != len(poses) or not poses or not frame_ids:
+        raise ValueError(f"fuse_window_outputs: {len(outputs_by_pose)} outputs for {len(poses)} poses and {len(frame_ids)} frames")
+    c2w = np.asarray(scene.c2w, dtype=np.float64)[frame_ids]
+    intr = np.broadcast_to(np.asarray(scene.intr, dtype=np.float64), (np.asarray(scene.c2w).shape[0], 3, 3))[frame_ids]
+    cams = [np.stack([render.virtual_poses(c, with_ori_pose=True)[int(p)] for c in c2w]) if np.ndim(p) == 0 else c2w @ np.asarray(p, dtype=np.float64)
+            for p in poses]
+    for out in outputs_by_pose:
+        if out["depth"].shape[0] != len(frame_ids):
+            raise ValueError(f"fuse_window_outputs: outputs of {out['depth'].shape[0]} frames for frames {frame_ids}")
+    stack = lambda name: torch.cat([out[name] for out in outputs_by_pose])
+    times = np.tile(np.asarray(frame_ids, dtype=np.int32), len(poses))
+    pose_ids = np.repeat(np.arange(len(poses), dtype=np.int32), len(frame_ids))
+    if "witnesses" not in rule:                                               # given lists go through as they are (reach beside them is refused)
+        rule["witnesses"] = depth.default_witnesses(times, pose_ids, rule.pop("reach", 2))
+    cloud, result = depth.fuse_views(stack("depth"), stack("color"), np.concatenate([intr] * len(poses)), np.concatenate(cams), scene.hw_native,
+                                     stack("semantic_labels"), times=times, **rule)
+    scores = metrics.view_consistency(result)
+    scores["result"] = result
+    return cloud, scores
