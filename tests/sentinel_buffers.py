@@ -2,10 +2,12 @@
 a flat allocation filled with NaN (0xA5 for bytes), and reading it back asserts that nothing outside the view was written.  Unlike
 `gapped` / `check_operand` of tests/test_backward_kernels_gpu.py (2-D views, 16-byte rows) this form states base pointers that are off by
 one element, row strides that are no multiple of 8, batch strides, piece planes and uint8 payloads, which the forward GEMM descriptors need.
-All views are in bounds."""
+All views are in bounds.  `Flat` is the one-dimensional sibling for the scene kernels: int64, int32, float32 and uint8 payloads inside
+an integer sentinel, compared byte for byte."""
 import torch
 
 NAN = float("nan")
+BYTE = 0xA5                                            # the sentinel byte: as a word neither 0, -1, a key of a small cloud nor a 24-bit colour
 
 
 class Buf:
@@ -48,3 +50,51 @@ class Buf:
         clean = bool((flat == 0xA5).all()) if self.dtype == torch.uint8 else bool(torch.isnan(flat.float()).all())
         assert clean, f"{name}: elements outside the view (gap columns / guard rows) were written"
         return pieces
+
+
+class Flat:
+    """`n` contiguous elements of int64, int32, float32 or uint8 inside a flat sentinel-filled allocation, `off` elements past a front of
+    FRONT elements (so `off` alone decides the alignment of the base pointer).  The sentinel is the byte 0xA5 repeated (BYTE), an integer
+    pattern that is neither an empty splat key (-1), a key of a small cloud nor a 24-bit colour; nan=True (float32 operands that a kernel
+    only reads) fills with NaN instead, so that a read of the padding shows in the result.  Everything is compared as bytes: read()
+    returns the view and asserts that every byte outside it still holds the sentinel, unchanged() that nothing at all was written."""
+    FRONT, TAIL = 256, 264
+
+    def __init__(self, n, dtype, *, off=0, nan=False):
+        assert dtype in (torch.int64, torch.int32, torch.float32, torch.uint8) and not (nan and dtype != torch.float32)
+        self.n, self.dtype, self.off = int(n), dtype, int(off)
+        total = self.FRONT + self.off + self.n + self.TAIL
+        if nan:
+            self.cpu = torch.full((total,), NAN, dtype=dtype)
+        else:
+            self.cpu = torch.full((total * torch.empty((), dtype=dtype).element_size(),), BYTE, dtype=torch.uint8).view(dtype)
+        self.sentinel = self.cpu.clone()
+        self.dev = None
+
+    def view(self, flat):
+        return flat[self.FRONT + self.off:self.FRONT + self.off + self.n]
+
+    def put(self, payload, dev):
+        payload = torch.as_tensor(payload).reshape(-1)
+        assert payload.dtype == self.dtype and payload.numel() == self.n, (payload.dtype, payload.numel(), self.dtype, self.n)
+        self.view(self.cpu).copy_(payload)
+        self.dev = self.cpu.to(dev)
+        return self
+
+    def blank(self, dev):
+        self.dev = self.cpu.to(dev)
+        return self
+
+    @property
+    def ptr(self):
+        return self.dev.data_ptr() + (self.FRONT + self.off) * self.dev.element_size()
+
+    def read(self, name):
+        flat = self.dev.cpu()
+        got = self.view(flat).clone()
+        self.view(flat).copy_(self.view(self.sentinel))
+        assert torch.equal(flat.view(torch.uint8), self.sentinel.view(torch.uint8)), f"{name}: elements outside the view were written"
+        return got
+
+    def unchanged(self, name):
+        assert torch.equal(self.dev.cpu().view(torch.uint8), self.cpu.view(torch.uint8)), f"{name}: was written"

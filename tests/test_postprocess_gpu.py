@@ -36,6 +36,10 @@ def test_postprocess_matches_oracle_on_frame_sized_inputs(cuda):
     wv, wl = pp.visualize_semantic(img.numpy())
     assert np.array_equal(lab.cpu().numpy(), wl) and np.array_equal(vis.cpu().numpy(), wv)
     assert int(lab.min()) >= 0 and int(lab.max()) <= 18
+    odd = torch.randint(0, 256, (3, 23, 29), generator=gen, dtype=torch.uint8)         # 667 pixels: the last workgroup's tail i >= hw runs
+    vis, lab = ops.semantic_nearest(odd.to(cuda))
+    wv, wl = pp.visualize_semantic(odd.numpy())
+    assert lab.shape == (23, 29) and np.array_equal(lab.cpu().numpy(), wl) and np.array_equal(vis.cpu().numpy(), wv)
 
 
 def test_eval_tools_mirror_keeps_the_reference_signature(cuda):
