@@ -133,6 +133,10 @@ int mudg_gemm_stats_rows(const MudgGemmDesc* d);
 /* 1 when `d` (mode 1, subpixel = 1) can run: batch 4, stride 1, pad 1, korder 1, Cin % 64 == 0, no X2 / R / gbias / stats /
  * upsample, and offsets within reach of the buffer-descriptor loader; else the caller uses upsample = 1 with 3x3 weights. */
 int mudg_conv_subpixel_ok(const MudgGemmDesc* d);
+/* 1 when mudg_gemm runs `d` on the stream kernel of the 16-bit builds (plain GEMMs with K = 320 and N = 320 or 640, a 16-bit result and residual, no
+ * GroupNorm partials, frames of whole 288-row tiles: the same sums as the 288 x 320-tile kernel, so no result depends on the answer).
+ * Needs a current device (the kernel's grid is its CU count); 0 without one.  For tests and measurements. */
+int mudg_gemm_stream_ok(const MudgGemmDesc* d);
 
 /* ------------------------------------------------------------------ attention
  * Flash-style softmax(scale * Q K^T) V for head dim 64, never materialising the score matrix.

@@ -883,6 +883,7 @@ struct GemmSwitches {
     int h144 = mudg_variant("GEMM_H144", 1), h144pf = mudg_variant("GEMM_H144PF", 1);
     int h144delay = mudg_variant("GEMM_H144DELAY", 0) | (mudg_variant("GEMM_H144ABL", 0) << 16) | (mudg_variant("GEMM_H144PRIO", 1) ? 0 : 1 << 20);
     int w160 = mudg_variant("GEMM_W160", 1), w160defer = mudg_variant("GEMM_W160DEFER", 1);
+    int stream = mudg_variant("GEMM_STREAM", 1);
 };
 
 // Whether the buffer-descriptor (FAST) kernels can run this problem.  Variant switch GEMM_FAST=0 forces the generic
@@ -1078,6 +1079,28 @@ bool wgemm288_ok(const MudgGemmDesc& d, int vflags, const GemmSwitches& sw) {
     return true;
 }
 
+// The stream kernel (sgemm.hip; 16-bit builds): K = 320 plain GEMMs with a 320-column slice of W resident in a workgroup's registers, rows
+// streamed through LDS.  Returns its grid (one workgroup per CU, whole XCDs, a multiple of 8 N / 320), or 0 where another kernel runs the problem.
+// Takes: mode 0, K == 320, N == 320 or 640 (two slices: the q | k projection of the long self-attention), 16-bit Y (operand or fp16 stream)
+// and residual, and what the 288-row tile takes of such a problem (wgemm_eligible: batch 1, no activation / fp8 copy, 16-byte pieces on Y
+// and R, a residual that may seed the accumulators, offsets within the 32-bit reach of a tile's descriptors); no second source, group bias
+// or GEGLU.  No GroupNorm partials: a problem with `stats` stays on the 288-row tile, whose per-288-row partials it would have to reproduce.
+// Same bits as the 288-row tile (tests/test_gemm_stream_gpu.py), so only the measurement decides where it runs; it still follows the
+// tile's own rule and never looks at M, because the kernels BELOW the 288-row tile add a residual last, not first.
+// Variant switch GEMM_STREAM: 0 = never, 1 = the rule — exactly the problems that wgemm288_ok's rule (GEMM_W288 = 1) hands to wgemm_kernel,
+// and none when GEMM_W288 / GEMM_W288P / GEMM_W288Q force a kernel —, 2 = every problem the kernel can run (ragged M included),
+// 3 = the rule without the two-slice problems (measurements).
+int stream_grid(const MudgGemmDesc& d, int vflags, const GemmSwitches& sw) {
+    if (PLANES != 1 || !sw.stream) return 0;
+    if (d.mode != 0 || d.K != 320 || (d.N != 320 && d.N != 640) || d.X2 || d.gbias || d.geglu || d.stats) return 0;
+    if (sw.stream == 3 && d.N != 320) return 0;
+    if (d.out_fp32 == KIND_F32 || (d.R && d.res_fp32 == KIND_F32)) return 0;
+    if (!wgemm_eligible(d, vflags, WBM)) return 0;
+    if (sw.stream != 2 && !(sw.w288 == 1 && sw.w288p != 2 && sw.w288q != 2 && wgemm288_ok(d, vflags, sw))) return 0;
+    const int n = mudg_cu_count(), slices = d.N / 320;
+    return n <= 0 ? 0 : ((n < 8 ? 8 : n) / (8 * slices)) * 8 * slices;
+}
+
 // The 160-row tile (wq_kernel<..., 5>): frames of whole 160-row tiles that are not whole 288-row tiles.  Variant switch GEMM_W160: 0 = never,
 // 1 = the rule, 2 = every eligible problem (as GEMM_W288 = 2; the 288-row tile's own rule is asked first).
 bool w160_ok(const MudgGemmDesc& d, int vflags, const GemmSwitches& sw) {
@@ -1111,7 +1134,7 @@ void normalise_desc(MudgGemmDesc& d) {
 
 // THE kernel choice of mudg_gemm, for a normalised descriptor: which kernel runs the problem and everything its launch needs.  A pure function
 // of the descriptor, the variant switches and the CU count: it launches nothing and does not fail.  mudg_gemm launches what it names,
-// mudg_gemm_stats_rows reports its `rows`.  Precedence: the 288-row tile, the 160-row tile, then — on the descriptor loader — the wide
+// mudg_gemm_stats_rows reports its `rows`.  Precedence: the stream kernel, the 288-row tile, the 160-row tile, then — on the descriptor loader — the wide
 // tiles, the persistent kernel, the single-buffer and the double-buffer kernel; the generic 128 x 128 kernel for everything else.
 GemmPlan gemm_plan(const MudgGemmDesc& d) {
     const GemmSwitches sw;
@@ -1125,7 +1148,11 @@ GemmPlan gemm_plan(const MudgGemmDesc& d) {
         d.K == 9 * d.Cin && (d.Cin & 63) == 0)
         p.vflags |= VF_XS;
     p.rows = 128;
-    if (PLANES <= 2 && wgemm288_ok(d, p.vflags, sw)) {
+    if (const int sg = stream_grid(d, p.vflags, sw); sg > 0) {
+        p.rows = WBM;
+        p.kernel = GK_STREAM;
+        p.grid = sg;
+    } else if (PLANES <= 2 && wgemm288_ok(d, p.vflags, sw)) {
         p.rows = WBM;
         // The 288-row tile on the loop of the 160-row one (wq_kernel<..., 9>), variant builds only.  Variant switch GEMM_W288Q: 0 = never (the
         // rule: wgemm_kernel's six-phase loop), 2 = every one-tile problem of the 288-row tile (GEGLU included).  Measured per shape against the
@@ -1173,6 +1200,14 @@ extern "C" int mudg_gemm_stats_rows(const MudgGemmDesc* dp) {
     if (d.out_fp32 < 0 || d.out_fp32 > 2 || d.res_fp32 < 0 || d.res_fp32 > 2 || d.mode < 0 || d.mode > 2) return 128;
     normalise_desc(d);
     return gemm_plan(d).rows;
+}
+
+extern "C" int mudg_gemm_stream_ok(const MudgGemmDesc* dp) {
+    if (!dp) return 0;
+    MudgGemmDesc d = *dp;
+    if (d.out_fp32 < 0 || d.out_fp32 > 2 || d.res_fp32 < 0 || d.res_fp32 > 2 || d.mode < 0 || d.mode > 2) return 0;
+    normalise_desc(d);
+    return gemm_plan(d).kernel == GK_STREAM ? 1 : 0;
 }
 
 extern "C" int mudg_conv_subpixel_ok(const MudgGemmDesc* dp) {
@@ -1261,6 +1296,7 @@ extern "C" int mudg_gemm(const MudgGemmDesc* dp, void* stream) {
     case GK_WIDE: rc = plan.ni == 5 ? by_mode(G320{}, std::true_type{}, std::false_type{}) : by_mode(G256{}, std::true_type{}, std::false_type{}); break;
 #endif
     case GK_PERSIST: rc = mudg_pgemm_launch(d, plan, s); break;
+    case GK_STREAM: rc = mudg_sgemm_launch(d, plan, s); break;
     default: rc = mudg_wgemm_launch(d, plan, s); break;
     }
     const double flops = 2.0 * d.M * (double)d.N * d.K * d.batch;          // algorithmic (the split builds issue NSEG times as many)

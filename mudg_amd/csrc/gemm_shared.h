@@ -1,8 +1,9 @@
-// gemm_shared.h — what the contraction kernels of gemm.hip, pgemm.hip and wgemm.hip have in common: K-tile geometry, the buffer-descriptor
+// gemm_shared.h — what the contraction kernels of gemm.hip, pgemm.hip, wgemm.hip and sgemm.hip have in common: K-tile geometry, the buffer-descriptor
 // helpers of the LDS-DMA loader, the GELU forms and the row steps of the epilogues (one site per rule), and the kernel plan (GemmPlan) that
 // gemm.hip makes and the launchers take.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 constexpr int BK = 64;
 constexpr int LDSLD = 64;                       // h16 elements per LDS row: unpadded, XOR-swizzled (see gemm.hip)
@@ -161,6 +162,27 @@ __device__ __forceinline__ void add_residual_raw(float (&v)[4], const u32x2 a, c
     }
 }
 
+// The bits a wide store of a piece of 16-bit storage holds: the fp16 stream saturates (f16_sat), a one-plane operand matrix rounds to
+// nearest even.  For the kernels that store through a buffer descriptor (sgemm.hip) instead of a pointer; store_piece's W = 4 pieces are these.
+template <int W>
+__device__ __forceinline__ auto f16_bits(const float (&v)[W]) {
+    static_assert(W == 8 || W == 4, "a piece is 8 or 4 channels");
+    union { std::conditional_t<W == 8, u32x4, u32x2> w; _Float16 h[W]; } t;
+#pragma unroll
+    for (int j = 0; j < W; ++j) t.h[j] = f16_sat(v[j]);
+    return t.w;
+}
+#if MUDG_PLANES == 1
+template <int W>
+__device__ __forceinline__ auto operand_bits(const float (&v)[W]) {
+    static_assert(W == 8 || W == 4, "a piece is 8 or 4 channels");
+    union { std::conditional_t<W == 8, u32x4, u32x2> w; h16 h[W]; } t;
+#pragma unroll
+    for (int j = 0; j < W; ++j) t.h[j] = (h16)v[j];
+    return t.w;
+}
+#endif
+
 // Store a piece at element offset yoff of Y in storage kind `kind` (ps: plane stride of an operand matrix, ldy / PLANES): one 16-byte
 // store per plane (fp32: two; W = 4: 8-byte stores, fp32 one 16-byte) when `wide`, else its first nvalid values one by one.
 template <int W>
@@ -171,12 +193,7 @@ __device__ __forceinline__ void store_piece(void* Y, const int64_t yoff, const i
         _Float16* yp = reinterpret_cast<_Float16*>(Y) + yoff;
         if (wide) {
             if constexpr (W == 8) store8_f16(yp, v);
-            else {
-                union { u32x2 w; _Float16 h[4]; } t;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) t.h[j] = f16_sat(v[j]);
-                *reinterpret_cast<u32x2*>(yp) = t.w;
-            }
+            else *reinterpret_cast<u32x2*>(yp) = f16_bits(v);
         } else {
 #pragma unroll
             for (int j = 0; j < W; ++j) if (j < nvalid) yp[j] = f16_sat(v[j]);
@@ -282,6 +299,7 @@ __device__ __forceinline__ u32x2 mx8_pack8(const float (&r8)[8], const float inv
 // Host side.  Tile heights of wgemm.hip: the 288-row tile (wgemm_kernel, wgemm_pkernel, wq_kernel<..., 9>) and the 160-row tile
 // (wq_kernel<..., 5>); what the GroupNorm partial blocks of a problem are cut to where one of them runs it.
 constexpr int WBM = 288, QBM = 160;
+constexpr int SBM = 64;                                  // tile height of the stream kernel (sgemm.hip)
 const float* mudg_phi_table(bool split_ok = false);      // device Phi table, or nullptr (split-operand builds unless split_ok in bf16x3 / variant switch)
 
 // What mudg_gemm runs for a problem and every parameter of that launch: chosen once, by gemm_plan (gemm.hip).
@@ -296,6 +314,7 @@ enum GemmKernel {
     GK_W288Q,            // wq_kernel<..., 9> (variant builds)
     GK_H144,             // hgeglu_kernel (16-bit builds)
     GK_W160,             // wq_kernel<..., 5> (16-bit builds)
+    GK_STREAM,           // sgemm_kernel (sgemm.hip; 16-bit builds)
 };
 struct GemmPlan {
     GemmKernel kernel;
@@ -303,10 +322,11 @@ struct GemmPlan {
     int rows;            // height of the GroupNorm partial blocks: 288 | 160 | 128
     int ni;              // GK_WIDE: NI of the wide tile (5: 256 x 320, 4: 256 x 256)
     int wgs;             // GK_PERSIST: workgroups per CU (4 | 3: one K-tile stage, 2: two)
-    int grid;            // GK_W288P: workgroups
+    int grid;            // GK_W288P, GK_STREAM: workgroups
     int rs;              // GK_W160: the residual — 0 none, 1 seeds the accumulators, 2 deferred to the epilogue
     bool pf;             // GK_H144: the prefetching K loop
     int delay;           // GK_H144: the measurement knobs of hgeglu_kernel (variant switches GEMM_H144DELAY / ABL / PRIO)
 };
 int mudg_pgemm_launch(const MudgGemmDesc& d, const GemmPlan& plan, hipStream_t s);       // GK_PERSIST
 int mudg_wgemm_launch(const MudgGemmDesc& d, const GemmPlan& plan, hipStream_t s);       // GK_W288 ... GK_W160
+int mudg_sgemm_launch(const MudgGemmDesc& d, const GemmPlan& plan, hipStream_t s);       // GK_STREAM

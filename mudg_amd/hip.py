@@ -132,6 +132,7 @@ SIGNATURES = {
     "mudg_gemm": (_I, [C.POINTER(GemmDesc), _P]),
     "mudg_gemm_stats_rows": (_I, [C.POINTER(GemmDesc)]),
     "mudg_conv_subpixel_ok": (_I, [C.POINTER(GemmDesc)]),
+    "mudg_gemm_stream_ok": (_I, [C.POINTER(GemmDesc)]),
     "mudg_attention": (_I, [C.POINTER(AttnDesc), _P]),
     "mudg_quantize_mxfp8": (_I, [_P, _I, _L, _I, _P, _I, _P, _I, _P]),
     "mudg_temporal_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),

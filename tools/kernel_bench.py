@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the kernels at the shapes the MDM1024 UNet issues (B = 1): TFLOP/s or GB/s per launch.
 Run on the GPU box:  python tools/kernel_bench.py [filter]
-`python tools/kernel_bench.py fused` is the table behind the rule of the fused temporal self-attention (fused_temporal below)."""
+`python tools/kernel_bench.py fused` is the table behind the rule of the fused temporal self-attention (fused_temporal below);
+`MUDG_DEBUG_VARIANTS=1 python tools/kernel_bench.py stream` times the stream kernel (csrc/sgemm.hip) against the kernels it replaces."""
 import os
 import sys
 
@@ -91,10 +92,48 @@ def fused_temporal(T=16):
             torch.cuda.empty_cache()
 
 
+def stream_projections(T=16):
+    """The square projections of an MDM1024 step (two clips: cond + uncond), the stream kernel (MUDG_GEMM_STREAM=1: its rule) against the
+    tile kernels (= 0), alternating in one process — the debug-variants library reads the switch at every call.  Median (min..max) of 7
+    timings of 10 back-to-back launches.  Back-to-back launches of one shape find part of their operands in the 256-MiB last-level
+    cache: the rule is decided inside a step (tools/shape_profile.py), this table says what a launch costs at best.  The kernel takes
+    K = 320 with N = 320 or 640; the level-1 rows show what the switch leaves alone."""
+    from mudg_amd import hip
+    if os.environ.get("MUDG_DEBUG_VARIANTS") != "1":
+        sys.exit("stream: run with MUDG_DEBUG_VARIANTS=1 (the library that reads MUDG_GEMM_STREAM)")
+    F16 = torch.float16
+    print("| shape (M x N x K) | flags | algorithmic MB | tiles us (min..max) | stream us (min..max) | stream TB/s | stream / tiles |")
+    print("|---|---|---:|---:|---:|---:|---:|")
+    shapes = [(2 * T * 9216, 320, 320, 9216), (2 * T * 2304, 640, 640, 2304), (2 * T * 9216, 640, 320, 9216)]
+    for M, n, k, hw in shapes:
+        for flags in ("bias, fp16 residual, fp16 out", "bias", "none"):
+            if n != k and flags != "none":
+                continue
+            x, w = rn(M, k), rn(n, k)
+            bias = torch.randn(n, device=dev) if flags != "none" else None
+            res = rn(M, n, dtype=F16) if "residual" in flags else None
+            out = torch.empty(M, n, device=dev, dtype=F16 if res is not None else BF)
+            call = lambda: ops.gemm(x, w, out=out, bias=bias, residual=res, frame_rows=hw)
+            t = {}
+            for rep in range(2):                           # tiles, stream, tiles, stream: the second pair is reported
+                for sw in ("0", "1"):
+                    os.environ["MUDG_GEMM_STREAM"] = sw
+                    t[sw] = spread(call)
+            mb = (M * k + n * k + M * n * (2 if res is not None else 1)) * 2 / 1e6
+            us = lambda v: f"{v[0] * 1e6:.1f} ({v[1] * 1e6:.1f}..{v[2] * 1e6:.1f})"
+            print(f"| {M} x {n} x {k} | {flags} | {mb:.0f} | {us(t['0'])} | {us(t['1'])} | {mb / t['1'][0] / 1e6:.2f} | {t['1'][0] / t['0'][0]:.3f} |",
+                  flush=True)
+            del x, w, out, res
+            torch.cuda.empty_cache()
+    os.environ.pop("MUDG_GEMM_STREAM", None)
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
     if flt == "fused":
         return fused_temporal()
+    if flt == "stream":
+        return stream_projections()
     T = 16
     levels = [(72 * 128, 320), (36 * 64, 640), (18 * 32, 1280), (9 * 16, 1280)]
     if "gemm" in flt or not flt:
