@@ -542,6 +542,26 @@ int mudg_view_consistency(const float* depth, const uint8_t* flags, const double
                           int max_violate, double rel_tol, double abs_tol, uint8_t* agree, uint8_t* violate, uint8_t* keep,
                           uint64_t* stats, void* stream);
 
+/* ------------------------------------------------------------------ neighbour search between clouds (csrc/neighbours.hip)
+ * The reference's pipeline takes radius outlier removal from open3d; the rule here is this project's own: brute force within r, found
+ * through a grid.  Points are §12's packed 16 bytes.  r in (0, 64], r2 = r r, cell = r (1 + 2^-10), all doubles formed by the caller;
+ * a point's cell is floor(double(p) / cell) per axis and its key cloud_voxel_keys' at voxel = cell.  ref_sorted: the n reference points
+ * in ascending key order (|cell index| <= 2^20 - 2, checked by the caller); keys: their keys; order: each one's original index.
+ * visit (or NULL): a permutation of 0 .. nq - 1, the order in which lanes take the queries (by cell, so that a wave's candidates share
+ * cache lines); results are stored at the query's own position.  A query's candidates are the nine key intervals (ix + a, iy + b,
+ * iz - 1 .. iz + 1); p is within reach iff d2 = ((dx dx + dy dy) + dz dz) <= r2 in fp64, d = double(q) - double(p).  A query with a
+ * coordinate that is not finite, or with |q / cell| >= 2^20 + 1, finds nothing.
+ * cloud_nearest: d2[q] = the smallest d2 within reach (+inf: none), index[q] = the lowest original index that attains it (-1: none).
+ * cloud_count: counts[q] = min(points within reach, cap), cap >= 1.
+ * metric_cloud: n < 2^31 such d2 values and K <= 8 squared thresholds t2 (host memory, 0 < t2[k] <= r2) -> sums[2 + K] int64 (zero on
+ *   entry) receive the number of finite values, the sum over them of floor(sqrt(d2) 2^20) (d2 taken into [0, r2]), and the counts of
+ *   d2 <= t2[k]. */
+int mudg_cloud_nearest(const void* ref_sorted, const int64_t* keys, const int64_t* order, int64_t n, const void* queries,
+                       const int64_t* visit, int64_t nq, double cell, double r2, double* d2, int64_t* index, void* stream);
+int mudg_cloud_count(const void* ref_sorted, const int64_t* keys, const int64_t* order, int64_t n, const void* queries,
+                     const int64_t* visit, int64_t nq, double cell, double r2, int cap, int32_t* counts, void* stream);
+int mudg_metric_cloud(const double* d2, int64_t n, const double* t2_host, int K, double r2, int64_t* sums, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

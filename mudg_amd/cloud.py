@@ -155,6 +155,91 @@ def voxel_downsample(cloud: render.PointCloud, voxel_size) -> render.PointCloud:
     return render.PointCloud(ops.cloud_voxel_finish(ops.cloud_voxel_reduce(pts, order, segments, v, voxels), v))
 
 
+# ------------------------------------------------------------------------------------------------ neighbour search
+class NeighbourGrid:
+    """A reference cloud ready to be searched within `radius`: `points` (n, 4) int32 in ascending cell-key order, `keys` (n,) int64,
+    `order` (n,) int64 — the original index of each sorted point —, and the doubles `radius`, `cell` = radius (1 + 2^-10), `r2`."""
+
+    def __init__(self, points, keys, order, radius, cell, r2):
+        self.points, self.keys, self.order, self.radius, self.cell, self.r2 = points, keys, order, radius, cell, r2
+
+    def __len__(self):
+        return self.points.shape[0]
+
+    @classmethod
+    def build(cls, cloud: render.PointCloud, radius):
+        """Keys (mudg_cloud_voxel_keys at the cell edge), a stable sort, a gather.  A radius outside (0, 64], an empty cloud, or
+        coordinates beyond 2^20 - 2 cells — so that a neighbour cell always fits the key — raise before anything is launched."""
+        if not isinstance(cloud, render.PointCloud):
+            raise hip.MudgError("NeighbourGrid.build: expected a render.PointCloud (on the GPU; there is no CPU path)")
+        try:
+            r = float(radius)
+        except (TypeError, ValueError):
+            raise hip.MudgError(f"NeighbourGrid.build: radius {radius!r}") from None
+        if not (0.0 < r <= ops.NEIGHBOUR_MAX_RADIUS):
+            raise hip.MudgError(f"NeighbourGrid.build: radius {radius} (0 < radius <= {ops.NEIGHBOUR_MAX_RADIUS:g})")
+        if len(cloud) == 0:
+            raise hip.MudgError("NeighbourGrid.build: an empty cloud")
+        cell = r * ops.NEIGHBOUR_MARGIN
+        pts = cloud.points
+        lo, hi = (float(t) for t in torch.aminmax(pts[:, :3].view(torch.float32)))    # the bounds, to the host: nothing is launched on a bad cloud
+        if not (np.isfinite(lo) and np.isfinite(hi)) or np.floor(lo / cell) < -(KEY_LIMIT - 2) or np.floor(hi / cell) > KEY_LIMIT - 2:
+            raise hip.MudgError(f"NeighbourGrid.build: coordinates in [{lo}, {hi}] leave the grid at radius {r} (|cell index| <= 2^20 - 2)")
+        keys, order = torch.sort(ops.cloud_voxel_keys(pts, cell), stable=True)
+        return cls(pts[order].contiguous(), keys, order, r, cell, r * r)
+
+
+def _queries(name, grid, queries):
+    if not isinstance(grid, NeighbourGrid):
+        raise hip.MudgError(f"{name}: expected a NeighbourGrid (NeighbourGrid.build makes one)")
+    points = queries.points if isinstance(queries, render.PointCloud) else queries
+    if not torch.is_tensor(points) or not points.is_cuda or points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 4:
+        raise hip.MudgError(f"{name}: expected the queries as a render.PointCloud or packed (nq, 4) int32 points on the GPU (there is no CPU path)")
+    return points.contiguous()
+
+
+def _visit(grid, points):
+    """The queries in the order of their own cells: a wave's lanes then walk the same or adjacent intervals.  Any permutation gives the
+    same results — a query outside the key's range, or one that is not finite, merely gets an arbitrary place in it."""
+    return torch.sort(ops.cloud_voxel_keys(points, grid.cell))[1]
+
+
+def nearest(grid, queries):
+    """For every query (a render.PointCloud or packed points) the nearest point of the grid's cloud within its radius: (d2 (nq,) float64,
+    index (nq,) int64) in the caller's order — the squared distance in fp64 and the point's index in the cloud the grid was built
+    from, the lowest on a tie; +inf and -1 where nothing is within the radius."""
+    points = _queries("nearest", grid, queries)
+    if points.shape[0] == 0:
+        return torch.empty((0,), dtype=torch.float64, device=points.device), torch.empty((0,), dtype=torch.int64, device=points.device)
+    return ops.cloud_nearest(grid.points, grid.keys, grid.order, points, grid.cell, grid.r2, visit=_visit(grid, points))
+
+
+def neighbour_counts(grid, queries, cap):
+    """min(points of the grid's cloud within its radius, cap) for every query, (nq,) int32."""
+    if not (isinstance(cap, (int, np.integer)) and 1 <= cap < 2 ** 31):
+        raise hip.MudgError(f"neighbour_counts: cap {cap!r} (an integer, at least 1)")
+    points = _queries("neighbour_counts", grid, queries)
+    if points.shape[0] == 0:
+        return torch.empty((0,), dtype=torch.int32, device=points.device)
+    return ops.cloud_count(grid.points, grid.keys, grid.order, points, grid.cell, grid.r2, int(cap), visit=_visit(grid, points))
+
+
+def radius_outliers(cloud: render.PointCloud, radius, min_neighbours):
+    """The keep mask (n,) bool of a radius outlier filter: a point stays iff at least min_neighbours other points of the cloud lie
+    within radius of it (a duplicate at its own position is another point).  A rule of this project — parity with open3d's
+    remove_radius_outlier is not claimed."""
+    if not (isinstance(min_neighbours, (int, np.integer)) and 0 <= min_neighbours < 2 ** 31 - 1):
+        raise hip.MudgError(f"radius_outliers: min_neighbours {min_neighbours!r} (an integer, at least 0)")
+    grid = NeighbourGrid.build(cloud, radius)
+    need = int(min_neighbours) + 1                                          # a point counts itself
+    return neighbour_counts(grid, cloud, need) >= need
+
+
+def remove_outliers(cloud: render.PointCloud, radius, min_neighbours) -> render.PointCloud:
+    """The points radius_outliers keeps, in their order."""
+    return render.PointCloud(cloud.points[radius_outliers(cloud, radius, min_neighbours)])
+
+
 def _arrays(points):
     """Packed points on the GPU -> host (n, 3) float32 and (n, 3) uint8."""
     p = points.cpu()

@@ -310,14 +310,17 @@ def consistent_views(depth, intr, c2w, hw_native, labels=None, *, times=None, wi
     return {"agree": agree, "violate": violate, "keep": keep, "stats": stats, "flags": flags}
 
 
-def fuse_views(depth, rgb, intr, c2w, hw_native, labels=None, *, voxel_size=-1, **rule):
-    """consistent_views, then lift_views of the pixels it keeps, then (voxel_size > 0) cloud.voxel_downsample: generated views as one
-    filtered cloud.  **rule: consistent_views' keywords (times, witnesses or reach — not both —, the bounds and the tolerances).  Returns
-    (render.PointCloud, consistent_views' result)."""
+def fuse_views(depth, rgb, intr, c2w, hw_native, labels=None, *, voxel_size=-1, neighbour_radius=None, min_neighbours=0, **rule):
+    """consistent_views, then lift_views of the pixels it keeps, then (neighbour_radius given) cloud.remove_outliers — a point stays iff
+    min_neighbours others lie within neighbour_radius metres: the flying pixels every view shares are isolated in space
+    —, then (voxel_size > 0) cloud.voxel_downsample: generated views as one filtered cloud.  **rule: consistent_views' keywords (times,
+    witnesses or reach — not both —, the bounds and the tolerances).  Returns (render.PointCloud, consistent_views' result)."""
     from . import cloud
     result = consistent_views(depth, intr, c2w, hw_native, labels, **rule)
     bounds = {k: rule[k] for k in ("min_depth", "max_depth", "sky_label") if k in rule}
     points = lift_views(depth, rgb, intr, c2w, hw_native, labels, keep=result["keep"], **bounds)
+    if neighbour_radius is not None and len(points):
+        points = cloud.remove_outliers(points, neighbour_radius, min_neighbours)
     if voxel_size > 0 and len(points):
         points = cloud.voxel_downsample(points, voxel_size)
     return points, result

@@ -187,6 +187,9 @@ SIGNATURES = {
     "mudg_depth_complete": (_I, [_P, _P, _L, _I, _I, _I, _F, _I, _P, _P, _P, _L, _P]),
     "mudg_view_flags": (_I, [_P, _P, _L, C.c_uint64, _I, _I, _I, _D, _D, _P, _P]),
     "mudg_view_consistency": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
+    "mudg_cloud_nearest": (_I, [_P, _P, _P, _L, _P, _P, _L, _D, _D, _P, _P, _P]),
+    "mudg_cloud_count": (_I, [_P, _P, _P, _L, _P, _P, _L, _D, _D, _I, _P, _P]),
+    "mudg_metric_cloud": (_I, [_P, _L, _P, _I, _D, _P, _P]),
     "mudg_short_attention_ok": (_I, [C.POINTER(ShortAttnDesc)]),
     "mudg_short_attention": (_I, [C.POINTER(ShortAttnDesc), _P]),
     "mudg_layernorm_f32": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P]),

@@ -1,6 +1,7 @@
 """Scores of generated views against the truths that are already on the GPU: PSNR and SSIM for colour, depth errors against the rendered
 LiDAR depth, class IoU for the semantic stream, angular errors for the normal stream — and, against no truth at all, how far the views
-of a window agree with one another (view_consistency).
+of a window agree with one another (view_consistency).  A fused cloud is scored against the scene's LiDAR cloud by
+cloud_scores: accuracy, completeness and F-score at distance thresholds and the mean nearest-neighbour distances.
 
 The reference has no scoring code (its eval_tools.py writes files, its validation_step logs the loss); its paper reports these
 numbers.  The rules here are this project's own and DESIGN.md §15 states them: every kernel of csrc/metrics.hip reduces a frame to a
@@ -115,6 +116,41 @@ def view_consistency(result):
     scores = {k: [v[k] for v in views] for k in ("tested", "kept", "violated", "mean_agree")}
     scores["overall"] = one([sum(s[k] for s in rows) for k in range(6)])
     return scores
+
+
+def cloud_scores(pred, truth, thresholds=(0.05, 0.1, 0.2, 0.5)):
+    """Two render.PointClouds — a reconstruction (depth.fuse_views') and a truth (cloud.build_scene_clouds' background) — and up to
+    eight ascending distance thresholds in metres, each in (0, 64].  Every point looks for its nearest neighbour in the
+    other cloud within max(thresholds): pred in truth for accuracy, truth in pred for completeness.  Returns {"accuracy", "completeness":
+    (K,) float64, the shares of all points with a neighbour within each threshold; "fscore": 2 a c / (a + c), nan at 0 / 0; "found":
+    (2,) the shares with a neighbour within the radius at all; "mean_accuracy", "mean_completeness": the mean distance in metres over
+    the found points (on a 2^-20 grid, rounded down; nan when nothing is found); "chamfer": their sum; "sums": (2, 2 + K) int64, the
+    integers everything comes from}."""
+    from . import cloud, render
+    if not isinstance(pred, render.PointCloud) or not isinstance(truth, render.PointCloud):
+        raise hip.MudgError("cloud_scores: expected two render.PointClouds (on the GPU; there is no CPU path)")
+    try:
+        th = [float(t) for t in thresholds]
+    except (TypeError, ValueError):
+        raise hip.MudgError(f"cloud_scores: thresholds {thresholds!r}") from None
+    if not 1 <= len(th) <= ops.CLOUD_MAX_THRESHOLDS or not all(0.0 < t <= ops.NEIGHBOUR_MAX_RADIUS for t in th) or any(b <= a for a, b in zip(th, th[1:])):
+        raise hip.MudgError(f"cloud_scores: thresholds {thresholds!r} (1 .. {ops.CLOUD_MAX_THRESHOLDS} ascending distances in (0, {ops.NEIGHBOUR_MAX_RADIUS:g}])")
+    if len(pred) == 0 or len(truth) == 0:
+        raise hip.MudgError(f"cloud_scores: clouds of {len(pred)} and {len(truth)} points")
+    radius, t2 = th[-1], [t * t for t in th]
+    rows = []
+    for queries, reference in ((pred, truth), (truth, pred)):
+        grid = cloud.NeighbourGrid.build(reference, radius)
+        rows.append(ops.metric_cloud(cloud.nearest(grid, queries)[0], t2, grid.r2))
+    sums = torch.stack(rows)
+    s = sums.to(_D)
+    const = lambda v: torch.full((), float(v), dtype=_D, device=sums.device)
+    total = torch.stack([const(len(pred)), const(len(truth))])
+    share = s[:, 2:] / total[:, None]
+    a, c = share[0], share[1]
+    mean = s[:, 1] / (const(2.0 ** 20) * s[:, 0])                            # 0 / 0 = nan: nothing found
+    return {"accuracy": a, "completeness": c, "fscore": (2.0 * a * c) / (a + c), "found": s[:, 0] / total, "mean_accuracy": mean[0],
+            "mean_completeness": mean[1], "chamfer": mean[0] + mean[1], "sums": sums}
 
 
 def score_window(outputs, *, color=None, lidar_depth=None, labels=None, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH, classes=CLASSES):

@@ -834,6 +834,64 @@ def cloud_voxel_finish(sums, voxel):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ neighbour search between clouds
+NEIGHBOUR_MAX_RADIUS = 64.0
+NEIGHBOUR_MARGIN = 1.0 + 2.0 ** -10        # cell edge / radius
+CLOUD_MAX_THRESHOLDS = 8
+
+
+def _neighbour_args(name, ref_sorted, keys, order, queries, visit):
+    _splat_tensor(f"{name}: the sorted reference", ref_sorted, torch.int32)
+    n = ref_sorted.shape[0]
+    if ref_sorted.dim() != 2 or ref_sorted.shape[1] != 4 or n == 0:
+        raise hip.MudgError(f"{name}: expected packed reference points (n > 0, 4), got {tuple(ref_sorted.shape)}")
+    _splat_tensor(f"{name}: keys", keys, torch.int64, (n,))
+    _splat_tensor(f"{name}: order", order, torch.int64, (n,))
+    _splat_tensor(f"{name}: queries", queries, torch.int32)
+    nq = queries.shape[0]
+    if queries.dim() != 2 or queries.shape[1] != 4 or nq == 0:
+        raise hip.MudgError(f"{name}: expected packed queries (nq > 0, 4), got {tuple(queries.shape)}")
+    if visit is not None:
+        _splat_tensor(f"{name}: visit", visit, torch.int64, (nq,))
+    return n, nq
+
+
+def cloud_nearest(ref_sorted, keys, order, queries, cell, r2, *, visit=None):
+    """The nearest reference point within reach of every query.  ref_sorted (n, 4) int32 packed points in ascending key
+    order, keys and order (n,) int64 (cloud.NeighbourGrid holds all three), queries (nq, 4) int32, visit (nq,) int64 or None: the order
+    in which the lanes take the queries.  Returns (d2 (nq,) float64, +inf where nothing is within reach; index (nq,) int64, -1 there)."""
+    n, nq = _neighbour_args("cloud_nearest", ref_sorted, keys, order, queries, visit)
+    d2 = torch.empty((nq,), dtype=torch.float64, device=queries.device)
+    index = torch.empty((nq,), dtype=torch.int64, device=queries.device)
+    hip.check(hip.lib().mudg_cloud_nearest(ref_sorted.data_ptr(), keys.data_ptr(), order.data_ptr(), n, queries.data_ptr(), _ptr(visit), nq,
+                                           float(cell), float(r2), d2.data_ptr(), index.data_ptr(), _stream()), "mudg_cloud_nearest")
+    return d2, index
+
+
+def cloud_count(ref_sorted, keys, order, queries, cell, r2, cap, *, visit=None):
+    """min(reference points within reach, cap) of every query, (nq,) int32; the arguments of cloud_nearest and cap >= 1."""
+    n, nq = _neighbour_args("cloud_count", ref_sorted, keys, order, queries, visit)
+    counts = torch.empty((nq,), dtype=torch.int32, device=queries.device)
+    hip.check(hip.lib().mudg_cloud_count(ref_sorted.data_ptr(), keys.data_ptr(), order.data_ptr(), n, queries.data_ptr(), _ptr(visit), nq,
+                                         float(cell), float(r2), int(cap), counts.data_ptr(), _stream()), "mudg_cloud_count")
+    return counts
+
+
+def metric_cloud(d2, t2, r2):
+    """d2 (n,) float64, cloud_nearest's; t2: up to eight squared thresholds (host floats, 0 < t2 <= r2) -> (2 + K,) int64: the number of
+    finite values, the sum over them of floor(sqrt(d2) 2^20), the counts of d2 <= t2[k]."""
+    _splat_tensor("metric_cloud: d2", d2, torch.float64)
+    if d2.dim() != 1 or d2.numel() == 0:
+        raise hip.MudgError(f"metric_cloud: expected (n > 0,) squared distances, got {tuple(d2.shape)}")
+    t2 = [float(t) for t in t2]
+    if len(t2) > CLOUD_MAX_THRESHOLDS:
+        raise hip.MudgError(f"metric_cloud: {len(t2)} thresholds (at most {CLOUD_MAX_THRESHOLDS})")
+    sums = torch.zeros((2 + len(t2),), dtype=torch.int64, device=d2.device)
+    table = (hip.C.c_double * max(len(t2), 1))(*t2)                         # read by the call itself, before it returns
+    hip.check(hip.lib().mudg_metric_cloud(d2.data_ptr(), d2.numel(), table, len(t2), float(r2), sums.data_ptr(), _stream()), "mudg_metric_cloud")
+    return sums
+
+
 # ------------------------------------------------------------------------------------------------ metric depth and lifted views
 def _depth_frames(name, frames):
     _splat_tensor(f"{name}: frames", frames, torch.uint8)
