@@ -562,6 +562,56 @@ int mudg_cloud_count(const void* ref_sorted, const int64_t* keys, const int64_t*
                      const int64_t* visit, int64_t nq, double cell, double r2, int cap, int32_t* counts, void* stream);
 int mudg_metric_cloud(const double* d2, int64_t n, const double* t2_host, int K, double r2, int64_t* sums, void* stream);
 
+/* ------------------------------------------------------------------ clouds as 3D Gaussians (csrc/gaussians.hip)
+ * The forward half of a tile-binned Gaussian splat renderer.  A Gaussian is a packed point of §12, six fp32 covariance entries
+ * (xx, xy, xz, yy, yz, zz) in the point's own frame, an fp32 opacity and a matrix id (clamped to 0 .. nmat - 1; ids NULL: nmat = 1).
+ * A call draws V views: mats (V, nmat, 12) fp32 as in mudg_splat_points, one camera fx, fy, cx, cy, pixel centres at i + 0.5.  Tiles are
+ * 16 x 16 pixels, TX = ceil(W / 16), TY = ceil(H / 16), NT = TX TY, V NT < 2^31.  Every operation is a single rounded fp32 one in the
+ * order written (division and root correctly rounded); min / max return the operand that is a number.  Every entry returns MUDG_EINVAL
+ * before any launch for null arguments, unaligned points, n, V, nmat, H or W <= 0, V NT >= 2^31, E outside 1 .. 2^31 - 1, more
+ * workgroups than a grid holds, and znear, zfar that are not finite with 0 < znear < zfar.
+ *
+ * project, a lane per Gaussian, all V views:
+ *   xc, yc, zc = ((m0 x + m1 y) + m2 z) + m3 per row; dropped unless znear < zc < zfar
+ *   u = fx (xc / zc) + cx, v = fy (yc / zc) + cy
+ *   limx = 1.3 (0.5 W / fx), tx = min(limx, max(-limx, xc / zc)) zc; likewise limy, ty
+ *   j00 = fx / zc, j02 = -(fx tx) / (zc zc), j11 = fy / zc, j12 = -(fy ty) / (zc zc)
+ *   T0k = j00 R0k + j02 R2k, T1k = j11 R1k + j12 R2k with R = M[:, :3];  Vrk = (Tr0 S0k + Tr1 S1k) + Tr2 S2k
+ *   a = ((V00 T00 + V01 T01) + V02 T02) + 0.3, b = (V00 T10 + V01 T11) + V02 T12, c = ((V10 T10 + V11 T11) + V12 T12) + 0.3
+ *   det = a c - b b, dropped unless 0 < det < inf;  A = c / det, B = -b / det, C = a / det
+ *   mid = 0.5 (a + c), lam = mid + sqrt(max(0.1, mid mid - det)), rad = ceil(3 sqrt(lam)); dropped unless rad <= 4096
+ *   dropped unless 1 / 255 <= opacity < inf
+ *   x0 = clamp(floor((u - rad) / 16), 0, TX), x1 = clamp(floor((u + rad) / 16) + 1, 0, TX) in fp32, then converted; likewise y0, y1
+ *   count = (x1 - x0)(y1 - y0), dropped if 0
+ *   outputs per (view, Gaussian): uv (V, n, 2), conic (V, n, 4) = (A, B, C, opacity), depth (V, n) = zc, rect (V, n, 4) =
+ *   (x0, x1, y0, y1), count (V, n); all zero where dropped.  conic and rect 16-byte aligned, uv 8-byte aligned.
+ * keys, a lane per (view, Gaussian): offsets (V n) int64 = the exclusive sum of count, E its total; tile k of the rectangle in
+ *   row-major order writes keys[offsets + k] = (view NT + tile) << 32 | bits(zc) and values[offsets + k] = the Gaussian's index.  A
+ *   rectangle outside the tile grid, a count that is not its rectangle's or an offset outside [0, E - count] writes nothing.
+ * ranges, a lane per entry of the keys sorted ascending: ranges (tiles = V NT, 2) int32 is zeroed by the call; where an entry's tile
+ *   differs from its predecessor's (or it is the first) ranges[tile][0] = e, from its successor's (or it is the last) ranges[tile][1] =
+ *   e + 1.  Plain stores; a tile outside 0 .. tiles - 1 is ignored.
+ * blend, a workgroup of 256 lanes per (view, tile), a lane per pixel (px, py) = (i + 0.5, j + 0.5); pixels outside the image store
+ *   nothing.  T = 1, Ck = 0, D = 0; the tile's entries in sorted order (staged through LDS 256 at a time; the workgroup leaves at a
+ *   batch's start once every pixel is done):
+ *     dx = u - px, dy = v - py, q = (A dx) dx + (C dy) dy, p = (-0.5 q) - (B dx) dy; skipped if p > 0 or p < -5.55
+ *     g = E(p): t = p 1.44269504f, n = floor(t), f = t - n, Horner over f (a multiply, then an add per step) with 0x1.f06faep-10,
+ *       0x1.25429cp-7, 0x1.c99b9ep-5, 0x1.ebcf7ap-3, 0x1.62e526p-1, 1; g = ldexp(poly, n)
+ *     alpha = min(0.99, opacity g); skipped if alpha < 1 / 255
+ *     Tn = T (1 - alpha); Tn < 1e-4: the pixel is done, the entry is not added
+ *     w = alpha T, Ck += float(byte k) w, D += zc w, T = Tn
+ *   rgb (V, 3, H, W) = Ck / 255, depth_out (V, H, W) = D, alpha (V, H, W) = 1 - T.  A range outside [0, E] is empty, a sorted value
+ *   outside 0 .. n - 1 an entry of opacity 0.  walked (V NT) int32 or NULL: the entries each workgroup staged (tools). */
+int mudg_gauss_project(const void* points, const float* cov, const float* opacity, const int32_t* ids, int64_t n, const float* mats,
+                       int V, int nmat, int H, int W, float fx, float fy, float cx, float cy, float znear, float zfar, float* uv,
+                       float* conic, float* depth, int32_t* rect, int32_t* count, void* stream);
+int mudg_gauss_keys(const float* depth, const int32_t* rect, const int32_t* count, const int64_t* offsets, int64_t n, int V, int H,
+                    int W, int64_t E, int64_t* keys, int32_t* values, void* stream);
+int mudg_gauss_ranges(const int64_t* keys_sorted, int64_t E, int64_t tiles, int32_t* ranges, void* stream);
+int mudg_gauss_blend(const void* points, const float* uv, const float* conic, const float* depth, const int32_t* values_sorted,
+                     const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb, float* depth_out, float* alpha,
+                     int32_t* walked, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

@@ -1,0 +1,192 @@
+"""Clouds rendered as 3D Gaussians: the forward half of a tile-binned splat renderer on the GPU (csrc/gaussians.hip).
+
+MuDG's generated views end up in a scene of 3D Gaussians that is rendered at poses nobody drove.  The point splat of render.py is
+sparse on purpose (its images are the model's conditions): it has no opacity, no footprint that grows towards the camera, and leaves
+holes.  Here every point of a PointCloud carries a covariance and an opacity; a call projects them with EWA covariances, bins them into
+16 x 16 tiles, sorts each tile by depth and blends front to back.  The rule is stated operation by operation in DESIGN.md §23 and
+the numpy definition that the tests keep reproduces it bit for bit.  Forward only; colour is one constant per Gaussian.  There is no CPU path:
+tensors that are not on the GPU are an error.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import hip, ops
+from .render import ZFAR, ObjectSet, PointCloud, scaled_intrinsics, virtual_poses
+
+ZNEAR = 0.2                      # the Jacobian has 1 / zc^2
+MAX_ENTRIES = 2 ** 28            # (key, value) pairs a call may sort: 3 GiB of keys and values
+
+
+def covariance_from_scales_rotations(scales, quats):
+    """scales (n, 3) and unit-or-not quaternions (n, 4) as (w, x, y, z) -> (n, 6) fp32 (xx, xy, xz, yy, yz, zz) of R S^2 R^T, in torch on
+    the tensors' device."""
+    scales = torch.as_tensor(scales, dtype=torch.float32)
+    quats = torch.as_tensor(quats, dtype=torch.float32).to(scales.device)
+    if scales.dim() != 2 or scales.shape[1] != 3 or tuple(quats.shape) != (scales.shape[0], 4):
+        raise hip.MudgError(f"expected scales (n, 3) and quaternions (n, 4), got {tuple(scales.shape)} and {tuple(quats.shape)}")
+    w, x, y, z = (quats / quats.norm(dim=1, keepdim=True)).unbind(1)
+    rot = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                       2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                       2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+    m = rot * scales[:, None, :]                                          # R S
+    full = m @ m.transpose(1, 2)
+    return torch.stack([full[:, 0, 0], full[:, 0, 1], full[:, 0, 2], full[:, 1, 1], full[:, 1, 2], full[:, 2, 2]], dim=1).contiguous()
+
+
+def _on_gpu(name, t, dtype, shape):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise hip.MudgError(f"{name}: expected a {dtype} tensor of shape {tuple(shape)} on the GPU (there is no CPU path), got {got}")
+    return t.contiguous()
+
+
+class Gaussians:
+    """A PointCloud (positions and colours), `cov` (n, 6) fp32 = (xx, xy, xz, yy, yz, zz) in the point's own frame (the world for the
+    background, the object's frame for an object), `opacity` (n,) fp32 in [0, 1] and `ids` (n,) int32 or None: the matrix a point goes
+    through, 0 for the background and 1 + object for an object."""
+
+    def __init__(self, cloud: PointCloud, cov: torch.Tensor, opacity: torch.Tensor, ids: Optional[torch.Tensor] = None):
+        if not isinstance(cloud, PointCloud) or not cloud.points.is_cuda:
+            raise hip.MudgError("Gaussians: the cloud is a PointCloud on the GPU (there is no CPU path)")
+        n = len(cloud)
+        self.cloud = cloud
+        self.cov = _on_gpu("Gaussians: cov", cov, torch.float32, (n, 6))
+        self.opacity = _on_gpu("Gaussians: opacity", opacity, torch.float32, (n,))
+        self.ids = None if ids is None else _on_gpu("Gaussians: ids", ids, torch.int32, (n,))
+
+    def __len__(self):
+        return len(self.cloud)
+
+    @staticmethod
+    def _per_point(name, value, n, device):
+        if torch.is_tensor(value) and value.dim() > 0:
+            if tuple(value.shape) != (n,):
+                raise hip.MudgError(f"Gaussians: {name} is a number or an (n,) tensor, got {tuple(value.shape)} for {n} points")
+            return value.to(device=device, dtype=torch.float32)
+        return torch.full((n,), float(value), dtype=torch.float32, device=device)
+
+    @classmethod
+    def from_cloud(cls, cloud: PointCloud, scale, opacity=1.0, ids=None):
+        """Isotropic: covariance s^2 I.  scale: a number or an (n,) tensor, metres; for a cloud thinned at voxel_size a multiple of it."""
+        if not isinstance(cloud, PointCloud) or not cloud.points.is_cuda:
+            raise hip.MudgError("Gaussians.from_cloud: the cloud is a PointCloud on the GPU (there is no CPU path)")
+        n, dev = len(cloud), cloud.points.device
+        s = cls._per_point("scale", scale, n, dev)
+        cov = torch.zeros((n, 6), dtype=torch.float32, device=dev)
+        cov[:, 0] = cov[:, 3] = cov[:, 5] = s * s
+        return cls(cloud, cov, cls._per_point("opacity", opacity, n, dev), ids)
+
+    @classmethod
+    def from_scales_rotations(cls, cloud: PointCloud, scales, quats, opacity=1.0, ids=None):
+        """Covariance R S^2 R^T from per-axis scales (n, 3) and quaternions (n, 4) = (w, x, y, z)."""
+        if not isinstance(cloud, PointCloud) or not cloud.points.is_cuda:
+            raise hip.MudgError("Gaussians.from_scales_rotations: the cloud is a PointCloud on the GPU (there is no CPU path)")
+        n, dev = len(cloud), cloud.points.device
+        cov = covariance_from_scales_rotations(torch.as_tensor(scales).to(dev), torch.as_tensor(quats).to(dev))
+        return cls(cloud, cov, cls._per_point("opacity", opacity, n, dev), ids)
+
+    @classmethod
+    def from_scene(cls, background: PointCloud, objects: Optional[ObjectSet], scale, object_scale=None, opacity=1.0):
+        """One set for a scene: the background with id 0 and scale `scale`, every object's points with id 1 + object and `object_scale`
+        (default: `scale`), so that one sort lets them occlude one another."""
+        if not isinstance(background, PointCloud) or (objects is not None and not isinstance(objects, ObjectSet)):
+            raise hip.MudgError("Gaussians.from_scene: the background is a PointCloud and the objects an ObjectSet (or None)")
+        if objects is None:
+            return cls.from_cloud(background, scale, opacity)
+        if torch.is_tensor(scale) and scale.dim() > 0 or torch.is_tensor(object_scale) and object_scale.dim() > 0:
+            raise hip.MudgError("Gaussians.from_scene: scale and object_scale are numbers")
+        nb, no, dev = len(background), len(objects.cloud), background.points.device
+        s = torch.cat([torch.full((nb,), float(scale)), torch.full((no,), float(scale if object_scale is None else object_scale))]).to(dev)
+        ids = torch.cat([torch.zeros((nb,), dtype=torch.int32, device=dev), objects.ids.to(dev) + 1])
+        return cls.from_cloud(PointCloud.concatenated(background, objects.cloud), s, opacity, ids)
+
+
+def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, stats=None):
+    """Draw `g` into V views.  mats: (V, nmat, 12) fp32 on the GPU, row-major 3 x 4 matrices, mats[v][0] the world-to-camera matrix of
+    view v and mats[v][1 + o] that matrix times object o's transform (zero for an object the view does not show); cams: (fx, fy, cx, cy)
+    shared by the views; hw: (H, W).  Returns {"rgb": (V, 3, H, W) in [0, 1] on black, "depth": (V, H, W) alpha-weighted metres, "alpha":
+    (V, H, W)}, fp32.  stats: a dict that receives "entries" (E, the (tile, Gaussian) pairs), "longest_tile" and the tensors "count",
+    "rect", "values" (sorted) and "ranges"; a (V NT,) int32 tensor put under "walked" beforehand is filled with the entries each tile's
+    workgroup staged (tools).  One host synchronisation reads E (a second one, for the longest tile, only with stats); more than
+    max_entries (or 2^31 - 1) entries are refused."""
+    if not isinstance(g, Gaussians):
+        raise hip.MudgError("render: expected Gaussians")
+    if not torch.is_tensor(mats) or not mats.is_cuda or mats.dtype != torch.float32 or mats.dim() != 3 or mats.shape[2] != 12:
+        raise hip.MudgError("render: the matrices are a (V, nmat, 12) fp32 tensor on the GPU (there is no CPU path)")
+    h, w = (int(v) for v in hw)
+    views = mats.shape[0]
+    tx, ty = ops.gauss_tiles(h, w)
+    tiles = views * tx * ty
+    if h <= 0 or w <= 0 or views == 0 or tiles >= 2 ** 31:
+        raise hip.MudgError(f"render: {views} views of {h} x {w} ({tiles} tiles; V NT < 2^31)")
+    if g.ids is None and mats.shape[1] != 1:
+        raise hip.MudgError(f"render: {mats.shape[1]} matrices per view need Gaussians with ids")
+    pts, dev = g.cloud.points, g.cloud.points.device
+    uv, conic, depth, rect, count = ops.gauss_project(pts, g.cov, g.opacity, mats.contiguous(), cams, (h, w), ids=g.ids, znear=znear, zfar=zfar)
+    ends = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
+    offsets = (ends - count.reshape(-1)).reshape(count.shape)
+    entries = int(ends[-1].item())
+    if entries >= 2 ** 31 or entries > int(max_entries):
+        raise hip.MudgError(f"render: {entries} (tile, Gaussian) entries exceed max_entries = {int(max_entries)} (and must stay below 2^31): "
+                            "thin the cloud, shrink the scale or draw fewer views per call")
+    if stats is not None:
+        stats.update(entries=entries, longest_tile=0, count=count, rect=rect, values=None, ranges=None)
+    if entries == 0:
+        return {"rgb": torch.zeros((views, 3, h, w), dtype=torch.float32, device=dev),
+                "depth": torch.zeros((views, h, w), dtype=torch.float32, device=dev),
+                "alpha": torch.zeros((views, h, w), dtype=torch.float32, device=dev)}
+    keys, values = ops.gauss_keys(depth, rect, count, offsets, entries, (h, w))
+    keys, order = torch.sort(keys, stable=True)
+    values = values[order]
+    ranges = ops.gauss_ranges(keys, tiles)
+    walked = stats.get("walked") if stats is not None else None
+    rgb, out_depth, alpha = ops.gauss_blend(pts, uv, conic, depth, values, ranges, (h, w), walked=walked)
+    if stats is not None:
+        stats.update(longest_tile=int((ranges[:, 1] - ranges[:, 0]).max().item()), values=values, ranges=ranges)
+    return {"rgb": rgb, "depth": out_depth, "alpha": alpha}
+
+
+def scene_matrices(objects: Optional[ObjectSet], w2c, frame):
+    """(P, 4, 4) float64 world-to-camera of one frame -> (P, 1 + objects, 12) fp32 on the host: §12's table with the background first."""
+    w2c = np.asarray(w2c, dtype=np.float64)
+    table = w2c[:, None, :3, :]
+    if objects is not None:
+        table = np.concatenate([table, objects.matrices(w2c, frame)], axis=1)
+    return np.ascontiguousarray(table.reshape(w2c.shape[0], -1, 12).astype(np.float32))
+
+
+def render_scene(g: Gaussians, objects: Optional[ObjectSet], intr, c2w_frames, hw_native, hw_out, poses=None, *, frame_ids=None, shift=2.0,
+                 znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, stats=None):
+    """Render T frames at P poses, with render_conditions' argument conventions: intr (3, 3) or (T, 3, 3) at hw_native, c2w_frames
+    (T, 4, 4), poses None (the original pose and virtual_poses(c2w, shift): P = 3) or (T, P, 4, 4), frame_ids the scene's frame numbers
+    for the objects' transforms.  `g` is Gaussians.from_scene's set (ids 0 and 1 + object): background and objects go through one sort
+    and occlude one another per pixel.  Returns {"rgb": (P, T, 3, H, W), "depth", "alpha": (P, T, H, W)} fp32 and "rgb_u8": (P, T, H, W, 3)
+    uint8 = floor(rgb 255 + 0.5) clamped.  stats: a list that receives one dict per frame."""
+    if not isinstance(g, Gaussians) or (objects is not None and not isinstance(objects, ObjectSet)):
+        raise hip.MudgError("render_scene: expected Gaussians and an ObjectSet (or None)")
+    c2w_frames = np.asarray(c2w_frames, dtype=np.float64)
+    T = c2w_frames.shape[0]
+    if poses is None:
+        poses = np.stack([np.stack(virtual_poses(c, shift, with_ori_pose=True)) for c in c2w_frames])
+    poses = np.asarray(poses, dtype=np.float64)
+    if c2w_frames.shape != (T, 4, 4) or poses.ndim != 4 or poses.shape[0] != T or poses.shape[2:] != (4, 4):
+        raise hip.MudgError(f"render_scene: cameras {c2w_frames.shape} with poses {poses.shape}")
+    frame_ids = list(range(T)) if frame_ids is None else [int(f) for f in frame_ids]
+    intr = np.broadcast_to(np.asarray(intr, dtype=np.float64), (T, 3, 3))
+    dev = g.cloud.points.device
+    w2c = np.linalg.inv(poses)                                                            # host, float64, once per (frame, pose)
+    mats = torch.from_numpy(np.stack([scene_matrices(objects, w2c[t], frame_ids[t]) for t in range(T)])).to(dev)      # one upload
+    frames = []
+    for t in range(T):
+        st = {} if stats is not None else None
+        frames.append(render(g, mats[t], scaled_intrinsics(intr[t], hw_native, hw_out).astype(np.float32), hw_out, znear=znear, zfar=zfar,
+                             max_entries=max_entries, stats=st))
+        if stats is not None:
+            stats.append(st)
+    out = {k: torch.stack([f[k] for f in frames], dim=1) for k in ("rgb", "depth", "alpha")}
+    out["rgb_u8"] = torch.floor(out["rgb"] * 255.0 + 0.5).clamp_(0.0, 255.0).to(torch.uint8).permute(0, 1, 3, 4, 2).contiguous()
+    return out

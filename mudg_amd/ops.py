@@ -892,6 +892,103 @@ def metric_cloud(d2, t2, r2):
     return sums
 
 
+# ------------------------------------------------------------------------------------------------ clouds as 3D Gaussians
+GAUSS_TILE = 16
+
+
+def gauss_tiles(h, w):
+    """(TX, TY) of an h x w image."""
+    return (int(w) + GAUSS_TILE - 1) // GAUSS_TILE, (int(h) + GAUSS_TILE - 1) // GAUSS_TILE
+
+
+def gauss_project(points, cov, opacity, mats, intr, hw, *, ids=None, znear=0.2, zfar=200.0):
+    """Project packed points (n, 4) int32 with covariances (n, 6) and opacities (n,) fp32 through mats (V, nmat, 12) fp32 and intr =
+    (fx, fy, cx, cy) into V views of hw.  Returns uv (V, n, 2), conic (V, n, 4) = (A, B, C, opacity), depth (V, n) fp32,
+    rect (V, n, 4) = (x0, x1, y0, y1) and count (V, n) int32, all zero where a Gaussian is dropped."""
+    _splat_tensor("gauss_project: points", points, torch.int32)
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
+        raise hip.MudgError(f"gauss_project: expected packed points (n > 0, 4), got {tuple(points.shape)}")
+    n = points.shape[0]
+    _splat_tensor("gauss_project: cov", cov, torch.float32, (n, 6))
+    _splat_tensor("gauss_project: opacity", opacity, torch.float32, (n,))
+    _splat_tensor("gauss_project: mats", mats, torch.float32)
+    if mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0 or mats.shape[1] == 0:
+        raise hip.MudgError(f"gauss_project: expected matrices (V, nmat, 12), got {tuple(mats.shape)}")
+    if ids is not None:
+        _splat_tensor("gauss_project: ids", ids, torch.int32, (n,))
+    v, nmat = mats.shape[:2]
+    h, w = (int(s) for s in hw)
+    fx, fy, cx, cy = (float(s) for s in intr)
+    dev = points.device
+    uv = torch.empty((v, n, 2), dtype=torch.float32, device=dev)
+    conic = torch.empty((v, n, 4), dtype=torch.float32, device=dev)
+    depth = torch.empty((v, n), dtype=torch.float32, device=dev)
+    rect = torch.empty((v, n, 4), dtype=torch.int32, device=dev)
+    count = torch.empty((v, n), dtype=torch.int32, device=dev)
+    hip.check(hip.lib().mudg_gauss_project(points.data_ptr(), cov.data_ptr(), opacity.data_ptr(), _ptr(ids), n, mats.data_ptr(), v, nmat, h, w,
+                                           fx, fy, cx, cy, float(znear), float(zfar), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(),
+                                           rect.data_ptr(), count.data_ptr(), _stream()), "mudg_gauss_project")
+    return uv, conic, depth, rect, count
+
+
+def gauss_keys(depth, rect, count, offsets, entries, hw):
+    """One (key, value) entry per tile of every rectangle: keys (E,) int64 = (view NT + tile) << 32 | bits(zc), values (E,) int32 = the
+    Gaussian's index.  offsets (V, n) int64: the exclusive sum of count; entries: its total E."""
+    _splat_tensor("gauss_keys: depth", depth, torch.float32)
+    if depth.dim() != 2:
+        raise hip.MudgError(f"gauss_keys: expected depths (V, n), got {tuple(depth.shape)}")
+    v, n = depth.shape
+    _splat_tensor("gauss_keys: rect", rect, torch.int32, (v, n, 4))
+    _splat_tensor("gauss_keys: count", count, torch.int32, (v, n))
+    _splat_tensor("gauss_keys: offsets", offsets, torch.int64, (v, n))
+    e = int(entries)
+    if e <= 0:
+        raise hip.MudgError(f"gauss_keys: {e} entries")
+    keys = torch.empty((e,), dtype=torch.int64, device=depth.device)
+    values = torch.empty((e,), dtype=torch.int32, device=depth.device)
+    hip.check(hip.lib().mudg_gauss_keys(depth.data_ptr(), rect.data_ptr(), count.data_ptr(), offsets.data_ptr(), n, v, int(hw[0]), int(hw[1]), e,
+                                        keys.data_ptr(), values.data_ptr(), _stream()), "mudg_gauss_keys")
+    return keys, values
+
+
+def gauss_ranges(keys_sorted, tiles):
+    """Sorted keys (E,) int64 -> (tiles, 2) int32: the [start, end) of every tile's entries, [0, 0) for an empty tile."""
+    _splat_tensor("gauss_ranges: keys", keys_sorted, torch.int64)
+    if keys_sorted.dim() != 1 or keys_sorted.numel() == 0:
+        raise hip.MudgError(f"gauss_ranges: expected (E > 0,) keys, got {tuple(keys_sorted.shape)}")
+    ranges = torch.empty((int(tiles), 2), dtype=torch.int32, device=keys_sorted.device)
+    hip.check(hip.lib().mudg_gauss_ranges(keys_sorted.data_ptr(), keys_sorted.numel(), int(tiles), ranges.data_ptr(), _stream()), "mudg_gauss_ranges")
+    return ranges
+
+
+def gauss_blend(points, uv, conic, depth, values_sorted, ranges, hw, *, walked=None):
+    """Front-to-back alpha blending of every tile's entries: rgb (V, 3, H, W) in [0, 1] on black, depth (V, H, W) alpha-weighted and
+    alpha (V, H, W), fp32.  walked: a (V NT,) int32 tensor that receives the entries each workgroup staged (tools)."""
+    _splat_tensor("gauss_blend: points", points, torch.int32)
+    _splat_tensor("gauss_blend: depth", depth, torch.float32)
+    if points.dim() != 2 or points.shape[1] != 4 or depth.dim() != 2 or depth.shape[1] != points.shape[0]:
+        raise hip.MudgError(f"gauss_blend: packed points {tuple(points.shape)} with depths {tuple(depth.shape)}")
+    v, n = depth.shape
+    h, w = (int(s) for s in hw)
+    tx, ty = gauss_tiles(h, w)
+    _splat_tensor("gauss_blend: uv", uv, torch.float32, (v, n, 2))
+    _splat_tensor("gauss_blend: conic", conic, torch.float32, (v, n, 4))
+    _splat_tensor("gauss_blend: values", values_sorted, torch.int32)
+    _splat_tensor("gauss_blend: ranges", ranges, torch.int32, (v * tx * ty, 2))
+    if values_sorted.dim() != 1 or values_sorted.numel() == 0:
+        raise hip.MudgError(f"gauss_blend: expected (E > 0,) sorted values, got {tuple(values_sorted.shape)}")
+    if walked is not None:
+        _splat_tensor("gauss_blend: walked", walked, torch.int32, (v * tx * ty,))
+    dev = points.device
+    rgb = torch.empty((v, 3, h, w), dtype=torch.float32, device=dev)
+    out_depth = torch.empty((v, h, w), dtype=torch.float32, device=dev)
+    alpha = torch.empty((v, h, w), dtype=torch.float32, device=dev)
+    hip.check(hip.lib().mudg_gauss_blend(points.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(), values_sorted.data_ptr(),
+                                         ranges.data_ptr(), n, values_sorted.numel(), v, h, w, rgb.data_ptr(), out_depth.data_ptr(),
+                                         alpha.data_ptr(), _ptr(walked), _stream()), "mudg_gauss_blend")
+    return rgb, out_depth, alpha
+
+
 # ------------------------------------------------------------------------------------------------ metric depth and lifted views
 def _depth_frames(name, frames):
     _splat_tensor(f"{name}: frames", frames, torch.uint8)

@@ -204,3 +204,28 @@ def fuse_window_outputs(outputs_by_pose, scene, frame_ids, poses, **rule):
     scores = metrics.view_consistency(result)
     scores["result"] = result
     return cloud, scores
+
+
+def render_cloud_views(cloud, scene, frame_ids, pose, hw_out, scale, **kw):
+    """A cloud drawn as isotropic 3D Gaussians at a pose (mudg_amd/gaussians.py): what a fused cloud looks like in pixels.
+
+    cloud: fuse_window_outputs' cloud, or any mudg_amd.render.PointCloud in world coordinates (the moving objects are whatever the cloud
+    holds of them: no ObjectSet is drawn); scene: the mudg_amd.render.Scene whose cameras are used; frame_ids: positions in the scene's
+    cameras; pose: as render_windows takes it, 0 / 1 / 2 or a (4, 4) camera-from-virtual-camera matrix; hw_out: the size rendered at;
+    scale: the Gaussians' standard deviation in metres, a number or one per point (for a cloud thinned at voxel_size a multiple of it).
+    **kw: opacity (default 1) and mudg_amd.gaussians.render_scene's keywords (znear, zfar, max_entries, stats).  Returns (frames (t, h,
+    w, 3) uint8, alpha (t, h, w) fp32): the frames on black, ready for mudg_amd.metrics.psnr_ssim against the scene's own frames."""
+    import numpy as np
+    from mudg_amd import gaussians, render
+    frame_ids = [int(f) for f in frame_ids]
+    if not frame_ids:
+        raise ValueError("render_cloud_views: no frames")
+    c2w = np.asarray(scene.c2w, dtype=np.float64)[frame_ids]
+    intr = np.broadcast_to(np.asarray(scene.intr, dtype=np.float64), (np.asarray(scene.c2w).shape[0], 3, 3))[frame_ids]
+    if np.ndim(pose) == 0:
+        cams = np.stack([render.virtual_poses(c, with_ori_pose=True)[int(pose)] for c in c2w])
+    else:
+        cams = c2w @ np.asarray(pose, dtype=np.float64)
+    g = gaussians.Gaussians.from_cloud(cloud, scale, kw.pop("opacity", 1.0))
+    out = gaussians.render_scene(g, None, intr, c2w, scene.hw_native, hw_out, poses=cams[:, None], frame_ids=frame_ids, **kw)
+    return out["rgb_u8"][0], out["alpha"][0]
