@@ -612,6 +612,37 @@ int mudg_gauss_blend(const void* points, const float* uv, const float* conic, co
                      const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb, float* depth_out, float* alpha,
                      int32_t* walked, void* stream);
 
+/* ------------------------------------------------------------------ fitting Gaussians to images (csrc/gaussians_bwd.hip)
+ * The training half of the renderer above: the same tiles, entries, operations and refusals; colour (n, 3) fp32 in byte units takes the
+ * place of the packed colour word.  project, keys and ranges are reused as they are.
+ * blend_train: mudg_gauss_blend with float(byte k) replaced by colour[g][k]; besides rgb, depth_out and alpha it stores state
+ *   (V, 5, H, W) = (C0, C1, C2, D, T), the accumulators before rgb = C / 255 and alpha = 1 - T round them.
+ * blend_bwd: order (E) int64 is the sort's permutation (sorted entry e was unsorted entry order[e]); partial (E, 10) fp32 is zeroed by
+ *   the call.  A workgroup per (view, tile) walks the tile's entries front to back and recomputes dx, dy, p, g, alpha, Tn, w and the
+ *   accumulators with the forward's operations, so the skips and the stopping entry are the forward's.  Per pixel gCk = d_rgb[k] / 255,
+ *   gD = d_depth, gAT = d_alpha state[4].  For an entry the pixel blends, with Ck, D the accumulators after adding it:
+ *     r0..2 = gCk w, r3 = gD w
+ *     unless opacity g > 0.99 (then r4..9 = 0):
+ *       own = ((gC0 c0 + gC1 c1) + gC2 c2) + gD zc, behind = ((gC0 (state0 - C0) + gC1 (state1 - C1)) + gC2 (state2 - C2)) + gD (state3 - D)
+ *       dal = (T own - behind / (1 - alpha)) + gAT / (1 - alpha), r4 = dal g, dp = (dal opacity) g
+ *       r5 = dp (-0.5 (dx dx)), r6 = dp (-(dx dy)), r7 = dp (-0.5 (dy dy)), r8 = dp (-(A dx + B dy)), r9 = dp (-(C dy + B dx))
+ *   every other lane has r = +0.  The 256 lanes' r are added by an xor butterfly over 1, 2, 4, 8, 16, 32 inside each wave of 64 and
+ *   the four waves as ((w0 + w1) + w2) + w3, and stored plainly at partial[order[e]]; an order value outside 0 .. E - 1 stores nothing.
+ * project_bwd, a lane per Gaussian, views in order; a view with count 0, an offset outside [0, E - count] or zc outside the depth range
+ *   adds nothing.  acc = the count partials at offsets + k added in ascending k; d_colour += acc0..2, d_opacity += acc4; the chain rule
+ *   through project's steps as DESIGN §24 writes it gives d_xyz (n, 3) in the point's own frame and d_cov (n, 6), the off-diagonal
+ *   entries with both symmetric halves.  A clamped tx or ty passes nothing through xc / zc; rad, the rectangle and 0.3 are constants. */
+int mudg_gauss_blend_train(const float* colour, const float* uv, const float* conic, const float* depth, const int32_t* values_sorted,
+                           const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb, float* depth_out, float* alpha,
+                           float* state, void* stream);
+int mudg_gauss_blend_bwd(const float* colour, const float* uv, const float* conic, const float* depth, const int32_t* values_sorted,
+                         const int64_t* order, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, const float* state,
+                         const float* d_rgb, const float* d_depth, const float* d_alpha, float* partial, void* stream);
+int mudg_gauss_project_bwd(const void* points, const float* cov, const int32_t* ids, int64_t n, const float* mats, int V, int nmat, int H,
+                           int W, float fx, float fy, float cx, float cy, float znear, float zfar, const int32_t* count,
+                           const int64_t* offsets, const float* partial, int64_t E, float* d_xyz, float* d_cov, float* d_opacity,
+                           float* d_colour, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

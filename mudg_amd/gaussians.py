@@ -4,8 +4,9 @@ MuDG's generated views end up in a scene of 3D Gaussians that is rendered at pos
 sparse on purpose (its images are the model's conditions): it has no opacity, no footprint that grows towards the camera, and leaves
 holes.  Here every point of a PointCloud carries a covariance and an opacity; a call projects them with EWA covariances, bins them into
 16 x 16 tiles, sorts each tile by depth and blends front to back.  The rule is stated operation by operation in DESIGN.md §23 and
-the numpy definition that the tests keep reproduces it bit for bit.  Forward only; colour is one constant per Gaussian.  There is no CPU path:
-tensors that are not on the GPU are an error.
+the numpy definition that the tests keep reproduces it bit for bit.  Colour is one constant per Gaussian.  `render` is the inference path;
+`render_differentiable`, `GaussianModel` and `fit` optimise position, covariance, opacity and colour against images
+through the backward kernels of csrc/gaussians_bwd.hip.  There is no CPU path: tensors that are not on the GPU are an error.
 """
 from __future__ import annotations
 
@@ -190,3 +191,193 @@ def render_scene(g: Gaussians, objects: Optional[ObjectSet], intr, c2w_frames, h
     out = {k: torch.stack([f[k] for f in frames], dim=1) for k in ("rgb", "depth", "alpha")}
     out["rgb_u8"] = torch.floor(out["rgb"] * 255.0 + 0.5).clamp_(0.0, 255.0).to(torch.uint8).permute(0, 1, 3, 4, 2).contiguous()
     return out
+
+
+# ------------------------------------------------------------------------------------------------ fitting Gaussians to images (§24)
+def _pack_xyz(xyz):
+    """(n, 3) fp32 -> packed (n, 4) int32 points with a zero colour word: how positions travel to the kernels."""
+    return torch.cat([xyz.detach().contiguous().view(torch.int32), torch.zeros((xyz.shape[0], 1), dtype=torch.int32, device=xyz.device)], dim=1)
+
+
+class _Render(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries):
+        h, w = hw
+        views, dev = mats.shape[0], xyz.device
+        tx, ty = ops.gauss_tiles(h, w)
+        pts = _pack_xyz(xyz)
+        cov, opacity, colour = cov.detach().contiguous(), opacity.detach().contiguous(), colour.detach().contiguous()
+        uv, conic, depth, rect, count = ops.gauss_project(pts, cov, opacity, mats, cams, (h, w), ids=ids, znear=znear, zfar=zfar)
+        ends = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
+        offsets = (ends - count.reshape(-1)).reshape(count.shape)
+        entries = int(ends[-1].item())
+        if entries >= 2 ** 31 or entries > int(max_entries):
+            raise hip.MudgError(f"render_differentiable: {entries} (tile, Gaussian) entries exceed max_entries = {int(max_entries)} (and must "
+                                "stay below 2^31): thin the cloud, shrink the scale or draw fewer views per call")
+        ctx.meta = (cams, (h, w), ids, znear, zfar, entries)
+        if entries == 0:
+            ctx.save_for_backward(xyz)
+            return (torch.zeros((views, 3, h, w), dtype=torch.float32, device=dev), torch.zeros((views, h, w), dtype=torch.float32, device=dev),
+                    torch.zeros((views, h, w), dtype=torch.float32, device=dev))
+        keys, values = ops.gauss_keys(depth, rect, count, offsets, entries, (h, w))
+        keys, order = torch.sort(keys, stable=True)
+        values = values[order]
+        ranges = ops.gauss_ranges(keys, views * tx * ty)
+        rgb, out_depth, alpha, state = ops.gauss_blend_train(colour, uv, conic, depth, values, ranges, (h, w))
+        ctx.save_for_backward(pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state)
+        return rgb, out_depth, alpha
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_alpha):
+        cams, hw, ids, znear, zfar, entries = ctx.meta
+        if entries == 0:                                                    # nothing was drawn: no launch
+            n, dev = ctx.saved_tensors[0].shape[0], ctx.saved_tensors[0].device
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            return (z(n, 3), z(n, 3), z(n, 6), z(n)) + (None,) * 7
+        pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state = ctx.saved_tensors
+        views, (h, w) = mats.shape[0], hw
+        grad = lambda g, shape: torch.zeros(shape, dtype=torch.float32, device=pts.device) if g is None else g.to(torch.float32).contiguous()
+        partial = ops.gauss_blend_bwd(colour, uv, conic, depth, values, order, ranges, hw, state, grad(d_rgb, (views, 3, h, w)),
+                                      grad(d_depth, (views, h, w)), grad(d_alpha, (views, h, w)))
+        d_xyz, d_cov, d_opacity, d_colour = ops.gauss_project_bwd(pts, cov, mats, cams, hw, count, offsets, partial, ids=ids, znear=znear,
+                                                                  zfar=zfar)
+        return (d_xyz, d_colour, d_cov, d_opacity) + (None,) * 7
+
+
+def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES):
+    """`render` with gradients.  xyz (n, 3), colour (n, 3) in byte units (0 .. 255, not necessarily whole), cov (n, 6) and
+    opacity (n,): fp32 on the GPU; mats, cams, hw and ids as `render` takes them.  Returns (rgb (V, 3, H, W), depth (V, H, W), alpha
+    (V, H, W)); backward gives gradients for the first four arguments, none for the matrices or the camera.  One host synchronisation reads
+    the entry count."""
+    n = xyz.shape[0] if torch.is_tensor(xyz) and xyz.dim() == 2 else -1
+    for name, t, shape in (("xyz", xyz, (n, 3)), ("colour", colour, (n, 3)), ("cov", cov, (n, 6)), ("opacity", opacity, (n,))):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or n <= 0:
+            got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise hip.MudgError(f"render_differentiable: {name} is an fp32 tensor of shape {shape} on the GPU (there is no CPU path), got {got}")
+    if not torch.is_tensor(mats) or not mats.is_cuda or mats.dtype != torch.float32 or mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0:
+        raise hip.MudgError("render_differentiable: the matrices are a (V, nmat, 12) fp32 tensor on the GPU (there is no CPU path)")
+    if ids is not None:
+        ids = _on_gpu("render_differentiable: ids", ids, torch.int32, (n,))
+    elif mats.shape[1] != 1:
+        raise hip.MudgError(f"render_differentiable: {mats.shape[1]} matrices per view need ids")
+    h, w = (int(v) for v in hw)
+    tx, ty = ops.gauss_tiles(h, w)
+    if h <= 0 or w <= 0 or mats.shape[0] * tx * ty >= 2 ** 31:
+        raise hip.MudgError(f"render_differentiable: {mats.shape[0]} views of {h} x {w} (V NT < 2^31)")
+    return _Render.apply(xyz, colour, cov, opacity, mats.contiguous(), tuple(float(c) for c in cams), (h, w), ids, float(znear), float(zfar),
+                         int(max_entries))
+
+
+PARAMETERS = ("xyz", "colour", "log_scale", "quat", "opacity_logit")
+LEARNING_RATES = {"xyz": 2e-3, "colour": 2.0, "log_scale": 5e-3, "quat": 1e-3, "opacity_logit": 5e-2}      # metres, bytes, log metres, -, logits
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-15
+MAX_SEED_OPACITY = 0.999                       # a seed opacity of 1 would be an infinite logit
+
+
+class GaussianModel:
+    """Gaussians as the tensors an optimiser moves: `xyz` (n, 3) metres, `colour` (n, 3) in byte units, `log_scale` (n, 3) (the logarithm
+    of the per-axis standard deviation), `quat` (n, 4) = (w, x, y, z), `opacity_logit` (n,), all fp32 leaves on the GPU that require
+    gradients, and `ids` (n,) int32 or None as Gaussians has them.  Covariance R exp(log_scale)^2 R^T and opacity sigmoid(opacity_logit)
+    are torch expressions, so autograd carries the kernels' gradients to the parameters."""
+
+    def __init__(self, xyz, colour, log_scale, quat, opacity_logit, ids=None):
+        n = xyz.shape[0] if torch.is_tensor(xyz) and xyz.dim() == 2 else -1
+        shapes = {"xyz": (n, 3), "colour": (n, 3), "log_scale": (n, 3), "quat": (n, 4), "opacity_logit": (n,)}
+        for name, t in zip(PARAMETERS, (xyz, colour, log_scale, quat, opacity_logit)):
+            setattr(self, name, _on_gpu(f"GaussianModel: {name}", t, torch.float32, shapes[name]).detach().clone().requires_grad_(True))
+        self.ids = None if ids is None else _on_gpu("GaussianModel: ids", ids, torch.int32, (n,))
+
+    def __len__(self):
+        return self.xyz.shape[0]
+
+    def parameters(self):
+        return {name: getattr(self, name) for name in PARAMETERS}
+
+    def covariance(self):
+        return covariance_from_scales_rotations(torch.exp(self.log_scale), self.quat)
+
+    def opacity(self):
+        return torch.sigmoid(self.opacity_logit)
+
+    @classmethod
+    def from_cloud(cls, cloud: PointCloud, scale, opacity=0.9, ids=None):
+        """Seeded as Gaussians.from_cloud seeds: isotropic `scale` (a number or (n,) tensor, metres), the cloud's positions and colours, the
+        identity rotation.  opacity is clamped to [1 / 255, 0.999] so that its logit is finite."""
+        if not isinstance(cloud, PointCloud) or not cloud.points.is_cuda:
+            raise hip.MudgError("GaussianModel.from_cloud: the cloud is a PointCloud on the GPU (there is no CPU path)")
+        n, dev = len(cloud), cloud.points.device
+        pts = cloud.points
+        xyz = pts[:, :3].contiguous().view(torch.float32)
+        word = pts[:, 3]
+        colour = torch.stack([word & 0xff, (word >> 8) & 0xff, (word >> 16) & 0xff], dim=1).to(torch.float32)
+        s = Gaussians._per_point("scale", scale, n, dev)
+        op = Gaussians._per_point("opacity", opacity, n, dev).clamp(1.0 / 255.0, MAX_SEED_OPACITY)
+        quat = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        quat[:, 0] = 1.0
+        return cls(xyz, colour, torch.log(s)[:, None].expand(n, 3).contiguous(), quat, torch.log(op) - torch.log1p(-op), ids)
+
+    @classmethod
+    def from_scene(cls, background: PointCloud, objects: Optional[ObjectSet], scale, object_scale=None, opacity=0.9):
+        """Gaussians.from_scene's set as a model: the background with id 0, every object's points with id 1 + object."""
+        g = Gaussians.from_scene(background, objects, scale, object_scale, 1.0)
+        s = torch.sqrt(g.cov[:, 0])
+        return cls.from_cloud(g.cloud, s, opacity, g.ids)
+
+    def gaussians(self) -> Gaussians:
+        """The inference set: positions as they are, colours rounded (floor(c + 0.5)) and clamped to bytes, covariance and opacity
+        evaluated.  render, render_scene and render_cloud_views' renderer draw it."""
+        with torch.no_grad():
+            byte = torch.floor(self.colour + 0.5).clamp_(0.0, 255.0).to(torch.int32)
+            word = byte[:, 0] | (byte[:, 1] << 8) | (byte[:, 2] << 16)
+            pts = torch.cat([self.xyz.contiguous().view(torch.int32), word[:, None]], dim=1).contiguous()
+            return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids)
+
+
+def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_per_step=None, depth_targets=None, depth_weight=0.0,
+        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES):
+    """Optimise `model` in place against targets (V, 3, H, W) fp32 in [0, 1] seen through mats (V, nmat, 12) and cams.
+    Iteration i renders the views_per_step (default: all) views (i views_per_step + k) mod V, takes the mean absolute difference of rgb,
+    adds depth_weight times the mean absolute depth difference over the pixels where depth_targets (V, H, W) is positive, and takes one
+    Adam step (betas 0.9 / 0.999, eps 1e-15, no weight decay) through train.kernels.adamw_multi_: one launch for all tensors that share
+    a learning rate.  lr: a dict over PARAMETERS (missing names take LEARNING_RATES) or None; trainable: the names that move.  No
+    densification, pruning, opacity reset, spherical harmonics, SSIM term or pose gradient.  Returns the loss of every iteration."""
+    from .train import kernels as K
+    if not isinstance(model, GaussianModel):
+        raise hip.MudgError("fit: expected a GaussianModel")
+    h, w = (int(v) for v in hw)
+    if not torch.is_tensor(mats) or not mats.is_cuda or mats.dtype != torch.float32 or mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0:
+        raise hip.MudgError("fit: the matrices are a (V, nmat, 12) fp32 tensor on the GPU (there is no CPU path)")
+    views = mats.shape[0]
+    targets = _on_gpu("fit: targets", targets, torch.float32, (views, 3, h, w))
+    if depth_targets is not None:
+        depth_targets = _on_gpu("fit: depth_targets", depth_targets, torch.float32, (views, h, w))
+    rates = dict(LEARNING_RATES, **(lr or {}))
+    names = [n for n in PARAMETERS if n in tuple(trainable)]
+    if not names or set(trainable) - set(PARAMETERS) or set(rates) - set(PARAMETERS) or int(iters) < 0:
+        raise hip.MudgError(f"fit: trainable and lr name parameters among {PARAMETERS}, got {tuple(trainable)} and {tuple(rates)}")
+    per = views if views_per_step is None else int(views_per_step)
+    if not 1 <= per <= views:
+        raise hip.MudgError(f"fit: {per} views per step of {views}")
+    params = [getattr(model, n) for n in names]
+    grads = [torch.zeros_like(p) for p in params]
+    moments = [(torch.zeros_like(p), torch.zeros_like(p)) for p in params]
+    tables = {}
+    for rate in sorted({float(rates[n]) for n in names}):
+        rows = [(p.detach(), g, m, v) for n, p, g, (m, v) in zip(names, params, grads, moments) if float(rates[n]) == rate]
+        tables[rate] = K.chunk_table(rows)
+    losses = []
+    for it in range(int(iters)):
+        pick = torch.tensor([(it * per + k) % views for k in range(per)], device=mats.device)
+        rgb, depth, _ = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(), mats[pick], cams, (h, w),
+                                              ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries)
+        loss = (rgb - targets[pick]).abs().mean()
+        if depth_targets is not None and depth_weight:
+            want = depth_targets[pick]
+            seen = want > 0
+            loss = loss + float(depth_weight) * ((depth - want).abs() * seen).sum() / seen.sum().clamp(min=1)
+        for g, d in zip(grads, torch.autograd.grad(loss, params, allow_unused=True)):
+            g.zero_() if d is None else g.copy_(d)
+        for rate, (table, chunks) in tables.items():
+            K.adamw_multi_(table, chunks, lr=rate, betas=ADAM_BETAS, eps=ADAM_EPS, weight_decay=0.0, step=it + 1)
+        losses.append(loss.detach())
+    return torch.stack(losses).tolist() if losses else []

@@ -194,6 +194,9 @@ SIGNATURES = {
     "mudg_gauss_keys": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P]),
     "mudg_gauss_ranges": (_I, [_P, _L, _L, _P, _P]),
     "mudg_gauss_blend": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mudg_gauss_blend_train": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mudg_gauss_blend_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mudg_gauss_project_bwd": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P, _L, _P, _P, _P, _P, _P]),
     "mudg_short_attention_ok": (_I, [C.POINTER(ShortAttnDesc)]),
     "mudg_short_attention": (_I, [C.POINTER(ShortAttnDesc), _P]),
     "mudg_layernorm_f32": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P]),

@@ -989,6 +989,92 @@ def gauss_blend(points, uv, conic, depth, values_sorted, ranges, hw, *, walked=N
     return rgb, out_depth, alpha
 
 
+GAUSS_SUMS = 10                  # a partial: dcolour0..2, dzc, dopacity, dA, dB, dC, du, dv
+
+
+def _gauss_entries(name, colour, uv, conic, depth, values_sorted, ranges, hw):
+    _splat_tensor(f"{name}: colour", colour, torch.float32)
+    _splat_tensor(f"{name}: depth", depth, torch.float32)
+    if colour.dim() != 2 or colour.shape[1] != 3 or depth.dim() != 2 or depth.shape[1] != colour.shape[0]:
+        raise hip.MudgError(f"{name}: colours {tuple(colour.shape)} with depths {tuple(depth.shape)}")
+    v, n = depth.shape
+    h, w = (int(s) for s in hw)
+    tx, ty = gauss_tiles(h, w)
+    _splat_tensor(f"{name}: uv", uv, torch.float32, (v, n, 2))
+    _splat_tensor(f"{name}: conic", conic, torch.float32, (v, n, 4))
+    _splat_tensor(f"{name}: values", values_sorted, torch.int32)
+    _splat_tensor(f"{name}: ranges", ranges, torch.int32, (v * tx * ty, 2))
+    if values_sorted.dim() != 1 or values_sorted.numel() == 0:
+        raise hip.MudgError(f"{name}: expected (E > 0,) sorted values, got {tuple(values_sorted.shape)}")
+    return v, n, h, w
+
+
+def gauss_blend_train(colour, uv, conic, depth, values_sorted, ranges, hw):
+    """gauss_blend with the colour an fp32 (n, 3) tensor in byte units.  Returns rgb, depth, alpha as gauss_blend does and
+    state (V, 5, H, W) fp32 = the accumulators (C0, C1, C2, D, T) of every pixel, which the backward needs unrounded."""
+    v, n, h, w = _gauss_entries("gauss_blend_train", colour, uv, conic, depth, values_sorted, ranges, hw)
+    dev = colour.device
+    rgb = torch.empty((v, 3, h, w), dtype=torch.float32, device=dev)
+    out_depth = torch.empty((v, h, w), dtype=torch.float32, device=dev)
+    alpha = torch.empty((v, h, w), dtype=torch.float32, device=dev)
+    state = torch.empty((v, 5, h, w), dtype=torch.float32, device=dev)
+    hip.check(hip.lib().mudg_gauss_blend_train(colour.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(), values_sorted.data_ptr(),
+                                               ranges.data_ptr(), n, values_sorted.numel(), v, h, w, rgb.data_ptr(), out_depth.data_ptr(),
+                                               alpha.data_ptr(), state.data_ptr(), _stream()), "mudg_gauss_blend_train")
+    return rgb, out_depth, alpha, state
+
+
+def gauss_blend_bwd(colour, uv, conic, depth, values_sorted, order, ranges, hw, state, d_rgb, d_depth, d_alpha):
+    """The blend's backward: partial (E, 10) fp32, one row per entry at its unsorted position order[e], the sums over the tile's pixels of
+    (dcolour0..2, dzc, dopacity, dA, dB, dC, du, dv) in one fixed order; zero for entries no workgroup reached."""
+    v, n, h, w = _gauss_entries("gauss_blend_bwd", colour, uv, conic, depth, values_sorted, ranges, hw)
+    e = values_sorted.numel()
+    _splat_tensor("gauss_blend_bwd: order", order, torch.int64, (e,))
+    _splat_tensor("gauss_blend_bwd: state", state, torch.float32, (v, 5, h, w))
+    _splat_tensor("gauss_blend_bwd: d_rgb", d_rgb, torch.float32, (v, 3, h, w))
+    _splat_tensor("gauss_blend_bwd: d_depth", d_depth, torch.float32, (v, h, w))
+    _splat_tensor("gauss_blend_bwd: d_alpha", d_alpha, torch.float32, (v, h, w))
+    partial = torch.empty((e, GAUSS_SUMS), dtype=torch.float32, device=colour.device)
+    hip.check(hip.lib().mudg_gauss_blend_bwd(colour.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(), values_sorted.data_ptr(),
+                                             order.data_ptr(), ranges.data_ptr(), n, e, v, h, w, state.data_ptr(), d_rgb.data_ptr(),
+                                             d_depth.data_ptr(), d_alpha.data_ptr(), partial.data_ptr(), _stream()), "mudg_gauss_blend_bwd")
+    return partial
+
+
+def gauss_project_bwd(points, cov, mats, intr, hw, count, offsets, partial, *, ids=None, znear=0.2, zfar=200.0):
+    """The projection's backward: every Gaussian's partials gathered per view in ascending order and taken through the chain rule of
+    gauss_project, the views added in order.  Returns d_xyz (n, 3), d_cov (n, 6) (off-diagonal entries: both symmetric halves),
+    d_opacity (n,) and d_colour (n, 3), fp32."""
+    _splat_tensor("gauss_project_bwd: points", points, torch.int32)
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
+        raise hip.MudgError(f"gauss_project_bwd: expected packed points (n > 0, 4), got {tuple(points.shape)}")
+    n = points.shape[0]
+    _splat_tensor("gauss_project_bwd: cov", cov, torch.float32, (n, 6))
+    _splat_tensor("gauss_project_bwd: mats", mats, torch.float32)
+    if mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0 or mats.shape[1] == 0:
+        raise hip.MudgError(f"gauss_project_bwd: expected matrices (V, nmat, 12), got {tuple(mats.shape)}")
+    if ids is not None:
+        _splat_tensor("gauss_project_bwd: ids", ids, torch.int32, (n,))
+    v, nmat = mats.shape[:2]
+    _splat_tensor("gauss_project_bwd: count", count, torch.int32, (v, n))
+    _splat_tensor("gauss_project_bwd: offsets", offsets, torch.int64, (v, n))
+    _splat_tensor("gauss_project_bwd: partial", partial, torch.float32)
+    if partial.dim() != 2 or partial.shape[1] != GAUSS_SUMS or partial.shape[0] == 0:
+        raise hip.MudgError(f"gauss_project_bwd: expected partials (E > 0, {GAUSS_SUMS}), got {tuple(partial.shape)}")
+    h, w = (int(s) for s in hw)
+    fx, fy, cx, cy = (float(s) for s in intr)
+    dev = points.device
+    d_xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    d_cov = torch.empty((n, 6), dtype=torch.float32, device=dev)
+    d_opacity = torch.empty((n,), dtype=torch.float32, device=dev)
+    d_colour = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    hip.check(hip.lib().mudg_gauss_project_bwd(points.data_ptr(), cov.data_ptr(), _ptr(ids), n, mats.data_ptr(), v, nmat, h, w, fx, fy, cx, cy,
+                                               float(znear), float(zfar), count.data_ptr(), offsets.data_ptr(), partial.data_ptr(),
+                                               partial.shape[0], d_xyz.data_ptr(), d_cov.data_ptr(), d_opacity.data_ptr(), d_colour.data_ptr(),
+                                               _stream()), "mudg_gauss_project_bwd")
+    return d_xyz, d_cov, d_opacity, d_colour
+
+
 # ------------------------------------------------------------------------------------------------ metric depth and lifted views
 def _depth_frames(name, frames):
     _splat_tensor(f"{name}: frames", frames, torch.uint8)

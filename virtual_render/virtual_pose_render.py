@@ -229,3 +229,41 @@ def render_cloud_views(cloud, scene, frame_ids, pose, hw_out, scale, **kw):
     g = gaussians.Gaussians.from_cloud(cloud, scale, kw.pop("opacity", 1.0))
     out = gaussians.render_scene(g, None, intr, c2w, scene.hw_native, hw_out, poses=cams[:, None], frame_ids=frame_ids, **kw)
     return out["rgb_u8"][0], out["alpha"][0]
+
+
+def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, **kw):
+    """The companion of render_cloud_views: a cloud seeded as isotropic Gaussians and optimised against a window's frames
+    (mudg_amd.gaussians.fit).
+
+    cloud, scene, frame_ids, pose, hw_out and scale as render_cloud_views takes them; frames_u8: (t, h, w, 3) uint8 on the GPU at hw_out,
+    what the cameras saw (or the model generated) at those frames and that pose.  The frames share one camera: per-frame intrinsics
+    that differ are refused.  **kw: opacity (the seed, default 0.9), history (a list that receives the loss of every iteration) and
+    fit's keywords (iters, default 200; lr, views_per_step, depth_targets, depth_weight, trainable, znear, zfar, max_entries).  Returns
+    the fitted mudg_amd.gaussians.Gaussians, which render, render_scene and the renderer of render_cloud_views draw."""
+    import numpy as np
+    import torch
+    from mudg_amd import gaussians, hip, render
+    frame_ids = [int(f) for f in frame_ids]
+    if not frame_ids:
+        raise ValueError("fit_cloud_views: no frames")
+    h, w = (int(v) for v in hw_out)
+    if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != (len(frame_ids), h, w, 3):
+        raise hip.MudgError(f"fit_cloud_views: the frames are a ({len(frame_ids)}, {h}, {w}, 3) uint8 tensor on the GPU (there is no CPU path)")
+    c2w = np.asarray(scene.c2w, dtype=np.float64)[frame_ids]
+    intr = np.broadcast_to(np.asarray(scene.intr, dtype=np.float64), (np.asarray(scene.c2w).shape[0], 3, 3))[frame_ids]
+    if not (intr == intr[0]).all():
+        raise hip.MudgError("fit_cloud_views: the frames of one fit share one camera")
+    if np.ndim(pose) == 0:
+        cams = np.stack([render.virtual_poses(c, with_ori_pose=True)[int(pose)] for c in c2w])
+    else:
+        cams = c2w @ np.asarray(pose, dtype=np.float64)
+    mats = torch.from_numpy(gaussians.scene_matrices(None, np.linalg.inv(cams), 0)).to(frames_u8.device)
+    k = render.scaled_intrinsics(intr[0], scene.hw_native, (h, w)).astype(np.float32)
+    model = gaussians.GaussianModel.from_cloud(cloud, scale, kw.pop("opacity", 0.9))
+    history = kw.pop("history", None)
+    kw.setdefault("iters", 200)
+    targets = frames_u8.permute(0, 3, 1, 2).to(torch.float32).div_(255.0).contiguous()
+    losses = gaussians.fit(model, targets, mats, k, (h, w), **kw)
+    if history is not None:
+        history.extend(losses)
+    return model.gaussians()
