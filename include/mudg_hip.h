@@ -643,6 +643,32 @@ int mudg_gauss_project_bwd(const void* points, const float* cov, const int32_t* 
                            const int64_t* offsets, const float* partial, int64_t E, float* d_xyz, float* d_cov, float* d_opacity,
                            float* d_colour, void* stream);
 
+/* ------------------------------------------------------------------ density control for the fit (csrc/gaussians_density.hip)
+ * Which Gaussians a fit clones, splits and prunes, and the pass that rewrites the parameters.  fp32, single rounded operations in the
+ * order written, a lane per Gaussian, plain stores, no atomics, no generator state, no transcendental.
+ * accumulate: partial (E, 10), count (V, n) and offsets (V, n) are what mudg_gauss_project_bwd reads, with its guards: a view with
+ *   count <= 0 or an offset outside [0, E - count] adds nothing.  Otherwise su, sv = columns 8, 9 of the count partials added in ascending
+ *   k from +0; a = (0.5 W) su, b = (0.5 H) sv; grad_sum[g] += sqrt(a a + b b) (the gradient norm in [-1, 1] screen units), seen[g] += 1.
+ *   The views are taken in order; grad_sum (n) fp32 and seen (n) int32 are updated in place.
+ * plan: opacity (n) and scale (n, 3) = exp(log_scale) come evaluated.  smax = max(max(s0, s1), s2).  action (n) / rows (n) int32:
+ *   1 / 0 (prune) if grad_sum, opacity or a scale is not a number, opacity < min_opacity or smax > max_scale; else, if grow != 0,
+ *   seen > 0 and grad_sum / float(seen) >= grad_threshold: 3 / 2 (split) if smax > split_scale, 2 / 2 (clone) if not; else 0 / 1 (keep).
+ * apply: start (n) int64 is the exclusive sum of rows and n_out its total.  src and dst are host arrays of 15 device pointers, read
+ *   before the call returns: tensor 3 p + k is parameter p of (xyz (n, 3), colour (n, 3), log_scale (n, 3), quat (n, 4), opacity_logit (n))
+ *   for k = 0, its first Adam moment for k = 1 and its second for k = 2; dst has n_out rows.  Keep copies the row and its moments to
+ *   start[g]; clone writes that row and then the same row with zero moments; split writes two rows with zero moments, xyz +- d axis and
+ *   log_scale - log_shrink, where k is the first index of the largest scale, axis column k of rot (n, 9) (row-major 3 x 3) and
+ *   d = split_offset scale[k]; ids (n) is copied to ids_out (n_out) when both are given.  An action outside 0 .. 3 is a prune; a start
+ *   outside [0, n_out - rows] stores nothing. */
+int mudg_gauss_density_accumulate(const float* partial, const int32_t* count, const int64_t* offsets, int64_t n, int V, int H, int W,
+                                  int64_t E, float* grad_sum, int32_t* seen, void* stream);
+int mudg_gauss_density_plan(const float* grad_sum, const int32_t* seen, const float* opacity, const float* scale, int64_t n,
+                            float grad_threshold, float split_scale, float min_opacity, float max_scale, int grow, int32_t* action,
+                            int32_t* rows, void* stream);
+int mudg_gauss_density_apply(const int32_t* action, const int64_t* start, int64_t n, int64_t n_out, const float* scale, const float* rot,
+                             float split_offset, float log_shrink, const float* const* src, float* const* dst, const int32_t* ids,
+                             int32_t* ids_out, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

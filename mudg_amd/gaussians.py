@@ -6,7 +6,9 @@ holes.  Here every point of a PointCloud carries a covariance and an opacity; a 
 16 x 16 tiles, sorts each tile by depth and blends front to back.  The rule is stated operation by operation in DESIGN.md §23 and
 the numpy definition that the tests keep reproduces it bit for bit.  Colour is one constant per Gaussian.  `render` is the inference path;
 `render_differentiable`, `GaussianModel` and `fit` optimise position, covariance, opacity and colour against images
-through the backward kernels of csrc/gaussians_bwd.hip.  There is no CPU path: tensors that are not on the GPU are an error.
+through the backward kernels of csrc/gaussians_bwd.hip; `DensityControl`, `DensityStats` and `densify_and_prune` let a
+fit clone, split and prune its Gaussians through csrc/gaussians_density.hip.  There is no CPU path: tensors that are not on the GPU are
+an error.
 """
 from __future__ import annotations
 
@@ -22,6 +24,14 @@ ZNEAR = 0.2                      # the Jacobian has 1 / zc^2
 MAX_ENTRIES = 2 ** 28            # (key, value) pairs a call may sort: 3 GiB of keys and values
 
 
+def rotation_from_quaternions(quats):
+    """Unit-or-not quaternions (n, 4) as (w, x, y, z) -> (n, 3, 3): the rotation of the normalised quaternion, in torch."""
+    w, x, y, z = (quats / quats.norm(dim=1, keepdim=True)).unbind(1)
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+
+
 def covariance_from_scales_rotations(scales, quats):
     """scales (n, 3) and unit-or-not quaternions (n, 4) as (w, x, y, z) -> (n, 6) fp32 (xx, xy, xz, yy, yz, zz) of R S^2 R^T, in torch on
     the tensors' device."""
@@ -29,11 +39,7 @@ def covariance_from_scales_rotations(scales, quats):
     quats = torch.as_tensor(quats, dtype=torch.float32).to(scales.device)
     if scales.dim() != 2 or scales.shape[1] != 3 or tuple(quats.shape) != (scales.shape[0], 4):
         raise hip.MudgError(f"expected scales (n, 3) and quaternions (n, 4), got {tuple(scales.shape)} and {tuple(quats.shape)}")
-    w, x, y, z = (quats / quats.norm(dim=1, keepdim=True)).unbind(1)
-    rot = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-                       2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                       2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
-    m = rot * scales[:, None, :]                                          # R S
+    m = rotation_from_quaternions(quats) * scales[:, None, :]             # R S
     full = m @ m.transpose(1, 2)
     return torch.stack([full[:, 0, 0], full[:, 0, 1], full[:, 0, 2], full[:, 1, 1], full[:, 1, 2], full[:, 2, 2]], dim=1).contiguous()
 
@@ -201,8 +207,9 @@ def _pack_xyz(xyz):
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries):
+    def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density=None):
         h, w = hw
+        ctx.density = density
         views, dev = mats.shape[0], xyz.device
         tx, ty = ops.gauss_tiles(h, w)
         pts = _pack_xyz(xyz)
@@ -233,7 +240,7 @@ class _Render(torch.autograd.Function):
         if entries == 0:                                                    # nothing was drawn: no launch
             n, dev = ctx.saved_tensors[0].shape[0], ctx.saved_tensors[0].device
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-            return (z(n, 3), z(n, 3), z(n, 6), z(n)) + (None,) * 7
+            return (z(n, 3), z(n, 3), z(n, 6), z(n)) + (None,) * 8
         pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state = ctx.saved_tensors
         views, (h, w) = mats.shape[0], hw
         grad = lambda g, shape: torch.zeros(shape, dtype=torch.float32, device=pts.device) if g is None else g.to(torch.float32).contiguous()
@@ -241,15 +248,21 @@ class _Render(torch.autograd.Function):
                                       grad(d_depth, (views, h, w)), grad(d_alpha, (views, h, w)))
         d_xyz, d_cov, d_opacity, d_colour = ops.gauss_project_bwd(pts, cov, mats, cams, hw, count, offsets, partial, ids=ids, znear=znear,
                                                                   zfar=zfar)
-        return (d_xyz, d_colour, d_cov, d_opacity) + (None,) * 7
+        if ctx.density is not None:                                         # §25: a second pass over the partials' columns 8 and 9
+            ops.gauss_density_accumulate(partial, count, offsets, hw, ctx.density.grad_sum, ctx.density.seen)
+        return (d_xyz, d_colour, d_cov, d_opacity) + (None,) * 8
 
 
-def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES):
+def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES,
+                          density=None):
     """`render` with gradients.  xyz (n, 3), colour (n, 3) in byte units (0 .. 255, not necessarily whole), cov (n, 6) and
     opacity (n,): fp32 on the GPU; mats, cams, hw and ids as `render` takes them.  Returns (rgb (V, 3, H, W), depth (V, H, W), alpha
     (V, H, W)); backward gives gradients for the first four arguments, none for the matrices or the camera.  One host synchronisation reads
-    the entry count."""
+    the entry count.  density: a DensityStats of n Gaussians; backward then adds every Gaussian's screen-space gradient norm and the
+    views that counted it.  With None nothing else happens: the same launches, the same bits."""
     n = xyz.shape[0] if torch.is_tensor(xyz) and xyz.dim() == 2 else -1
+    if density is not None and (not isinstance(density, DensityStats) or density.grad_sum.shape[0] != n):
+        raise hip.MudgError(f"render_differentiable: density is a DensityStats of {n} Gaussians")
     for name, t, shape in (("xyz", xyz, (n, 3)), ("colour", colour, (n, 3)), ("cov", cov, (n, 6)), ("opacity", opacity, (n,))):
         if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or n <= 0:
             got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
@@ -265,7 +278,7 @@ def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None
     if h <= 0 or w <= 0 or mats.shape[0] * tx * ty >= 2 ** 31:
         raise hip.MudgError(f"render_differentiable: {mats.shape[0]} views of {h} x {w} (V NT < 2^31)")
     return _Render.apply(xyz, colour, cov, opacity, mats.contiguous(), tuple(float(c) for c in cams), (h, w), ids, float(znear), float(zfar),
-                         int(max_entries))
+                         int(max_entries), density)
 
 
 PARAMETERS = ("xyz", "colour", "log_scale", "quat", "opacity_logit")
@@ -333,17 +346,132 @@ class GaussianModel:
             return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids)
 
 
+# ------------------------------------------------------------------------------------------------ growing and pruning while fitting (§25)
+class DensityStats:
+    """What density control knows about n Gaussians: `grad_sum` (n,) fp32, the sum over the counted views of the norm of the loss's
+    gradient with respect to the projected centre in [-1, 1] screen units, and `seen` (n,) int32, the number of those views.
+    render_differentiable(..., density=stats) adds to both in its backward; reset() zeroes them (reset(n): for n Gaussians)."""
+
+    def __init__(self, n, device):
+        self.device = torch.device(device)
+        if int(n) <= 0 or self.device.type != "cuda":
+            raise hip.MudgError(f"DensityStats: {int(n)} Gaussians on {self.device} (n > 0, on the GPU: there is no CPU path)")
+        self.reset(n)
+
+    def __len__(self):
+        return self.grad_sum.shape[0]
+
+    def reset(self, n=None):
+        n = len(self) if n is None else int(n)
+        self.grad_sum = torch.zeros((n,), dtype=torch.float32, device=self.device)
+        self.seen = torch.zeros((n,), dtype=torch.int32, device=self.device)
+
+
+class DensityControl:
+    """When and how `fit` grows and prunes.  Statistics are gathered in iterations start <= i < stop; after every `every`
+    of them densify_and_prune runs: a Gaussian whose opacity is below min_opacity or whose largest scale exceeds max_scale (metres) goes; one
+    whose mean gradient norm reaches grad_threshold is split in two along its longest axis if that scale exceeds split_scale (metres) and
+    cloned if not.  split_shrink divides a child's scales; the children sit split_offset = sqrt(1 - 1 / split_shrink^2) standard
+    deviations either side of the parent, which keeps the variance along that axis.  reset_every: inside the window, every so many iterations
+    opacities above reset_opacity are set to it.  max_gaussians: a step that would exceed it only prunes.  grad_threshold, min_opacity,
+    reset_opacity and split_shrink default to the 3DGS paper's values and are not tuned here; split_scale and max_scale have no default:
+    the paper derives them from a scene extent this project does not define.  `history` receives one dict of counts per step."""
+
+    def __init__(self, start, stop, every, grad_threshold=2e-4, *, split_scale, max_scale, min_opacity=0.005, reset_every=None,
+                 reset_opacity=0.01, max_gaussians=None, split_shrink=1.6):
+        self.start, self.stop, self.every = int(start), int(stop), int(every)
+        self.grad_threshold, self.split_scale, self.max_scale = float(grad_threshold), float(split_scale), float(max_scale)
+        self.min_opacity, self.reset_opacity, self.split_shrink = float(min_opacity), float(reset_opacity), float(split_shrink)
+        self.reset_every = None if reset_every is None else int(reset_every)
+        self.max_gaussians = None if max_gaussians is None else int(max_gaussians)
+        numbers = (self.grad_threshold, self.split_scale, self.max_scale, self.min_opacity, self.reset_opacity, self.split_shrink)
+        if (self.start < 0 or self.every <= 0 or any(v != v for v in numbers) or not 0.0 < self.reset_opacity < 1.0 or self.split_shrink <= 1.0
+                or (self.reset_every is not None and self.reset_every <= 0) or (self.max_gaussians is not None and self.max_gaussians <= 0)):
+            raise hip.MudgError("DensityControl: start >= 0, every > 0, thresholds that are numbers, 0 < reset_opacity < 1, split_shrink > 1, "
+                                "reset_every and max_gaussians positive or None")
+        self.split_offset = float(np.sqrt(1.0 - 1.0 / self.split_shrink ** 2))
+        self.log_shrink = float(np.float32(np.log(self.split_shrink)))
+        self.reset_logit = float(np.log(self.reset_opacity) - np.log1p(-self.reset_opacity))
+        self.history = []
+
+    def gathers(self, it):
+        return self.start <= it < self.stop
+
+    def densifies_after(self, it):
+        return self.gathers(it) and (it + 1 - self.start) % self.every == 0
+
+    def resets_after(self, it):
+        return self.reset_every is not None and self.gathers(it) and (it + 1) % self.reset_every == 0
+
+
+def densify_and_prune(model: GaussianModel, stats: DensityStats, moments: dict, control: DensityControl, *, grow=True) -> dict:
+    """One step of density control: plan, exclusive sum, apply.  moments: {name: (m, v)}, the Adam moments of the model's
+    parameters (a missing name: zeros).  Replaces the model's five leaves (fresh leaves that require gradients), its ids and the
+    entries of `moments`, and zeroes `stats` at the new size; survivors keep their order and a Gaussian's children are adjacent.  If growing
+    would exceed control.max_gaussians the step is planned again without it.  A step that would leave no Gaussian raises MudgError and
+    leaves everything as it was.  Two host synchronisations: the new count, and the counts returned: {"before", "after", "kept",
+    "pruned", "cloned", "split", "grew"}."""
+    if not isinstance(model, GaussianModel) or not isinstance(stats, DensityStats) or not isinstance(control, DensityControl):
+        raise hip.MudgError("densify_and_prune: expected a GaussianModel, a DensityStats and a DensityControl")
+    n = len(model)
+    if len(stats) != n:
+        raise hip.MudgError(f"densify_and_prune: statistics of {len(stats)} Gaussians for a model of {n}")
+    with torch.no_grad():
+        scale = torch.exp(model.log_scale.detach()).contiguous()
+        rot = rotation_from_quaternions(model.quat.detach()).reshape(n, 9).contiguous()
+        opacity = torch.sigmoid(model.opacity_logit.detach()).contiguous()
+        for grew in ((True, False) if grow else (False,)):
+            action, rows = ops.gauss_density_plan(stats.grad_sum, stats.seen, opacity, scale, grad_threshold=control.grad_threshold,
+                                                  split_scale=control.split_scale, min_opacity=control.min_opacity,
+                                                  max_scale=control.max_scale, grow=grew)
+            ends = torch.cumsum(rows, 0, dtype=torch.int64)
+            total = int(ends[-1].item())
+            if not grew or control.max_gaussians is None or total <= control.max_gaussians:
+                break
+        if total <= 0:
+            raise hip.MudgError(f"densify_and_prune: the step would prune all {n} Gaussians (min_opacity {control.min_opacity}, max_scale "
+                                f"{control.max_scale})")
+        tensors = []
+        for name in PARAMETERS:
+            p = getattr(model, name).detach()
+            m, v = moments[name] if name in moments else (torch.zeros_like(p), torch.zeros_like(p))
+            tensors += [p, m, v]
+        outs, ids = ops.gauss_density_apply(action, ends - rows, total, scale, rot, tensors, split_offset=control.split_offset,
+                                            log_shrink=control.log_shrink, ids=model.ids)
+        kept, pruned, cloned, split = torch.bincount(action, minlength=4).tolist()
+    for k, name in enumerate(PARAMETERS):
+        setattr(model, name, outs[3 * k].requires_grad_(True))
+        moments[name] = (outs[3 * k + 1], outs[3 * k + 2])
+    model.ids = ids
+    stats.reset(total)
+    return {"before": n, "after": total, "kept": kept, "pruned": pruned, "cloned": cloned, "split": split, "grew": grew}
+
+
+def reset_opacity(model: GaussianModel, moments: dict, control: DensityControl):
+    """Opacities above control.reset_opacity become it, and the opacity's two Adam moments start again at zero."""
+    with torch.no_grad():
+        model.opacity_logit.clamp_(max=control.reset_logit)
+        for t in moments.get("opacity_logit", ()):
+            t.zero_()
+
+
 def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_per_step=None, depth_targets=None, depth_weight=0.0,
-        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES):
+        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None):
     """Optimise `model` in place against targets (V, 3, H, W) fp32 in [0, 1] seen through mats (V, nmat, 12) and cams.
     Iteration i renders the views_per_step (default: all) views (i views_per_step + k) mod V, takes the mean absolute difference of rgb,
     adds depth_weight times the mean absolute depth difference over the pixels where depth_targets (V, H, W) is positive, and takes one
     Adam step (betas 0.9 / 0.999, eps 1e-15, no weight decay) through train.kernels.adamw_multi_: one launch for all tensors that share
-    a learning rate.  lr: a dict over PARAMETERS (missing names take LEARNING_RATES) or None; trainable: the names that move.  No
-    densification, pruning, opacity reset, spherical harmonics, SSIM term or pose gradient.  Returns the loss of every iteration."""
+    a learning rate.  lr: a dict over PARAMETERS (missing names take LEARNING_RATES) or None; trainable: the names that move.
+    density: a DensityControl or None.  With one, iterations inside its window gather statistics, densify_and_prune runs
+    after every `every` of them (the model's leaves, the moments and the optimiser's tables are rebuilt, the Adam step count keeps running),
+    opacities are reset every reset_every iterations, and each step's counts are appended to density.history; with None, or an empty
+    window, the fit is the fixed-set fit bit for bit.  No spherical harmonics, SSIM term or pose gradient.  Returns the loss of every
+    iteration."""
     from .train import kernels as K
     if not isinstance(model, GaussianModel):
         raise hip.MudgError("fit: expected a GaussianModel")
+    if density is not None and not isinstance(density, DensityControl):
+        raise hip.MudgError("fit: density is a DensityControl or None")
     h, w = (int(v) for v in hw)
     if not torch.is_tensor(mats) or not mats.is_cuda or mats.dtype != torch.float32 or mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0:
         raise hip.MudgError("fit: the matrices are a (V, nmat, 12) fp32 tensor on the GPU (there is no CPU path)")
@@ -358,18 +486,32 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
     per = views if views_per_step is None else int(views_per_step)
     if not 1 <= per <= views:
         raise hip.MudgError(f"fit: {per} views per step of {views}")
-    params = [getattr(model, n) for n in names]
-    grads = [torch.zeros_like(p) for p in params]
-    moments = [(torch.zeros_like(p), torch.zeros_like(p)) for p in params]
-    tables = {}
-    for rate in sorted({float(rates[n]) for n in names}):
-        rows = [(p.detach(), g, m, v) for n, p, g, (m, v) in zip(names, params, grads, moments) if float(rates[n]) == rate]
-        tables[rate] = K.chunk_table(rows)
+    moments = {}
+
+    def bind():
+        """The optimiser's view of the model's leaves: again after every step that replaced them (their addresses changed)."""
+        params = [getattr(model, n) for n in names]
+        grads = [torch.zeros_like(p) for p in params]
+        for n, p in zip(names, params):
+            if n not in moments:
+                moments[n] = (torch.zeros_like(p), torch.zeros_like(p))
+        tables = {}
+        for rate in sorted({float(rates[n]) for n in names}):
+            rows = [(p.detach(), g, *moments[n]) for n, p, g in zip(names, params, grads) if float(rates[n]) == rate]
+            tables[rate] = K.chunk_table(rows)
+        return params, grads, tables
+
+    params, grads, tables = bind()
+    stats = None
     losses = []
     for it in range(int(iters)):
+        gathers = density is not None and density.gathers(it)
+        if gathers and stats is None:
+            stats = DensityStats(len(model), mats.device)
         pick = torch.tensor([(it * per + k) % views for k in range(per)], device=mats.device)
         rgb, depth, _ = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(), mats[pick], cams, (h, w),
-                                              ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries)
+                                              ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries,
+                                              density=stats if gathers else None)
         loss = (rgb - targets[pick]).abs().mean()
         if depth_targets is not None and depth_weight:
             want = depth_targets[pick]
@@ -380,4 +522,9 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
         for rate, (table, chunks) in tables.items():
             K.adamw_multi_(table, chunks, lr=rate, betas=ADAM_BETAS, eps=ADAM_EPS, weight_decay=0.0, step=it + 1)
         losses.append(loss.detach())
+        if gathers and density.densifies_after(it):
+            density.history.append(dict(densify_and_prune(model, stats, moments, density), iteration=it))
+            params, grads, tables = bind()
+        if gathers and density.resets_after(it):
+            reset_opacity(model, moments, density)
     return torch.stack(losses).tolist() if losses else []

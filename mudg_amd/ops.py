@@ -1075,6 +1075,78 @@ def gauss_project_bwd(points, cov, mats, intr, hw, count, offsets, partial, *, i
     return d_xyz, d_cov, d_opacity, d_colour
 
 
+GAUSS_KEEP, GAUSS_PRUNE, GAUSS_CLONE, GAUSS_SPLIT = 0, 1, 2, 3      # the plan's action codes
+GAUSS_PARAMETER_WIDTHS = (3, 3, 3, 4, 1)                            # xyz, colour, log_scale, quat, opacity_logit
+
+
+def gauss_density_accumulate(partial, count, offsets, hw, grad_sum, seen):
+    """Add every Gaussian's screen-space gradient norm of this backward to grad_sum (n,) fp32 and the views that counted it to seen (n,)
+    int32, in place.  partial (E, 10), count (V, n) and offsets (V, n) are gauss_project_bwd's."""
+    _splat_tensor("gauss_density_accumulate: count", count, torch.int32)
+    if count.dim() != 2 or count.numel() == 0:
+        raise hip.MudgError(f"gauss_density_accumulate: expected counts (V > 0, n > 0), got {tuple(count.shape)}")
+    v, n = count.shape
+    _splat_tensor("gauss_density_accumulate: offsets", offsets, torch.int64, (v, n))
+    _splat_tensor("gauss_density_accumulate: partial", partial, torch.float32)
+    if partial.dim() != 2 or partial.shape[1] != GAUSS_SUMS or partial.shape[0] == 0:
+        raise hip.MudgError(f"gauss_density_accumulate: expected partials (E > 0, {GAUSS_SUMS}), got {tuple(partial.shape)}")
+    _splat_tensor("gauss_density_accumulate: grad_sum", grad_sum, torch.float32, (n,))
+    _splat_tensor("gauss_density_accumulate: seen", seen, torch.int32, (n,))
+    h, w = (int(s) for s in hw)
+    hip.check(hip.lib().mudg_gauss_density_accumulate(partial.data_ptr(), count.data_ptr(), offsets.data_ptr(), n, v, h, w, partial.shape[0],
+                                                      grad_sum.data_ptr(), seen.data_ptr(), _stream()), "mudg_gauss_density_accumulate")
+
+
+def gauss_density_plan(grad_sum, seen, opacity, scale, *, grad_threshold, split_scale, min_opacity, max_scale, grow=True):
+    """What becomes of every Gaussian: action (n,) int32 (GAUSS_KEEP, GAUSS_PRUNE, GAUSS_CLONE, GAUSS_SPLIT) and rows (n,)
+    int32, the rows it leaves (1, 0, 2, 2).  opacity (n,) and scale (n, 3) = exp(log_scale) come evaluated."""
+    _splat_tensor("gauss_density_plan: grad_sum", grad_sum, torch.float32)
+    if grad_sum.dim() != 1 or grad_sum.numel() == 0:
+        raise hip.MudgError(f"gauss_density_plan: expected (n > 0,) gradient sums, got {tuple(grad_sum.shape)}")
+    n = grad_sum.shape[0]
+    _splat_tensor("gauss_density_plan: seen", seen, torch.int32, (n,))
+    _splat_tensor("gauss_density_plan: opacity", opacity, torch.float32, (n,))
+    _splat_tensor("gauss_density_plan: scale", scale, torch.float32, (n, 3))
+    action = torch.empty((n,), dtype=torch.int32, device=grad_sum.device)
+    rows = torch.empty((n,), dtype=torch.int32, device=grad_sum.device)
+    hip.check(hip.lib().mudg_gauss_density_plan(grad_sum.data_ptr(), seen.data_ptr(), opacity.data_ptr(), scale.data_ptr(), n,
+                                                float(grad_threshold), float(split_scale), float(min_opacity), float(max_scale), int(bool(grow)),
+                                                action.data_ptr(), rows.data_ptr(), _stream()), "mudg_gauss_density_plan")
+    return action, rows
+
+
+def gauss_density_apply(action, start, n_out, scale, rot, tensors, *, split_offset, log_shrink, ids=None):
+    """Rewrite the fifteen tensors of a fit as the plan says.  tensors: for each of xyz (n, 3), colour (n, 3), log_scale
+    (n, 3), quat (n, 4), opacity_logit (n,) the value and its two Adam moments, fifteen fp32 tensors in that order; start (n,) int64 the
+    exclusive sum of the plan's rows, n_out its total; scale (n, 3) and rot (n, 9) evaluated by the caller.  Returns the fifteen tensors
+    with n_out rows and ids with n_out rows (or None).  A start that is the exclusive sum of the plan's rows writes every row once."""
+    _splat_tensor("gauss_density_apply: action", action, torch.int32)
+    if action.dim() != 1 or action.numel() == 0:
+        raise hip.MudgError(f"gauss_density_apply: expected (n > 0,) actions, got {tuple(action.shape)}")
+    n, m = action.shape[0], int(n_out)
+    if m <= 0:
+        raise hip.MudgError(f"gauss_density_apply: {m} rows out")
+    _splat_tensor("gauss_density_apply: start", start, torch.int64, (n,))
+    _splat_tensor("gauss_density_apply: scale", scale, torch.float32, (n, 3))
+    _splat_tensor("gauss_density_apply: rot", rot, torch.float32, (n, 9))
+    tensors = list(tensors)
+    if len(tensors) != 3 * len(GAUSS_PARAMETER_WIDTHS):
+        raise hip.MudgError(f"gauss_density_apply: {len(tensors)} tensors (five parameters with two moments each)")
+    for k, t in enumerate(tensors):
+        width = GAUSS_PARAMETER_WIDTHS[k // 3]
+        _splat_tensor(f"gauss_density_apply: tensor {k}", t, torch.float32, (n,) if width == 1 else (n, width))
+    if ids is not None:
+        _splat_tensor("gauss_density_apply: ids", ids, torch.int32, (n,))
+    dev = action.device
+    outs = [torch.empty((m,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in tensors]
+    ids_out = None if ids is None else torch.empty((m,), dtype=torch.int32, device=dev)
+    table = hip.C.c_void_p * len(tensors)                                   # read by the call itself, before it returns
+    src, dst = table(*[t.data_ptr() for t in tensors]), table(*[t.data_ptr() for t in outs])
+    hip.check(hip.lib().mudg_gauss_density_apply(action.data_ptr(), start.data_ptr(), n, m, scale.data_ptr(), rot.data_ptr(), float(split_offset),
+                                                 float(log_shrink), src, dst, _ptr(ids), _ptr(ids_out), _stream()), "mudg_gauss_density_apply")
+    return outs, ids_out
+
+
 # ------------------------------------------------------------------------------------------------ metric depth and lifted views
 def _depth_frames(name, frames):
     _splat_tensor(f"{name}: frames", frames, torch.uint8)

@@ -238,8 +238,10 @@ def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, **k
     cloud, scene, frame_ids, pose, hw_out and scale as render_cloud_views takes them; frames_u8: (t, h, w, 3) uint8 on the GPU at hw_out,
     what the cameras saw (or the model generated) at those frames and that pose.  The frames share one camera: per-frame intrinsics
     that differ are refused.  **kw: opacity (the seed, default 0.9), history (a list that receives the loss of every iteration) and
-    fit's keywords (iters, default 200; lr, views_per_step, depth_targets, depth_weight, trainable, znear, zfar, max_entries).  Returns
-    the fitted mudg_amd.gaussians.Gaussians, which render, render_scene and the renderer of render_cloud_views draw."""
+    fit's keywords (iters, default 200; lr, views_per_step, depth_targets, depth_weight, trainable, znear, zfar, max_entries; density, a
+    mudg_amd.gaussians.DensityControl: the fit then clones, splits and prunes Gaussians, DESIGN.md §25, so that the result need not have
+    the cloud's size).  Returns the fitted mudg_amd.gaussians.Gaussians, which render, render_scene and the renderer of
+    render_cloud_views draw."""
     import numpy as np
     import torch
     from mudg_amd import gaussians, hip, render
