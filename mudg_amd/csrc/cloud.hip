@@ -144,10 +144,12 @@ __global__ __launch_bounds__(256) void cloud_voxel_reduce_kernel(const u32x4* __
     }
     const long long before = __shfl_up(seg, 1, 64);
     const bool head = seg >= 0 && (lane == 0 || before != seg);
+    // A run ends before the next head or dropped lane: a dropped entry inside a run of equal ranks splits it in two, each with a head of
+    // its own, and neither takes the other's lanes (comparing ranks alone would add the second part twice).
+    const unsigned long long ends = __ballot(head || seg < 0);
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-        const long long oseg = __shfl_down(seg, o, 64);
-        const bool take = seg >= 0 && lane + o < 64 && oseg == seg;
+        const bool take = seg >= 0 && lane + o < 64 && ((ends >> (lane + 1)) & ((1ull << o) - 1ull)) == 0ull;
         run_add(cnt, o, take); run_add(r, o, take); run_add(g, o, take); run_add(b, o, take);
         run_add(fx, o, take); run_add(fy, o, take); run_add(fz, o, take);
     }

@@ -57,15 +57,20 @@ class Flat:
     FRONT elements (so `off` alone decides the alignment of the base pointer).  The sentinel is the byte 0xA5 repeated (BYTE), an integer
     pattern that is neither an empty splat key (-1), a key of a small cloud nor a 24-bit colour; nan=True (float32 operands that a kernel
     only reads) fills with NaN instead, so that a read of the padding shows in the result.  Everything is compared as bytes: read()
-    returns the view and asserts that every byte outside it still holds the sentinel, unchanged() that nothing at all was written."""
+    returns the view and asserts that every byte outside it still holds the sentinel, unchanged() that nothing at all was written.
+    fill=value (an element of `dtype`) is for an operand whose rule would ignore both sentinels (a label that is negative, a depth that
+    is not a number): the padding holds a value the rule counts, so that a read of it changes the result; it is compared like the others."""
     FRONT, TAIL = 256, 264
 
-    def __init__(self, n, dtype, *, off=0, nan=False):
+    def __init__(self, n, dtype, *, off=0, nan=False, fill=None):
         assert dtype in (torch.int64, torch.int32, torch.float32, torch.uint8) and not (nan and dtype != torch.float32)
+        assert fill is None or not nan
         self.n, self.dtype, self.off = int(n), dtype, int(off)
         total = self.FRONT + self.off + self.n + self.TAIL
         if nan:
             self.cpu = torch.full((total,), NAN, dtype=dtype)
+        elif fill is not None:
+            self.cpu = torch.full((total,), fill, dtype=dtype)
         else:
             self.cpu = torch.full((total * torch.empty((), dtype=dtype).element_size(),), BYTE, dtype=torch.uint8).view(dtype)
         self.sentinel = self.cpu.clone()
