@@ -669,6 +669,25 @@ int mudg_gauss_density_apply(const int32_t* action, const int64_t* start, int64_
                              float split_offset, float log_shrink, const float* const* src, float* const* dst, const int32_t* ids,
                              int32_t* ids_out, void* stream);
 
+/* The image loss of the fit (csrc/gaussians_loss.hip): (1 - l) mean|x - y| + l (1 - mean S) + depth_weight times the mean
+ * of |d - dt| over the pixels with dt > 0, with l = ssim_weight.  rgb and targets (V, 3, H, W), depth and depth_targets (V, H, W) or both
+ * null: fp32.  S is SSIM per pixel and channel with the 11-tap window mudg_ssim's taps / 65536, zero padding, C1 = 0.01^2, C2 = 0.03^2,
+ * every operation a single rounded fp32 one in the order §26 states.  NT = ceil(W / 16) ceil(H / 16).
+ * loss: maps (V, 3, 3, H, W) = dS/da, dS/db, dS/dc of every pixel (a = w*x, b = w*(x x), c = w*(x y)); partial (V, 3, NT, 4): the
+ *   tile's sum |x - y|, sum S, and in channel 0 the depth sum and the depth count (an int32 in the fourth word; +0.0 and 0 elsewhere).
+ * finish: adds the partials in a fixed order (fp64, the count in int64) into totals (8): the loss, mean |x - y|, mean S, the depth
+ *   mean, float(max(count, 1)), the count as int32 (saturated), 0, 0.
+ * bwd: upstream (1) is the gradient of the loss, on the device.  d_rgb (V, 3, H, W) = upstream ((1 - l) / N sgn(x - y) - l / N dSum S / dx),
+ *   N = 3 V H W; d_depth (V, H, W), or null = upstream depth_weight / totals[4] sgn(d - dt) [dt > 0].  maps and totals are the outputs above.
+ * Refused: null or unaligned pointers, exactly one of depth / depth_targets, d_depth without depth, V, H or W <= 0, V NT >= 2^31,
+ * 3 V NT workgroups beyond a grid, ssim_weight outside [0, 1], a negative or non-finite depth_weight. */
+int mudg_gauss_loss(const float* rgb, const float* targets, const float* depth, const float* depth_targets, int V, int H, int W, float* maps,
+                    float* partial, void* stream);
+int mudg_gauss_loss_finish(const float* partial, int V, int H, int W, float ssim_weight, float depth_weight, float* totals, void* stream);
+int mudg_gauss_loss_bwd(const float* rgb, const float* targets, const float* maps, const float* depth, const float* depth_targets,
+                        const float* totals, const float* upstream, int V, int H, int W, float ssim_weight, float depth_weight, float* d_rgb,
+                        float* d_depth, void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

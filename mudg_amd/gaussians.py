@@ -7,7 +7,8 @@ holes.  Here every point of a PointCloud carries a covariance and an opacity; a 
 the numpy definition that the tests keep reproduces it bit for bit.  Colour is one constant per Gaussian.  `render` is the inference path;
 `render_differentiable`, `GaussianModel` and `fit` optimise position, covariance, opacity and colour against images
 through the backward kernels of csrc/gaussians_bwd.hip; `DensityControl`, `DensityStats` and `densify_and_prune` let a
-fit clone, split and prune its Gaussians through csrc/gaussians_density.hip.  There is no CPU path: tensors that are not on the GPU are
+fit clone, split and prune its Gaussians through csrc/gaussians_density.hip; `image_loss` is 3DGS's L1 + D-SSIM loss with
+its backward in csrc/gaussians_loss.hip, which `fit(..., ssim_weight=0.2)` minimises.  There is no CPU path: tensors that are not on the GPU are
 an error.
 """
 from __future__ import annotations
@@ -455,8 +456,73 @@ def reset_opacity(model: GaussianModel, moments: dict, control: DensityControl):
             t.zero_()
 
 
+# ------------------------------------------------------------------------------------------------ the image loss with an SSIM term (§26)
+class _ImageLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgb, targets, depth, depth_targets, ssim_weight, depth_weight):
+        maps, partial = ops.gauss_loss(rgb, targets, depth, depth_targets)
+        totals = ops.gauss_loss_finish(partial, rgb.shape[2:], ssim_weight=ssim_weight, depth_weight=depth_weight)
+        ctx.weights = (ssim_weight, depth_weight)
+        ctx.has_depth = depth is not None
+        ctx.save_for_backward(rgb, targets, maps, totals, *((depth, depth_targets) if depth is not None else ()))
+        ctx.mark_non_differentiable(totals)
+        return totals[0].clone(), totals
+
+    @staticmethod
+    def backward(ctx, up, _):
+        rgb, targets, maps, totals = ctx.saved_tensors[:4]
+        depth, depth_targets = ctx.saved_tensors[4:] if ctx.has_depth else (None, None)
+        ssim_weight, depth_weight = ctx.weights
+        up = up.to(torch.float32).reshape(1).contiguous()                   # stays on the device: the kernel reads it
+        d_rgb, d_depth = ops.gauss_loss_bwd(rgb, targets, maps, totals, up, depth, depth_targets, ssim_weight=ssim_weight,
+                                            depth_weight=depth_weight, want_depth=ctx.has_depth and ctx.needs_input_grad[2])
+        return d_rgb, None, d_depth, None, None, None
+
+
+def _image_loss_args(rgb, targets, depth, depth_targets, ssim_weight, depth_weight):
+    if not torch.is_tensor(rgb) or rgb.dim() != 4 or rgb.shape[1] != 3 or rgb.numel() == 0:
+        got = tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__
+        raise hip.MudgError(f"image_loss: rgb is a (V, 3, H, W) fp32 tensor on the GPU (there is no CPU path), got {got}")
+    v, _, h, w = rgb.shape
+    rgb = _on_gpu("image_loss: rgb", rgb, torch.float32, (v, 3, h, w))
+    targets = _on_gpu("image_loss: targets", targets, torch.float32, (v, 3, h, w))
+    if (depth is None) != (depth_targets is None):
+        raise hip.MudgError("image_loss: depth and depth_targets come together or not at all")
+    if depth is not None:
+        depth = _on_gpu("image_loss: depth", depth, torch.float32, (v, h, w))
+        depth_targets = _on_gpu("image_loss: depth_targets", depth_targets, torch.float32, (v, h, w))
+    ssim_weight, depth_weight = float(ssim_weight), float(depth_weight)
+    if not 0.0 <= ssim_weight <= 1.0 or not (0.0 <= depth_weight < float("inf")):
+        raise hip.MudgError(f"image_loss: ssim_weight {ssim_weight} lies in [0, 1] and depth_weight {depth_weight} is finite and not negative")
+    return rgb, targets, depth, depth_targets, ssim_weight, depth_weight
+
+
+def image_loss(rgb, targets, depth=None, depth_targets=None, *, ssim_weight=0.2, depth_weight=0.0):
+    """(1 - ssim_weight) mean|rgb - targets| + ssim_weight (1 - mean SSIM) + depth_weight times the mean of |depth - depth_targets| over
+    the pixels where depth_targets is positive (divisor at least 1): 3DGS's L1 + D-SSIM loss with fit's depth term, in three launches of
+    csrc/gaussians_loss.hip.  rgb and targets (V, 3, H, W), depth and depth_targets (V, H, W) or both None: fp32 on the
+    GPU.  Returns a 0-d fp32 loss whose backward gives gradients for rgb and depth, with no host synchronisation on either side.  SSIM here
+    is the training convention: float images, the 11-tap window ops.SSIM_WINDOW / 65536 with zero padding so that every pixel has a value
+    (images below 11 x 11 are legal), C1 = 0.01^2, C2 = 0.03^2, the mean over all V 3 H W values.  It is not metrics.psnr_ssim's
+    convention, which takes uint8 frames, the valid region only and integer moments.  image_loss.terms gives the parts for logging."""
+    return _ImageLoss.apply(*_image_loss_args(rgb, targets, depth, depth_targets, ssim_weight, depth_weight))[0]
+
+
+def _image_loss_terms(rgb, targets, depth=None, depth_targets=None, *, ssim_weight=0.2, depth_weight=0.0):
+    """The parts of image_loss as 0-d fp32 tensors on the GPU, without gradients: loss, l1 (mean |rgb - targets|), ssim (mean S), depth (the
+    masked mean absolute depth difference) and depth_count (the pixels it is over, int32)."""
+    rgb, targets, depth, depth_targets, ssim_weight, depth_weight = _image_loss_args(rgb, targets, depth, depth_targets, ssim_weight, depth_weight)
+    with torch.no_grad():
+        _, partial = ops.gauss_loss(rgb.detach(), targets.detach(), None if depth is None else depth.detach(), depth_targets)
+        totals = ops.gauss_loss_finish(partial, rgb.shape[2:], ssim_weight=ssim_weight, depth_weight=depth_weight)
+    return dict(loss=totals[0], l1=totals[1], ssim=totals[2], depth=totals[3], depth_count=totals.view(torch.int32)[5])
+
+
+image_loss.terms = _image_loss_terms
+
+
 def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_per_step=None, depth_targets=None, depth_weight=0.0,
-        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None):
+        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None, ssim_weight=0.0):
     """Optimise `model` in place against targets (V, 3, H, W) fp32 in [0, 1] seen through mats (V, nmat, 12) and cams.
     Iteration i renders the views_per_step (default: all) views (i views_per_step + k) mod V, takes the mean absolute difference of rgb,
     adds depth_weight times the mean absolute depth difference over the pixels where depth_targets (V, H, W) is positive, and takes one
@@ -465,13 +531,19 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
     density: a DensityControl or None.  With one, iterations inside its window gather statistics, densify_and_prune runs
     after every `every` of them (the model's leaves, the moments and the optimiser's tables are rebuilt, the Adam step count keeps running),
     opacities are reset every reset_every iterations, and each step's counts are appended to density.history; with None, or an empty
-    window, the fit is the fixed-set fit bit for bit.  No spherical harmonics, SSIM term or pose gradient.  Returns the loss of every
+    window, the fit is the fixed-set fit bit for bit.  ssim_weight: with 0 (the default) the loss is the torch expression above, bit for
+    bit what it was before the keyword existed; with a value in (0, 1] the iteration's loss is image_loss:
+    (1 - ssim_weight) times the mean absolute difference plus ssim_weight (1 - mean SSIM) plus the same depth term, forward and backward
+    in the kernels of csrc/gaussians_loss.hip; 3DGS fits with 0.2.  No spherical harmonics or pose gradient.  Returns the loss of every
     iteration."""
     from .train import kernels as K
     if not isinstance(model, GaussianModel):
         raise hip.MudgError("fit: expected a GaussianModel")
     if density is not None and not isinstance(density, DensityControl):
         raise hip.MudgError("fit: density is a DensityControl or None")
+    ssim_weight = float(ssim_weight)
+    if not 0.0 <= ssim_weight <= 1.0:
+        raise hip.MudgError(f"fit: ssim_weight {ssim_weight} lies in [0, 1]")
     h, w = (int(v) for v in hw)
     if not torch.is_tensor(mats) or not mats.is_cuda or mats.dtype != torch.float32 or mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0:
         raise hip.MudgError("fit: the matrices are a (V, nmat, 12) fp32 tensor on the GPU (there is no CPU path)")
@@ -512,11 +584,16 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
         rgb, depth, _ = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(), mats[pick], cams, (h, w),
                                               ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries,
                                               density=stats if gathers else None)
-        loss = (rgb - targets[pick]).abs().mean()
-        if depth_targets is not None and depth_weight:
-            want = depth_targets[pick]
-            seen = want > 0
-            loss = loss + float(depth_weight) * ((depth - want).abs() * seen).sum() / seen.sum().clamp(min=1)
+        with_depth = depth_targets is not None and bool(depth_weight)
+        if ssim_weight:                                                     # §26: the loss and its backward in csrc/gaussians_loss.hip
+            loss = image_loss(rgb, targets[pick], depth if with_depth else None, depth_targets[pick] if with_depth else None,
+                              ssim_weight=ssim_weight, depth_weight=float(depth_weight) if with_depth else 0.0)
+        else:
+            loss = (rgb - targets[pick]).abs().mean()
+            if with_depth:
+                want = depth_targets[pick]
+                seen = want > 0
+                loss = loss + float(depth_weight) * ((depth - want).abs() * seen).sum() / seen.sum().clamp(min=1)
         for g, d in zip(grads, torch.autograd.grad(loss, params, allow_unused=True)):
             g.zero_() if d is None else g.copy_(d)
         for rate, (table, chunks) in tables.items():

@@ -200,6 +200,9 @@ SIGNATURES = {
     "mudg_gauss_density_accumulate": (_I, [_P, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P]),
     "mudg_gauss_density_plan": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _P, _P, _P]),
     "mudg_gauss_density_apply": (_I, [_P, _P, _L, _L, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "mudg_gauss_loss": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "mudg_gauss_loss_finish": (_I, [_P, _I, _I, _I, _F, _F, _P, _P]),
+    "mudg_gauss_loss_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P]),
     "mudg_short_attention_ok": (_I, [C.POINTER(ShortAttnDesc)]),
     "mudg_short_attention": (_I, [C.POINTER(ShortAttnDesc), _P]),
     "mudg_layernorm_f32": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P]),

@@ -1147,6 +1147,69 @@ def gauss_density_apply(action, start, n_out, scale, rot, tensors, *, split_offs
     return outs, ids_out
 
 
+GAUSS_LOSS_COLS, GAUSS_LOSS_TOTALS = 4, 8                           # a tile's partial row; the finish buffer
+
+
+def _gauss_loss_images(name, rgb, targets, depth, depth_targets):
+    _splat_tensor(f"{name}: rgb", rgb, torch.float32)
+    if rgb.dim() != 4 or rgb.shape[1] != 3 or rgb.numel() == 0:
+        raise hip.MudgError(f"{name}: expected (V > 0, 3, H > 0, W > 0) images, got {tuple(rgb.shape)}")
+    v, _, h, w = rgb.shape
+    _splat_tensor(f"{name}: targets", targets, torch.float32, (v, 3, h, w))
+    if (depth is None) != (depth_targets is None):
+        raise hip.MudgError(f"{name}: depth and depth_targets come together or not at all")
+    if depth is not None:
+        _splat_tensor(f"{name}: depth", depth, torch.float32, (v, h, w))
+        _splat_tensor(f"{name}: depth_targets", depth_targets, torch.float32, (v, h, w))
+    tx, ty = gauss_tiles(h, w)
+    return v, h, w, tx * ty
+
+
+def gauss_loss(rgb, targets, depth=None, depth_targets=None):
+    """The forward of the fit's image loss.  rgb and targets (V, 3, H, W), depth and depth_targets (V, H, W) or both None:
+    fp32 on the GPU.  Returns maps (V, 3, 3, H, W), the derivatives of every pixel's SSIM value with respect to the three windowed moments
+    of rgb, and partial (V, 3, NT, 4): each 16 x 16 tile's sum |x - y|, sum S, depth sum and depth count (int32 bits).  The window is
+    SSIM_WINDOW / 65536 with zero padding on float images: not metrics.psnr_ssim's convention (uint8, valid region, integer moments)."""
+    v, h, w, nt = _gauss_loss_images("gauss_loss", rgb, targets, depth, depth_targets)
+    maps = torch.empty((v, 3, 3, h, w), dtype=torch.float32, device=rgb.device)
+    partial = torch.empty((v, 3, nt, GAUSS_LOSS_COLS), dtype=torch.float32, device=rgb.device)
+    hip.check(hip.lib().mudg_gauss_loss(rgb.data_ptr(), targets.data_ptr(), _ptr(depth), _ptr(depth_targets), v, h, w, maps.data_ptr(),
+                                        partial.data_ptr(), _stream()), "mudg_gauss_loss")
+    return maps, partial
+
+
+def gauss_loss_finish(partial, hw, *, ssim_weight, depth_weight=0.0):
+    """gauss_loss's partials (V, 3, NT, 4) of (H, W) images -> totals (8,) fp32: the loss, mean |x - y|, mean S, the depth mean,
+    float(max(count, 1)), the depth count as int32 bits, 0, 0.  One workgroup, one fixed order, no host synchronisation."""
+    h, w = (int(s) for s in hw)
+    tx, ty = gauss_tiles(h, w)
+    _splat_tensor("gauss_loss_finish: partial", partial, torch.float32)
+    if partial.dim() != 4 or partial.shape[0] == 0 or tuple(partial.shape[1:]) != (3, tx * ty, GAUSS_LOSS_COLS):
+        raise hip.MudgError(f"gauss_loss_finish: expected partials (V > 0, 3, {tx * ty}, {GAUSS_LOSS_COLS}) for {h} x {w}, got {tuple(partial.shape)}")
+    totals = torch.empty((GAUSS_LOSS_TOTALS,), dtype=torch.float32, device=partial.device)
+    hip.check(hip.lib().mudg_gauss_loss_finish(partial.data_ptr(), partial.shape[0], h, w, float(ssim_weight), float(depth_weight),
+                                               totals.data_ptr(), _stream()), "mudg_gauss_loss_finish")
+    return totals
+
+
+def gauss_loss_bwd(rgb, targets, maps, totals, upstream, depth=None, depth_targets=None, *, ssim_weight, depth_weight=0.0, want_depth=True):
+    """The backward of the fit's image loss: d_rgb (V, 3, H, W) and d_depth (V, H, W) (None without the depth pair or with
+    want_depth false).  maps and totals are gauss_loss's and gauss_loss_finish's; upstream is the loss's gradient, one fp32 on the GPU,
+    read by the kernel."""
+    v, h, w, _ = _gauss_loss_images("gauss_loss_bwd", rgb, targets, depth, depth_targets)
+    _splat_tensor("gauss_loss_bwd: maps", maps, torch.float32, (v, 3, 3, h, w))
+    _splat_tensor("gauss_loss_bwd: totals", totals, torch.float32, (GAUSS_LOSS_TOTALS,))
+    _splat_tensor("gauss_loss_bwd: upstream", upstream, torch.float32)
+    if upstream.numel() != 1:
+        raise hip.MudgError(f"gauss_loss_bwd: the upstream gradient is one number, got {tuple(upstream.shape)}")
+    d_rgb = torch.empty((v, 3, h, w), dtype=torch.float32, device=rgb.device)
+    d_depth = torch.empty((v, h, w), dtype=torch.float32, device=rgb.device) if depth is not None and want_depth else None
+    hip.check(hip.lib().mudg_gauss_loss_bwd(rgb.data_ptr(), targets.data_ptr(), maps.data_ptr(), _ptr(depth), _ptr(depth_targets),
+                                            totals.data_ptr(), upstream.data_ptr(), v, h, w, float(ssim_weight), float(depth_weight),
+                                            d_rgb.data_ptr(), _ptr(d_depth), _stream()), "mudg_gauss_loss_bwd")
+    return d_rgb, d_depth
+
+
 # ------------------------------------------------------------------------------------------------ metric depth and lifted views
 def _depth_frames(name, frames):
     _splat_tensor(f"{name}: frames", frames, torch.uint8)

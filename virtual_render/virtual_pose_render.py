@@ -240,7 +240,8 @@ def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, **k
     that differ are refused.  **kw: opacity (the seed, default 0.9), history (a list that receives the loss of every iteration) and
     fit's keywords (iters, default 200; lr, views_per_step, depth_targets, depth_weight, trainable, znear, zfar, max_entries; density, a
     mudg_amd.gaussians.DensityControl: the fit then clones, splits and prunes Gaussians, DESIGN.md §25, so that the result need not have
-    the cloud's size).  Returns the fitted mudg_amd.gaussians.Gaussians, which render, render_scene and the renderer of
+    the cloud's size; ssim_weight, default 0: above it the fit minimises mudg_amd.gaussians.image_loss, L1 + D-SSIM, DESIGN.md §26, and
+    3DGS's value is 0.2).  Returns the fitted mudg_amd.gaussians.Gaussians, which render, render_scene and the renderer of
     render_cloud_views draw."""
     import numpy as np
     import torch
