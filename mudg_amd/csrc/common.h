@@ -202,6 +202,7 @@ static inline int mudg_check_launch(const char* what) {
     return MUDG_OK;
 }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // Per-device host state (capi.hip) is kept in arrays of MAX_DEVICES: one process may drive several GPUs.
 constexpr int MAX_DEVICES = 64;

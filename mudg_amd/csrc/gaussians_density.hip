@@ -12,7 +12,6 @@
 
 namespace {
 
-constexpr int SUMS = 10;                            // a partial's row (gaussians_bwd.hip); columns 8 and 9 are du, dv
 constexpr int KEEP = 0, PRUNE = 1, CLONE = 2, SPLIT = 3;
 constexpr int TENSORS = 15;                         // 3 p + k: parameter p (xyz, colour, log_scale, quat, opacity_logit), k = value, m, v
 constexpr int P_XYZ = 0, P_LOG_SCALE = 2;
@@ -31,20 +30,11 @@ __global__ __launch_bounds__(256) void gauss_density_accumulate_kernel(const flo
     float total = grad_sum[idx];
     int32_t views = seen[idx];
     for (int view = 0; view < V; ++view) {
-        const int64_t o = (int64_t)view * n + idx;
-        const int cnt = count[o];
-        if (cnt <= 0) continue;                                             // dropped in this view
-        const int64_t off = offsets[o];
-        if (off < 0 || off > E - cnt) continue;                             // not this call's entries
-        float su = 0.0f, sv = 0.0f;
-        for (int k = 0; k < cnt; ++k) {
-            const float* p = partial + (off + k) * SUMS;
-            su = add(su, p[8]);
-            sv = add(sv, p[9]);
-        }
-        const float a = mul(half_w, su), b = mul(half_h, sv);
-        total = add(total, sqrtf(add(mul(a, a), mul(b, b))));              // sqrtf: the correctly rounded root (__fsqrt_rn is the native one)
-        views += 1;
+        with_partials<SUM_U, 2>(partial, count, offsets, (int64_t)view * n + idx, E, [&](const float (&s)[2]) {         // du, dv
+            const float a = mul(half_w, s[0]), b = mul(half_h, s[1]);
+            total = add(total, sqrtf(add(mul(a, a), mul(b, b))));          // sqrtf: the correctly rounded root (__fsqrt_rn is the native one)
+            views += 1;
+        });
     }
     grad_sum[idx] = total;
     seen[idx] = views;
@@ -115,7 +105,6 @@ __global__ __launch_bounds__(256) void gauss_density_apply_kernel(const int32_t*
     }
 }
 
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 inline bool rows_ok(int64_t n) { return n >= 1 && n <= 0x7fffffffLL; }
 
 }  // namespace

@@ -11,6 +11,7 @@
 // Everything on images is fp32, each operation a single rounded one in the order DESIGN.md §26 writes it, so every output is bit-equal to
 // the numpy definition in tests/gaussians_loss_reference.py and a repeat run gives the same bits.  No address depends on a pixel value.
 // No MFMA operand is touched.
+#include "depth_shared.h"
 #include "gauss_shared.h"
 
 namespace {
@@ -40,6 +41,20 @@ __device__ __forceinline__ void stage_apron(const float* __restrict__ plane, int
     }
 }
 
+// the vertical pass of the window at the lane's pixel (row, col) of the tile, over the N planes the horizontal pass left in LDS
+template <int N>
+__device__ __forceinline__ void window_vertical(const float (&rows)[N][APRON * TILE], int row, int col, float (&out)[N]) {
+#pragma unroll
+    for (int p = 0; p < N; ++p) out[p] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < TAPS; ++q) {
+        const int k = (row + q) * TILE + col;
+        const float w = tap(q);
+#pragma unroll
+        for (int p = 0; p < N; ++p) out[p] = add(out[p], mul(w, rows[p][k]));
+    }
+}
+
 __global__ __launch_bounds__(256) void gauss_loss_kernel(const float* __restrict__ rgb, const float* __restrict__ targets,
                                                           const float* __restrict__ depth, const float* __restrict__ depth_targets, int TX,
                                                           int NT, int H, int W, float* __restrict__ maps, float* __restrict__ partial) {
@@ -48,9 +63,9 @@ __global__ __launch_bounds__(256) void gauss_loss_kernel(const float* __restrict
     __shared__ float rows[MOMENTS][APRON * TILE];                           // the horizontal pass: 26 rows of 16 columns
     __shared__ float wsum[4][COLS];
     const int64_t t = blockIdx.x;
-    const int64_t vc = t / NT;                                              // view * 3 + channel
-    const int tile = (int)(t - vc * NT);
-    const int ti = tile % TX, tj = tile / TX;
+    const TileId id = tile_id(t, TX, NT);
+    const int64_t vc = id.group;                                            // view * 3 + channel
+    const int ti = id.ti, tj = id.tj;
     const int64_t plane = (int64_t)H * W;
     stage_apron(rgb + vc * plane, ti, tj, H, W, xs);
     stage_apron(targets + vc * plane, ti, tj, H, W, ys);
@@ -73,17 +88,9 @@ __global__ __launch_bounds__(256) void gauss_loss_kernel(const float* __restrict
     const int col = threadIdx.x & (TILE - 1), row = threadIdx.x >> 4;
     const int i = ti * TILE + col, j = tj * TILE + row;
     const bool inside = i < W && j < H;
-    float a = 0.0f, m = 0.0f, b = 0.0f, n = 0.0f, c = 0.0f;
-#pragma unroll
-    for (int q = 0; q < TAPS; ++q) {
-        const int k = (row + q) * TILE + col;
-        const float w = tap(q);
-        a = add(a, mul(w, rows[0][k]));
-        m = add(m, mul(w, rows[1][k]));
-        b = add(b, mul(w, rows[2][k]));
-        n = add(n, mul(w, rows[3][k]));
-        c = add(c, mul(w, rows[4][k]));
-    }
+    float mom[MOMENTS];
+    window_vertical(rows, row, col, mom);
+    const float a = mom[0], m = mom[1], b = mom[2], n = mom[3], c = mom[4];
     const float aa = mul(a, a), mm = mul(m, m), am = mul(a, m);
     const float s1 = sub(b, aa), s2 = sub(n, mm), s12 = sub(c, am);
     const float A1 = add(mul(2.0f, am), C1), A2 = add(mul(2.0f, s12), C2);
@@ -109,13 +116,10 @@ __global__ __launch_bounds__(256) void gauss_loss_kernel(const float* __restrict
             }
         }
     }
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        r0 = add(r0, __shfl_xor(r0, s));
-        r1 = add(r1, __shfl_xor(r1, s));
-        r2 = add(r2, __shfl_xor(r2, s));
-        r3 += __shfl_xor(r3, s);
-    }
+    r0 = butterfly_sum(r0);
+    r1 = butterfly_sum(r1);
+    r2 = butterfly_sum(r2);
+    r3 = butterfly_sum(r3);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         wsum[wave][0] = r0; wsum[wave][1] = r1; wsum[wave][2] = r2; wsum[wave][3] = __int_as_float(r3);
@@ -123,9 +127,9 @@ __global__ __launch_bounds__(256) void gauss_loss_kernel(const float* __restrict
     __syncthreads();
     if (threadIdx.x < 3) {
         const int k = threadIdx.x;
-        partial[t * COLS + k] = add(add(add(wsum[0][k], wsum[1][k]), wsum[2][k]), wsum[3][k]);
+        partial[t * COLS + k] = four_waves(wsum[0][k], wsum[1][k], wsum[2][k], wsum[3][k]);
     } else if (threadIdx.x == 3) {
-        const int cnt = __float_as_int(wsum[0][3]) + __float_as_int(wsum[1][3]) + __float_as_int(wsum[2][3]) + __float_as_int(wsum[3][3]);
+        const int cnt = four_waves(__float_as_int(wsum[0][3]), __float_as_int(wsum[1][3]), __float_as_int(wsum[2][3]), __float_as_int(wsum[3][3]));
         partial[t * COLS + 3] = __int_as_float(cnt);
     }
 }
@@ -143,23 +147,20 @@ __global__ __launch_bounds__(256) void gauss_loss_finish_kernel(const float* __r
         dd += (double)row[2];
         cnt += (long long)__float_as_int(row[3]);
     }
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        l1 += __shfl_xor(l1, s);
-        ss += __shfl_xor(ss, s);
-        dd += __shfl_xor(dd, s);
-        cnt += __shfl_xor(cnt, s);
-    }
+    l1 = butterfly_sum(l1);
+    ss = butterfly_sum(ss);
+    dd = butterfly_sum(dd);
+    cnt = butterfly_sum(cnt);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         wreal[wave][0] = l1; wreal[wave][1] = ss; wreal[wave][2] = dd; wcount[wave] = cnt;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double L = ((wreal[0][0] + wreal[1][0]) + wreal[2][0]) + wreal[3][0];
-        const double S = ((wreal[0][1] + wreal[1][1]) + wreal[2][1]) + wreal[3][1];
-        const double D = ((wreal[0][2] + wreal[1][2]) + wreal[2][2]) + wreal[3][2];
-        const long long count = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        const double L = four_waves(wreal[0][0], wreal[1][0], wreal[2][0], wreal[3][0]);
+        const double S = four_waves(wreal[0][1], wreal[1][1], wreal[2][1], wreal[3][1]);
+        const double D = four_waves(wreal[0][2], wreal[1][2], wreal[2][2], wreal[3][2]);
+        const long long count = four_waves(wcount[0], wcount[1], wcount[2], wcount[3]);
         const long long seen = count < 1 ? 1 : count;
         const float l1_mean = (float)(L / N), s_mean = (float)(S / N), d_mean = (float)(D / (double)seen);
         totals[0] = add(add(mul(sub(1.0f, ssim_weight), l1_mean), mul(ssim_weight, sub(1.0f, s_mean))), mul(depth_weight, d_mean));
@@ -181,10 +182,9 @@ __global__ __launch_bounds__(256) void gauss_loss_bwd_kernel(const float* __rest
                                                               float* __restrict__ d_depth) {
     __shared__ float ms[MAPS][APRON * APRON];
     __shared__ float rows[MAPS][APRON * TILE];
-    const int64_t t = blockIdx.x;
-    const int64_t vc = t / NT;
-    const int tile = (int)(t - vc * NT);
-    const int ti = tile % TX, tj = tile / TX;
+    const TileId id = tile_id(blockIdx.x, TX, NT);
+    const int64_t vc = id.group;
+    const int ti = id.ti, tj = id.tj;
     const int64_t plane = (int64_t)H * W;
 #pragma unroll
     for (int k = 0; k < MAPS; ++k) stage_apron(maps + (vc * MAPS + k) * plane, ti, tj, H, W, ms[k]);
@@ -205,15 +205,9 @@ __global__ __launch_bounds__(256) void gauss_loss_bwd_kernel(const float* __rest
     const int col = threadIdx.x & (TILE - 1), row = threadIdx.x >> 4;
     const int i = ti * TILE + col, j = tj * TILE + row;
     if (!(i < W && j < H)) return;                                          // no barrier follows
-    float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
-#pragma unroll
-    for (int q = 0; q < TAPS; ++q) {
-        const int k = (row + q) * TILE + col;
-        const float w = tap(q);
-        g0 = add(g0, mul(w, rows[0][k]));
-        g1 = add(g1, mul(w, rows[1][k]));
-        g2 = add(g2, mul(w, rows[2][k]));
-    }
+    float gm[MAPS];
+    window_vertical(rows, row, col, gm);
+    const float g0 = gm[0], g1 = gm[1], g2 = gm[2];
     const int64_t pix = (int64_t)j * W + i;
     const float x = rgb[vc * plane + pix], y = targets[vc * plane + pix];
     const float up = upstream[0];
@@ -228,13 +222,11 @@ __global__ __launch_bounds__(256) void gauss_loss_bwd_kernel(const float* __rest
     }
 }
 
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 // the image, the tile grid (V NT < 2^31) and the launch grid of one workgroup per (view, channel, tile)
 inline int check_image(const char* name, int V, int H, int W) {
     MUDG_REQUIRE(V > 0 && H > 0 && W > 0, "%s: %d views of %d x %d", name, V, H, W);
     if (const int e = check_views(name, 1, V, H, W)) return e;
-    const int64_t NT = (int64_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+    const int64_t NT = GaussGrid(H, W).NT;
     MUDG_REQUIRE(3 * (int64_t)V * NT <= 0x7fffffffLL, "%s: %d views of 3 x %lld tiles are more workgroups than a grid holds", name, V,
                  (long long)NT);
     return MUDG_OK;
@@ -256,9 +248,9 @@ extern "C" int mudg_gauss_loss(const float* rgb, const float* targets, const flo
     MUDG_REQUIRE(aligned4(rgb) && aligned4(targets) && aligned4(depth) && aligned4(depth_targets) && aligned4(maps) && aligned4(partial),
                  "mudg_gauss_loss: unaligned argument");
     if (const int e = check_image("mudg_gauss_loss", V, H, W)) return e;
-    const int TX = (W + TILE - 1) / TILE, NT = TX * ((H + TILE - 1) / TILE);
-    hipLaunchKernelGGL(gauss_loss_kernel, dim3((unsigned)(3 * (int64_t)V * NT)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), rgb, targets,
-                       depth, depth_targets, TX, NT, H, W, maps, partial);
+    const GaussGrid grid(H, W);
+    hipLaunchKernelGGL(gauss_loss_kernel, dim3((unsigned)(3 * (int64_t)V * grid.NT)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), rgb, targets,
+                       depth, depth_targets, grid.TX, grid.NT, H, W, maps, partial);
     return mudg_check_launch("mudg_gauss_loss");
 }
 
@@ -268,7 +260,7 @@ extern "C" int mudg_gauss_loss_finish(const float* partial, int V, int H, int W,
     MUDG_REQUIRE(aligned4(partial) && aligned4(totals), "mudg_gauss_loss_finish: unaligned argument");
     if (const int e = check_image("mudg_gauss_loss_finish", V, H, W)) return e;
     if (const int e = check_weights("mudg_gauss_loss_finish", ssim_weight, depth_weight)) return e;
-    const int64_t NT = (int64_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+    const int64_t NT = GaussGrid(H, W).NT;
     hipLaunchKernelGGL(gauss_loss_finish_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), partial, 3 * (int64_t)V * NT,
                        3.0 * (double)V * (double)H * (double)W, ssim_weight, depth_weight, totals);
     return mudg_check_launch("mudg_gauss_loss_finish");
@@ -285,9 +277,9 @@ extern "C" int mudg_gauss_loss_bwd(const float* rgb, const float* targets, const
                  "mudg_gauss_loss_bwd: unaligned argument");
     if (const int e = check_image("mudg_gauss_loss_bwd", V, H, W)) return e;
     if (const int e = check_weights("mudg_gauss_loss_bwd", ssim_weight, depth_weight)) return e;
-    const int TX = (W + TILE - 1) / TILE, NT = TX * ((H + TILE - 1) / TILE);
+    const GaussGrid grid(H, W);
     const float count = (float)(3.0 * (double)V * (double)H * (double)W);   // N, rounded once
-    hipLaunchKernelGGL(gauss_loss_bwd_kernel, dim3((unsigned)(3 * (int64_t)V * NT)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), rgb,
-                       targets, maps, depth, depth_targets, totals, upstream, TX, NT, H, W, count, ssim_weight, depth_weight, d_rgb, d_depth);
+    hipLaunchKernelGGL(gauss_loss_bwd_kernel, dim3((unsigned)(3 * (int64_t)V * grid.NT)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), rgb,
+                       targets, maps, depth, depth_targets, totals, upstream, grid.TX, grid.NT, H, W, count, ssim_weight, depth_weight, d_rgb, d_depth);
     return mudg_check_launch("mudg_gauss_loss_bwd");
 }

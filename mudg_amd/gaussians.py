@@ -13,6 +13,7 @@ an error.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -113,6 +114,33 @@ class Gaussians:
         return cls.from_cloud(PointCloud.concatenated(background, objects.cloud), s, opacity, ids)
 
 
+def _bin(name, pts, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries):
+    """Project, scan the tile counts, read the entry count E (the one host synchronisation) and refuse too many in `name`'s words, then
+    keys, the stable sort and the tiles' ranges.  Returns a namespace of uv, conic, depth, rect, count, offsets, entries (E), values
+    (sorted), order and ranges; the last three are None when E is 0."""
+    uv, conic, depth, rect, count = ops.gauss_project(pts, cov, opacity, mats, cams, hw, ids=ids, znear=znear, zfar=zfar)
+    ends = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
+    offsets = (ends - count.reshape(-1)).reshape(count.shape)
+    entries = int(ends[-1].item())
+    if entries >= 2 ** 31 or entries > int(max_entries):
+        raise hip.MudgError(f"{name}: {entries} (tile, Gaussian) entries exceed max_entries = {int(max_entries)} (and must stay below 2^31): "
+                            "thin the cloud, shrink the scale or draw fewer views per call")
+    b = SimpleNamespace(uv=uv, conic=conic, depth=depth, rect=rect, count=count, offsets=offsets, entries=entries, values=None, order=None,
+                        ranges=None)
+    if entries:
+        keys, values = ops.gauss_keys(depth, rect, count, offsets, entries, hw)
+        keys, b.order = torch.sort(keys, stable=True)
+        tx, ty = ops.gauss_tiles(*hw)
+        b.values, b.ranges = values[b.order], ops.gauss_ranges(keys, mats.shape[0] * tx * ty)
+    return b
+
+
+def _blank(views, h, w, device):
+    """(rgb, depth, alpha) of a call that drew nothing."""
+    return (torch.zeros((views, 3, h, w), dtype=torch.float32, device=device), torch.zeros((views, h, w), dtype=torch.float32, device=device),
+            torch.zeros((views, h, w), dtype=torch.float32, device=device))
+
+
 def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, stats=None):
     """Draw `g` into V views.  mats: (V, nmat, 12) fp32 on the GPU, row-major 3 x 4 matrices, mats[v][0] the world-to-camera matrix of
     view v and mats[v][1 + o] that matrix times object o's transform (zero for an object the view does not show); cams: (fx, fy, cx, cy)
@@ -134,27 +162,15 @@ def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=
     if g.ids is None and mats.shape[1] != 1:
         raise hip.MudgError(f"render: {mats.shape[1]} matrices per view need Gaussians with ids")
     pts, dev = g.cloud.points, g.cloud.points.device
-    uv, conic, depth, rect, count = ops.gauss_project(pts, g.cov, g.opacity, mats.contiguous(), cams, (h, w), ids=g.ids, znear=znear, zfar=zfar)
-    ends = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
-    offsets = (ends - count.reshape(-1)).reshape(count.shape)
-    entries = int(ends[-1].item())
-    if entries >= 2 ** 31 or entries > int(max_entries):
-        raise hip.MudgError(f"render: {entries} (tile, Gaussian) entries exceed max_entries = {int(max_entries)} (and must stay below 2^31): "
-                            "thin the cloud, shrink the scale or draw fewer views per call")
+    b = _bin("render", pts, g.cov, g.opacity, mats.contiguous(), cams, (h, w), g.ids, znear, zfar, max_entries)
     if stats is not None:
-        stats.update(entries=entries, longest_tile=0, count=count, rect=rect, values=None, ranges=None)
-    if entries == 0:
-        return {"rgb": torch.zeros((views, 3, h, w), dtype=torch.float32, device=dev),
-                "depth": torch.zeros((views, h, w), dtype=torch.float32, device=dev),
-                "alpha": torch.zeros((views, h, w), dtype=torch.float32, device=dev)}
-    keys, values = ops.gauss_keys(depth, rect, count, offsets, entries, (h, w))
-    keys, order = torch.sort(keys, stable=True)
-    values = values[order]
-    ranges = ops.gauss_ranges(keys, tiles)
+        stats.update(entries=b.entries, longest_tile=0, count=b.count, rect=b.rect, values=None, ranges=None)
+    if b.entries == 0:
+        return dict(zip(("rgb", "depth", "alpha"), _blank(views, h, w, dev)))
     walked = stats.get("walked") if stats is not None else None
-    rgb, out_depth, alpha = ops.gauss_blend(pts, uv, conic, depth, values, ranges, (h, w), walked=walked)
+    rgb, out_depth, alpha = ops.gauss_blend(pts, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w), walked=walked)
     if stats is not None:
-        stats.update(longest_tile=int((ranges[:, 1] - ranges[:, 0]).max().item()), values=values, ranges=ranges)
+        stats.update(longest_tile=int((b.ranges[:, 1] - b.ranges[:, 0]).max().item()), values=b.values, ranges=b.ranges)
     return {"rgb": rgb, "depth": out_depth, "alpha": alpha}
 
 
@@ -211,28 +227,15 @@ class _Render(torch.autograd.Function):
     def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density=None):
         h, w = hw
         ctx.density = density
-        views, dev = mats.shape[0], xyz.device
-        tx, ty = ops.gauss_tiles(h, w)
         pts = _pack_xyz(xyz)
         cov, opacity, colour = cov.detach().contiguous(), opacity.detach().contiguous(), colour.detach().contiguous()
-        uv, conic, depth, rect, count = ops.gauss_project(pts, cov, opacity, mats, cams, (h, w), ids=ids, znear=znear, zfar=zfar)
-        ends = torch.cumsum(count.reshape(-1), 0, dtype=torch.int64)
-        offsets = (ends - count.reshape(-1)).reshape(count.shape)
-        entries = int(ends[-1].item())
-        if entries >= 2 ** 31 or entries > int(max_entries):
-            raise hip.MudgError(f"render_differentiable: {entries} (tile, Gaussian) entries exceed max_entries = {int(max_entries)} (and must "
-                                "stay below 2^31): thin the cloud, shrink the scale or draw fewer views per call")
-        ctx.meta = (cams, (h, w), ids, znear, zfar, entries)
-        if entries == 0:
+        b = _bin("render_differentiable", pts, cov, opacity, mats, cams, (h, w), ids, znear, zfar, max_entries)
+        ctx.meta = (cams, (h, w), ids, znear, zfar, b.entries)
+        if b.entries == 0:
             ctx.save_for_backward(xyz)
-            return (torch.zeros((views, 3, h, w), dtype=torch.float32, device=dev), torch.zeros((views, h, w), dtype=torch.float32, device=dev),
-                    torch.zeros((views, h, w), dtype=torch.float32, device=dev))
-        keys, values = ops.gauss_keys(depth, rect, count, offsets, entries, (h, w))
-        keys, order = torch.sort(keys, stable=True)
-        values = values[order]
-        ranges = ops.gauss_ranges(keys, views * tx * ty)
-        rgb, out_depth, alpha, state = ops.gauss_blend_train(colour, uv, conic, depth, values, ranges, (h, w))
-        ctx.save_for_backward(pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state)
+            return _blank(mats.shape[0], h, w, xyz.device)
+        rgb, out_depth, alpha, state = ops.gauss_blend_train(colour, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w))
+        ctx.save_for_backward(pts, colour, cov, mats, b.uv, b.conic, b.depth, b.values, b.order, b.offsets, b.count, b.ranges, state)
         return rgb, out_depth, alpha
 
     @staticmethod

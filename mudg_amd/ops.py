@@ -894,6 +894,7 @@ def metric_cloud(d2, t2, r2):
 
 # ------------------------------------------------------------------------------------------------ clouds as 3D Gaussians
 GAUSS_TILE = 16
+GAUSS_SUMS = 10                  # a partial: dcolour0..2, dzc, dopacity, dA, dB, dC, du, dv
 
 
 def gauss_tiles(h, w):
@@ -901,22 +902,63 @@ def gauss_tiles(h, w):
     return (int(w) + GAUSS_TILE - 1) // GAUSS_TILE, (int(h) + GAUSS_TILE - 1) // GAUSS_TILE
 
 
+def _gauss_cloud(name, points, cov, mats, ids):
+    """The operands gauss_project and its backward share -> (n, V, nmat)."""
+    _splat_tensor(f"{name}: points", points, torch.int32)
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
+        raise hip.MudgError(f"{name}: expected packed points (n > 0, 4), got {tuple(points.shape)}")
+    n = points.shape[0]
+    _splat_tensor(f"{name}: cov", cov, torch.float32, (n, 6))
+    _splat_tensor(f"{name}: mats", mats, torch.float32)
+    if mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0 or mats.shape[1] == 0:
+        raise hip.MudgError(f"{name}: expected matrices (V, nmat, 12), got {tuple(mats.shape)}")
+    if ids is not None:
+        _splat_tensor(f"{name}: ids", ids, torch.int32, (n,))
+    return (n, *mats.shape[:2])
+
+
+# a blend's first operand: its name, its name in the shape error, its dtype, its row width
+_GAUSS_POINTS = ("points", "packed points", torch.int32, 4)
+_GAUSS_COLOURS = ("colour", "colours", torch.float32, 3)
+
+
+def _gauss_entries(name, first, kind, uv, conic, depth, values_sorted, ranges, hw):
+    """The operands the three blends share, `first` checked as `kind` (_GAUSS_POINTS or _GAUSS_COLOURS) -> (V, n, h, w, V NT)."""
+    label, plural, dtype, width = kind
+    _splat_tensor(f"{name}: {label}", first, dtype)
+    _splat_tensor(f"{name}: depth", depth, torch.float32)
+    if first.dim() != 2 or first.shape[1] != width or depth.dim() != 2 or depth.shape[1] != first.shape[0]:
+        raise hip.MudgError(f"{name}: {plural} {tuple(first.shape)} with depths {tuple(depth.shape)}")
+    v, n = depth.shape
+    h, w = (int(s) for s in hw)
+    tx, ty = gauss_tiles(h, w)
+    _splat_tensor(f"{name}: uv", uv, torch.float32, (v, n, 2))
+    _splat_tensor(f"{name}: conic", conic, torch.float32, (v, n, 4))
+    _splat_tensor(f"{name}: values", values_sorted, torch.int32)
+    _splat_tensor(f"{name}: ranges", ranges, torch.int32, (v * tx * ty, 2))
+    if values_sorted.dim() != 1 or values_sorted.numel() == 0:
+        raise hip.MudgError(f"{name}: expected (E > 0,) sorted values, got {tuple(values_sorted.shape)}")
+    return v, n, h, w, v * tx * ty
+
+
+def _gauss_images(v, h, w, device):
+    """rgb (V, 3, H, W), depth (V, H, W) and alpha (V, H, W) for a blend to fill."""
+    return (torch.empty((v, 3, h, w), dtype=torch.float32, device=device), torch.empty((v, h, w), dtype=torch.float32, device=device),
+            torch.empty((v, h, w), dtype=torch.float32, device=device))
+
+
+def _gauss_partial(name, partial):
+    _splat_tensor(f"{name}: partial", partial, torch.float32)
+    if partial.dim() != 2 or partial.shape[1] != GAUSS_SUMS or partial.shape[0] == 0:
+        raise hip.MudgError(f"{name}: expected partials (E > 0, {GAUSS_SUMS}), got {tuple(partial.shape)}")
+
+
 def gauss_project(points, cov, opacity, mats, intr, hw, *, ids=None, znear=0.2, zfar=200.0):
     """Project packed points (n, 4) int32 with covariances (n, 6) and opacities (n,) fp32 through mats (V, nmat, 12) fp32 and intr =
     (fx, fy, cx, cy) into V views of hw.  Returns uv (V, n, 2), conic (V, n, 4) = (A, B, C, opacity), depth (V, n) fp32,
     rect (V, n, 4) = (x0, x1, y0, y1) and count (V, n) int32, all zero where a Gaussian is dropped."""
-    _splat_tensor("gauss_project: points", points, torch.int32)
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
-        raise hip.MudgError(f"gauss_project: expected packed points (n > 0, 4), got {tuple(points.shape)}")
-    n = points.shape[0]
-    _splat_tensor("gauss_project: cov", cov, torch.float32, (n, 6))
+    n, v, nmat = _gauss_cloud("gauss_project", points, cov, mats, ids)
     _splat_tensor("gauss_project: opacity", opacity, torch.float32, (n,))
-    _splat_tensor("gauss_project: mats", mats, torch.float32)
-    if mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0 or mats.shape[1] == 0:
-        raise hip.MudgError(f"gauss_project: expected matrices (V, nmat, 12), got {tuple(mats.shape)}")
-    if ids is not None:
-        _splat_tensor("gauss_project: ids", ids, torch.int32, (n,))
-    v, nmat = mats.shape[:2]
     h, w = (int(s) for s in hw)
     fx, fy, cx, cy = (float(s) for s in intr)
     dev = points.device
@@ -964,60 +1006,22 @@ def gauss_ranges(keys_sorted, tiles):
 def gauss_blend(points, uv, conic, depth, values_sorted, ranges, hw, *, walked=None):
     """Front-to-back alpha blending of every tile's entries: rgb (V, 3, H, W) in [0, 1] on black, depth (V, H, W) alpha-weighted and
     alpha (V, H, W), fp32.  walked: a (V NT,) int32 tensor that receives the entries each workgroup staged (tools)."""
-    _splat_tensor("gauss_blend: points", points, torch.int32)
-    _splat_tensor("gauss_blend: depth", depth, torch.float32)
-    if points.dim() != 2 or points.shape[1] != 4 or depth.dim() != 2 or depth.shape[1] != points.shape[0]:
-        raise hip.MudgError(f"gauss_blend: packed points {tuple(points.shape)} with depths {tuple(depth.shape)}")
-    v, n = depth.shape
-    h, w = (int(s) for s in hw)
-    tx, ty = gauss_tiles(h, w)
-    _splat_tensor("gauss_blend: uv", uv, torch.float32, (v, n, 2))
-    _splat_tensor("gauss_blend: conic", conic, torch.float32, (v, n, 4))
-    _splat_tensor("gauss_blend: values", values_sorted, torch.int32)
-    _splat_tensor("gauss_blend: ranges", ranges, torch.int32, (v * tx * ty, 2))
-    if values_sorted.dim() != 1 or values_sorted.numel() == 0:
-        raise hip.MudgError(f"gauss_blend: expected (E > 0,) sorted values, got {tuple(values_sorted.shape)}")
+    v, n, h, w, tiles = _gauss_entries("gauss_blend", points, _GAUSS_POINTS, uv, conic, depth, values_sorted, ranges, hw)
     if walked is not None:
-        _splat_tensor("gauss_blend: walked", walked, torch.int32, (v * tx * ty,))
-    dev = points.device
-    rgb = torch.empty((v, 3, h, w), dtype=torch.float32, device=dev)
-    out_depth = torch.empty((v, h, w), dtype=torch.float32, device=dev)
-    alpha = torch.empty((v, h, w), dtype=torch.float32, device=dev)
+        _splat_tensor("gauss_blend: walked", walked, torch.int32, (tiles,))
+    rgb, out_depth, alpha = _gauss_images(v, h, w, points.device)
     hip.check(hip.lib().mudg_gauss_blend(points.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(), values_sorted.data_ptr(),
                                          ranges.data_ptr(), n, values_sorted.numel(), v, h, w, rgb.data_ptr(), out_depth.data_ptr(),
                                          alpha.data_ptr(), _ptr(walked), _stream()), "mudg_gauss_blend")
     return rgb, out_depth, alpha
 
 
-GAUSS_SUMS = 10                  # a partial: dcolour0..2, dzc, dopacity, dA, dB, dC, du, dv
-
-
-def _gauss_entries(name, colour, uv, conic, depth, values_sorted, ranges, hw):
-    _splat_tensor(f"{name}: colour", colour, torch.float32)
-    _splat_tensor(f"{name}: depth", depth, torch.float32)
-    if colour.dim() != 2 or colour.shape[1] != 3 or depth.dim() != 2 or depth.shape[1] != colour.shape[0]:
-        raise hip.MudgError(f"{name}: colours {tuple(colour.shape)} with depths {tuple(depth.shape)}")
-    v, n = depth.shape
-    h, w = (int(s) for s in hw)
-    tx, ty = gauss_tiles(h, w)
-    _splat_tensor(f"{name}: uv", uv, torch.float32, (v, n, 2))
-    _splat_tensor(f"{name}: conic", conic, torch.float32, (v, n, 4))
-    _splat_tensor(f"{name}: values", values_sorted, torch.int32)
-    _splat_tensor(f"{name}: ranges", ranges, torch.int32, (v * tx * ty, 2))
-    if values_sorted.dim() != 1 or values_sorted.numel() == 0:
-        raise hip.MudgError(f"{name}: expected (E > 0,) sorted values, got {tuple(values_sorted.shape)}")
-    return v, n, h, w
-
-
 def gauss_blend_train(colour, uv, conic, depth, values_sorted, ranges, hw):
     """gauss_blend with the colour an fp32 (n, 3) tensor in byte units.  Returns rgb, depth, alpha as gauss_blend does and
     state (V, 5, H, W) fp32 = the accumulators (C0, C1, C2, D, T) of every pixel, which the backward needs unrounded."""
-    v, n, h, w = _gauss_entries("gauss_blend_train", colour, uv, conic, depth, values_sorted, ranges, hw)
-    dev = colour.device
-    rgb = torch.empty((v, 3, h, w), dtype=torch.float32, device=dev)
-    out_depth = torch.empty((v, h, w), dtype=torch.float32, device=dev)
-    alpha = torch.empty((v, h, w), dtype=torch.float32, device=dev)
-    state = torch.empty((v, 5, h, w), dtype=torch.float32, device=dev)
+    v, n, h, w, _ = _gauss_entries("gauss_blend_train", colour, _GAUSS_COLOURS, uv, conic, depth, values_sorted, ranges, hw)
+    rgb, out_depth, alpha = _gauss_images(v, h, w, colour.device)
+    state = torch.empty((v, 5, h, w), dtype=torch.float32, device=colour.device)
     hip.check(hip.lib().mudg_gauss_blend_train(colour.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(), values_sorted.data_ptr(),
                                                ranges.data_ptr(), n, values_sorted.numel(), v, h, w, rgb.data_ptr(), out_depth.data_ptr(),
                                                alpha.data_ptr(), state.data_ptr(), _stream()), "mudg_gauss_blend_train")
@@ -1027,7 +1031,7 @@ def gauss_blend_train(colour, uv, conic, depth, values_sorted, ranges, hw):
 def gauss_blend_bwd(colour, uv, conic, depth, values_sorted, order, ranges, hw, state, d_rgb, d_depth, d_alpha):
     """The blend's backward: partial (E, 10) fp32, one row per entry at its unsorted position order[e], the sums over the tile's pixels of
     (dcolour0..2, dzc, dopacity, dA, dB, dC, du, dv) in one fixed order; zero for entries no workgroup reached."""
-    v, n, h, w = _gauss_entries("gauss_blend_bwd", colour, uv, conic, depth, values_sorted, ranges, hw)
+    v, n, h, w, _ = _gauss_entries("gauss_blend_bwd", colour, _GAUSS_COLOURS, uv, conic, depth, values_sorted, ranges, hw)
     e = values_sorted.numel()
     _splat_tensor("gauss_blend_bwd: order", order, torch.int64, (e,))
     _splat_tensor("gauss_blend_bwd: state", state, torch.float32, (v, 5, h, w))
@@ -1045,22 +1049,10 @@ def gauss_project_bwd(points, cov, mats, intr, hw, count, offsets, partial, *, i
     """The projection's backward: every Gaussian's partials gathered per view in ascending order and taken through the chain rule of
     gauss_project, the views added in order.  Returns d_xyz (n, 3), d_cov (n, 6) (off-diagonal entries: both symmetric halves),
     d_opacity (n,) and d_colour (n, 3), fp32."""
-    _splat_tensor("gauss_project_bwd: points", points, torch.int32)
-    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
-        raise hip.MudgError(f"gauss_project_bwd: expected packed points (n > 0, 4), got {tuple(points.shape)}")
-    n = points.shape[0]
-    _splat_tensor("gauss_project_bwd: cov", cov, torch.float32, (n, 6))
-    _splat_tensor("gauss_project_bwd: mats", mats, torch.float32)
-    if mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0 or mats.shape[1] == 0:
-        raise hip.MudgError(f"gauss_project_bwd: expected matrices (V, nmat, 12), got {tuple(mats.shape)}")
-    if ids is not None:
-        _splat_tensor("gauss_project_bwd: ids", ids, torch.int32, (n,))
-    v, nmat = mats.shape[:2]
+    n, v, nmat = _gauss_cloud("gauss_project_bwd", points, cov, mats, ids)
     _splat_tensor("gauss_project_bwd: count", count, torch.int32, (v, n))
     _splat_tensor("gauss_project_bwd: offsets", offsets, torch.int64, (v, n))
-    _splat_tensor("gauss_project_bwd: partial", partial, torch.float32)
-    if partial.dim() != 2 or partial.shape[1] != GAUSS_SUMS or partial.shape[0] == 0:
-        raise hip.MudgError(f"gauss_project_bwd: expected partials (E > 0, {GAUSS_SUMS}), got {tuple(partial.shape)}")
+    _gauss_partial("gauss_project_bwd", partial)
     h, w = (int(s) for s in hw)
     fx, fy, cx, cy = (float(s) for s in intr)
     dev = points.device
@@ -1087,9 +1079,7 @@ def gauss_density_accumulate(partial, count, offsets, hw, grad_sum, seen):
         raise hip.MudgError(f"gauss_density_accumulate: expected counts (V > 0, n > 0), got {tuple(count.shape)}")
     v, n = count.shape
     _splat_tensor("gauss_density_accumulate: offsets", offsets, torch.int64, (v, n))
-    _splat_tensor("gauss_density_accumulate: partial", partial, torch.float32)
-    if partial.dim() != 2 or partial.shape[1] != GAUSS_SUMS or partial.shape[0] == 0:
-        raise hip.MudgError(f"gauss_density_accumulate: expected partials (E > 0, {GAUSS_SUMS}), got {tuple(partial.shape)}")
+    _gauss_partial("gauss_density_accumulate", partial)
     _splat_tensor("gauss_density_accumulate: grad_sum", grad_sum, torch.float32, (n,))
     _splat_tensor("gauss_density_accumulate: seen", seen, torch.int32, (n,))
     h, w = (int(s) for s in hw)

@@ -187,6 +187,9 @@ def test_tensors_off_the_gpu_are_refused():
     with pytest.raises(hip.MudgError, match="GaussianModel"):
         gaussians.fit(pc, f(1, 3, 16, 16), f(1, 1, 12), (1.0, 1.0, 0.0, 0.0), (16, 16), iters=1)
     assert callable(virtual_pose_render.fit_cloud_views) and ops.GAUSS_SUMS == gb.SUMS
+    shared = open(os.path.join(ROOT, "mudg_amd", "csrc", "gauss_shared.h")).read()
+    assert [int(v) for v in re.findall(r"constexpr int GAUSS_SUMS = (\d+);", shared)] == [ops.GAUSS_SUMS]
+    assert [int(v) for v in re.findall(r"constexpr int TILE = (\d+);", shared)] == [ops.GAUSS_TILE]
 
 
 def test_the_product_does_not_import_the_cpu_definition():
