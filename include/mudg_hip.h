@@ -319,6 +319,7 @@ int mudg_cond_dropout(const float* r, float p, float p2, float p3, const float* 
 /* ------------------------------------------------------------------ post-processing of decoded frames
  * (virtual_render/eval_tools.py: byte / integer work, results bit-equal to the reference's)
  * frames_to_u8:     out[b][t][p][c] = (uint8) trunc((clamp(v[b][c][t][p], -1, 1) + 1) / 2 * 255)      eval_tools.py:22-27
+ *                   clamp(x, -1, 1) = fminf(fmaxf(x, -1), 1): what is not a number becomes -1, byte 0; + 1, / 2, * 255 each in fp32
  * depth_from_u8:    depth[i] = ((r + g + b) / 3) / 255 over `pixels` (.., 3)-interleaved uint8 pixels   eval_tools.py:71
  * semantic_nearest: planar (3, hw) uint8 image -> label of the nearest of the 19 palette colours (Euclidean distance,
  *                   first minimum wins) and the image recoloured with the palette                       eval_tools.py:309-347 */
@@ -326,8 +327,9 @@ int mudg_frames_to_u8(const float* video, uint8_t* out, int B, int C, int T, int
 int mudg_depth_from_u8(const uint8_t* frames, float* depth, int64_t pixels, void* stream);
 /* The frame sheet of a logged entry (utils/save_video.py:62-136): video (N, C, T, H, W) fp32, C = 1 or 3 -> out (T, N H, W, 3) uint8,
  * the samples stacked along the height (make_grid(nrow=1, padding=0)), one channel repeated to three; clamp != 0: clamp to [-1, 1]
- * first (prepare_to_log); rescale != 0: (x + 1) / 2; then * 255 and truncation, in the reference's fp32 order: byte-equal.  An
- * image entry (N, C, H, W) -> (N H, W, 3) is the call with T = 1. */
+ * first (prepare_to_log; frames_to_u8's clamp: NaN becomes -1); rescale != 0: (x + 1) / 2; then * 255 and truncation toward zero, in
+ * the reference's fp32 order: byte-equal.  The byte is defined where -1 < the product < 256 (with the clamp and the rescale: for every
+ * value).  An image entry (N, C, H, W) -> (N H, W, 3) is the call with T = 1. */
 int mudg_log_sheet(const float* video, uint8_t* out, int N, int C, int T, int H, int W, int clamp, int rescale, void* stream);
 int mudg_semantic_nearest(const uint8_t* img, uint8_t* vis, int64_t* labels, int64_t hw, void* stream);
 
@@ -431,7 +433,8 @@ int mudg_metric_confusion(const int64_t* pred, const int64_t* gt, int frames, in
  * the rules are this project's, written out in DESIGN §16, and bit-equal to tests/frames_reference.py.)
  * A table has one 16-byte entry per output sample of an axis, made on the host: int32 s0, s1 (the two source indices; nearest reads s0
  * only) and the coefficients of s0 and s1 — int32 that sum to 2048 for the 8-bit rule, fp32 bit patterns w0, w1 for the fp32 rule.
- * xtab has W entries, ytab H.  T, H <= 65535; H0 W0, H W <= 2^28.
+ * xtab has W entries, ytab H.  T, H <= 65535; H0 W0, H W <= 2^28.  A source index outside its axis is clamped to [0, n - 1] before it is
+ * used (the coefficients stay): no table sends a load out of the source.
  * resize_u8:  src (T, H0, W0, C) uint8 -> dst (T, H, W, C), C = 1 or 3.  Linear: R = S[x0] a0 + S[x1] a1 per source row in int32,
  *   out = (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2                    waymo_data.py:80, 92 (INTER_LINEAR)
  *   nearest: out = S[y.s0][x.s0]                                                          waymo_data.py:86 (INTER_NEAREST)
@@ -496,7 +499,9 @@ int mudg_metric_normals(const uint8_t* pred_u8, const float* gt, const uint8_t* 
  *   near(q) iff q is in the image, its occluder key is not all ones and its depth < fmul(zc, rel_keep), rel_keep = fp32(1 - rel_tol);
  *   the point is hidden iff for one of the directions (0,1), (1,0), (1,1), (1,-1) some pixel home + k d and some pixel home - k' d,
  *   k, k' in 1 .. reach (<= 16), are near.  A hidden point writes nothing; every other one takes the unsigned 64-bit minimum of
- *   (bits(zc) << 32 | index_base + candidate number) in keys[H][W] over its cover.
+ *   (bits(zc) << 32 | index_base + candidate number) in keys[H][W] over its cover.  A candidate's number is its place among the
+ *   runs in the order given (a point that two runs name is two candidates).  index_base >= 0 and index_base + candidates <= 2^32:
+ *   every index fits the key's low word (no key of a depth in (znear, zfar) is all ones).
  * lidar_depth_resolve: depth = the key's high word as fp32, 0 where the key is all ones; keys, and occluder_keys unless NULL, are
  *   all ones afterwards.
  * depth_complete: depth (frames, H, W) fp32 metres -> out, the same shape.  M = max_depth; a value is empty iff it is < 0.1f.
@@ -509,8 +514,9 @@ int mudg_metric_normals(const uint8_t* pred_u8, const float* gt, const uint8_t* 
  *      one fp64 division rounded to fp32                   8  out = M - x where filled, else 0
  *   9  labels (frames, H, W) int64 or NULL: out = M where the label is sky_label
  *   source (frames, H, W) bytes or NULL: 4 sky, else 0 where out is empty, else 1 filled after step 1, 2 after step 4, 3 later.
- *   scratch: depth_complete_scratch's bytes (-1: bad shape), 16-byte aligned.  1 .. 65535 frames and rows, H W <= 2^24,
- *   0.1 < max_depth <= 65536. */
+ *   scratch: depth_complete_scratch's bytes (-1: bad shape), 16-byte aligned: 2 round16(4 px) + round16(px), px = frames H W, round16
+ *   to the next multiple of 16 (two fp32 maps and a byte map).  What it holds before the call does not matter and nothing outside
+ *   those bytes is touched.  depth and out need fp32 alignment only.  1 .. 65535 frames and rows, H W <= 2^24, 0.1 < max_depth <= 65536. */
 int mudg_lidar_splat_visible(const void* points, const int32_t* ids, const int64_t* segments, int nseg, const float* mats, int nmat,
                              const uint64_t* occluder_keys, uint64_t* keys, int H, int W, float fx, float fy, float cx, float cy,
                              float znear, float zfar, float point_size, int reach, float rel_keep, int64_t index_base, void* stream);

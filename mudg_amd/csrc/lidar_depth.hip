@@ -319,7 +319,7 @@ extern "C" int mudg_lidar_splat_visible(const void* points, const int32_t* ids, 
         seg.start[s + 1] = seg.start[s] + segments[2 * s + 1];
     }
     const int64_t n = seg.total = seg.start[nseg];
-    MUDG_REQUIRE(index_base >= 0 && index_base + n <= 0xffffffffLL, "mudg_lidar_splat_visible: %lld candidates from %lld (the key holds a 32-bit index)", (long long)n, (long long)index_base);
+    MUDG_REQUIRE(index_base >= 0 && index_base + n <= 0x100000000LL, "mudg_lidar_splat_visible: %lld candidates from %lld (the key holds a 32-bit index)", (long long)n, (long long)index_base);
     const SplatCam cam = {fx, fy, cx, cy, znear, zfar, point_size * 0.5f};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
