@@ -649,6 +649,37 @@ int mudg_gauss_project_bwd(const void* points, const float* cov, const int32_t* 
                            const int64_t* offsets, const float* partial, int64_t E, float* d_xyz, float* d_cov, float* d_opacity,
                            float* d_colour, void* stream);
 
+/* ------------------------------------------------------------------ view-dependent colour (csrc/gaussians_sh.hip)
+ * Real spherical harmonics of degrees 1 .. L (L = degree = 1, 2 or 3; K = (L + 1)^2) on top of colour (n, 3), the direction-independent
+ * term in byte units with the degree-0 constant folded in.  sh (n, K - 1, 3) fp32, row-major, 16-byte aligned, in byte units; order, signs
+ * and constants are the 3DGS code's, the constants rounded once to fp32.  points, ids, mats, count: what mudg_gauss_project takes and
+ * writes.  active (0 .. L) cuts the sum at Ka = (active + 1)^2.  Single rounded fp32 operations in the order DESIGN §27 writes them.
+ * sh_colour, a lane per (view, Gaussian): where count[v][g] <= 0 the colour is +0 and nothing of the Gaussian is read.  Otherwise, with
+ *   m = mats[v][id], c_j = -((m[j] m[3] + m[4 + j] m[7]) + m[8 + j] m[11]), w = p - c, len = sqrt((wx wx + wy wy) + wz wz), d = w / len:
+ *   a = colour[g]; a += B_k(d) sh[g][k - 1] for k = 1 .. Ka - 1 in order; colours[v][g] = a < 0 ? +0 : a.  colours is (V, n, 3).  V <= 65535.
+ * sh_bwd, a lane per Gaussian, views in order; partial (E, 10), count and offsets as mudg_gauss_project_bwd reads them, with its guards.
+ *   Per counted view: g = columns 0 .. 2 of the partials added in ascending order from +0; the forward's d, B and a again; ge = a < 0 ?
+ *   +0 : g per channel; d_colour += ge; d_sh[k - 1] += B_k ge for k < Ka; s_k = (ge0 sh0 + ge1 sh1) + ge2 sh2 for k < Ka, +0 above;
+ *   gd = sum_k s_k dB_k/dd as DESIGN §27 orders its terms; dot = (dx gdx + dy gdy) + dz gdz; d_xyz_dir += (gd - d dot) / len.  d_colour
+ *   (n, 3), d_sh (n, K - 1, 3) (16-byte aligned; +0 at and above Ka) and d_xyz_dir (n, 3), in the Gaussian's own frame, are written in
+ *   full with plain stores.
+ * blend_views, blend_train_views, blend_bwd_views: mudg_gauss_blend_train (the first without state) and mudg_gauss_blend_bwd with
+ *   colours (V, n, 3), an entry of view v and Gaussian g taking colours[v][g]; everything else, refusals included, is theirs. */
+int mudg_gauss_sh_colour(const void* points, const int32_t* ids, int64_t n, const float* mats, int V, int nmat, const int32_t* count,
+                         const float* colour, const float* sh, int degree, int active, float* colours, void* stream);
+int mudg_gauss_sh_bwd(const void* points, const int32_t* ids, int64_t n, const float* mats, int V, int nmat, const int32_t* count,
+                      const int64_t* offsets, const float* partial, int64_t E, const float* colour, const float* sh, int degree, int active,
+                      float* d_colour, float* d_sh, float* d_xyz_dir, void* stream);
+int mudg_gauss_blend_views(const float* colours, const float* uv, const float* conic, const float* depth, const int32_t* values_sorted,
+                           const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb, float* depth_out, float* alpha,
+                           void* stream);
+int mudg_gauss_blend_train_views(const float* colours, const float* uv, const float* conic, const float* depth, const int32_t* values_sorted,
+                                 const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb, float* depth_out, float* alpha,
+                                 float* state, void* stream);
+int mudg_gauss_blend_bwd_views(const float* colours, const float* uv, const float* conic, const float* depth, const int32_t* values_sorted,
+                               const int64_t* order, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, const float* state,
+                               const float* d_rgb, const float* d_depth, const float* d_alpha, float* partial, void* stream);
+
 /* ------------------------------------------------------------------ density control for the fit (csrc/gaussians_density.hip)
  * Which Gaussians a fit clones, splits and prunes, and the pass that rewrites the parameters.  fp32, single rounded operations in the
  * order written, a lane per Gaussian, plain stores, no atomics, no generator state, no transcendental.

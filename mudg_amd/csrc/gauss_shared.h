@@ -1,5 +1,5 @@
 // gauss_shared.h — every step that more than one kernel of the Gaussian splat renderer computes (gaussians.hip, DESIGN.md §23;
-// gaussians_bwd.hip, §24; gaussians_density.hip, §25; gaussians_loss.hip, §26), written once: the constants of the rule, the single
+// gaussians_bwd.hip, §24; gaussians_density.hip, §25; gaussians_loss.hip, §26; gaussians_sh.hip, §27), written once: the constants of the rule, the single
 // rounded operations, the polynomial exponential, a Gaussian's load and its projection into a view, a tile's prologue, the staging of an
 // entry, the blend step and the forward blend loop, the walk over a Gaussian's partials, the fixed-order tile reduction, and the checks
 // the entry points share.  One copy, so that the backward recomputes the forward's values bit for bit.

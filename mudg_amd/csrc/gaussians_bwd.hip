@@ -8,6 +8,9 @@
 //                      The result is stored at the entry's unsorted position; no atomics on global memory
 //   gauss_project_bwd  a lane owns a Gaussian: per view it sums the Gaussian's partials in ascending order and applies the chain rule
 //                      through the projection of §23; the views are added in view order
+// The two blends also serve DESIGN.md §27's entry points (`_views`): there the colour tensor is (V, n, 3) and per_view, the floats from
+// one view's colours to the next, is 3 n; for one colour per Gaussian it is 0.  The inference blend of §27 is gauss_blend_train without
+// a state pointer.
 // Everything is fp32, each operation a single rounded one in the order DESIGN.md §24 writes it, so the gradients are bit-equal to the
 // numpy definition in tests/gaussians_bwd_reference.py and a repeat run gives the same bits.  No MFMA operand is touched.
 #include "gauss_shared.h"
@@ -15,7 +18,7 @@
 namespace {
 
 // An entry in LDS is 48 bytes: stage_batch's two words and (colour0, colour1, colour2, -).
-__global__ __launch_bounds__(256) void gauss_blend_train_kernel(const float* __restrict__ colour, const f32x2* __restrict__ uv,
+__global__ __launch_bounds__(256) void gauss_blend_train_kernel(const float* __restrict__ colour, int64_t per_view, const f32x2* __restrict__ uv,
                                                                  const f32x4* __restrict__ conic, const float* __restrict__ depth,
                                                                  const int32_t* __restrict__ values, const int32_t* __restrict__ ranges,
                                                                  int64_t n, int64_t E, int TX, int NT, int H, int W, float* __restrict__ rgb,
@@ -26,9 +29,10 @@ __global__ __launch_bounds__(256) void gauss_blend_train_kernel(const float* __r
     __shared__ f32x4 tint[BATCH];
     const GaussTile tile = gauss_tile(blockIdx.x, ranges, E, TX, NT, H, W);
     GaussPixel acc;
-    blend_forward(uv, conic, depth, values, n, tile, FloatColour{colour, tint}, geom, look, acc);
+    blend_forward(uv, conic, depth, values, n, tile, FloatColour{colour + tile.view * per_view, tint}, geom, look, acc);
     if (tile.inside) {
         store_images(tile, H, W, acc, rgb, depth_out, alpha_out);
+        if (!state) return;                                                 // inference: the images only
         const int64_t plane = (int64_t)H * W;
         float* st = state + tile.view * 5 * plane + (int64_t)tile.j * W + tile.i;
         st[0] = acc.c0;
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(256) void gauss_blend_train_kernel(const float* __r
 
 // order[e]: the unsorted position of sorted entry e (the forward sort's permutation); a value outside [0, E) writes nothing.  Every entry
 // of a batch that was staged gets its partial stored, +0.0 where no pixel blends it; the batches never staged keep the entry point's zeros.
-__global__ __launch_bounds__(256) void gauss_blend_bwd_kernel(const float* __restrict__ colour, const f32x2* __restrict__ uv,
+__global__ __launch_bounds__(256) void gauss_blend_bwd_kernel(const float* __restrict__ colour, int64_t per_view, const f32x2* __restrict__ uv,
                                                                const f32x4* __restrict__ conic, const float* __restrict__ depth,
                                                                const int32_t* __restrict__ values, const int64_t* __restrict__ order,
                                                                const int32_t* __restrict__ ranges, int64_t n, int64_t E, int TX, int NT, int H,
@@ -53,7 +57,7 @@ __global__ __launch_bounds__(256) void gauss_blend_bwd_kernel(const float* __res
     __shared__ f32x4 tint[BATCH];
     __shared__ float wsum[4 * BATCH * GAUSS_SUMS];                          // the four waves' sums of every entry of the batch
     const GaussTile tile = gauss_tile(blockIdx.x, ranges, E, TX, NT, H, W);
-    const FloatColour tints = {colour, tint};
+    const FloatColour tints = {colour + tile.view * per_view, tint};
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float gC0 = 0.0f, gC1 = 0.0f, gC2 = 0.0f, gD = 0.0f, gAT = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sD = 0.0f;
     if (tile.inside) {
@@ -211,36 +215,75 @@ __global__ __launch_bounds__(256) void gauss_project_bwd_kernel(const u32x4* __r
 
 }  // namespace
 
+// The two float-colour blends behind their entry points: `name` speaks in the refusals, per_view is 0 for one colour per Gaussian and 3 n
+// for one per (view, Gaussian) (§27), state may be NULL only for the inference blend.
+static int blend_train(const char* name, const float* colour, int64_t per_view, const float* uv, const float* conic, const float* depth,
+                       const int32_t* values_sorted, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb,
+                       float* depth_out, float* alpha, float* state, bool with_state, void* stream) {
+    MUDG_REQUIRE(colour && uv && conic && depth && values_sorted && ranges && rgb && depth_out && alpha && (state || !with_state),
+                 "%s: null argument", name);
+    MUDG_REQUIRE(aligned16(conic) && aligned8(uv), "%s: unaligned projections", name);
+    if (const int e = check_views(name, n, V, H, W)) return e;
+    MUDG_REQUIRE(entries_ok(E), "%s: %lld entries (1 .. 2^31 - 1)", name, (long long)E);
+    const GaussGrid grid(H, W);
+    hipLaunchKernelGGL(gauss_blend_train_kernel, dim3((unsigned)((int64_t)V * grid.NT)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), colour,
+                       per_view, reinterpret_cast<const f32x2*>(uv), reinterpret_cast<const f32x4*>(conic), depth, values_sorted, ranges, n, E,
+                       grid.TX, grid.NT, H, W, rgb, depth_out, alpha, with_state ? state : nullptr);
+    return mudg_check_launch(name);
+}
+
+static int blend_bwd(const char* name, const float* colour, int64_t per_view, const float* uv, const float* conic, const float* depth,
+                     const int32_t* values_sorted, const int64_t* order, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W,
+                     const float* state, const float* d_rgb, const float* d_depth, const float* d_alpha, float* partial, void* stream) {
+    MUDG_REQUIRE(colour && uv && conic && depth && values_sorted && order && ranges && state && d_rgb && d_depth && d_alpha && partial,
+                 "%s: null argument", name);
+    MUDG_REQUIRE(aligned16(conic) && aligned8(uv) && aligned8(order), "%s: unaligned projections or order", name);
+    if (const int e = check_views(name, n, V, H, W)) return e;
+    MUDG_REQUIRE(entries_ok(E), "%s: %lld entries (1 .. 2^31 - 1)", name, (long long)E);
+    const GaussGrid grid(H, W);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(partial, 0, (size_t)E * GAUSS_SUMS * sizeof(float), s) != hipSuccess) return mudg_check_launch(name);
+    hipLaunchKernelGGL(gauss_blend_bwd_kernel, dim3((unsigned)((int64_t)V * grid.NT)), dim3(256), 0, s, colour, per_view,
+                       reinterpret_cast<const f32x2*>(uv), reinterpret_cast<const f32x4*>(conic), depth, values_sorted, order, ranges, n, E, grid.TX,
+                       grid.NT, H, W, state, d_rgb, d_depth, d_alpha, partial);
+    return mudg_check_launch(name);
+}
+
 extern "C" int mudg_gauss_blend_train(const float* colour, const float* uv, const float* conic, const float* depth,
                                       const int32_t* values_sorted, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb,
                                       float* depth_out, float* alpha, float* state, void* stream) {
-    MUDG_REQUIRE(colour && uv && conic && depth && values_sorted && ranges && rgb && depth_out && alpha && state,
-                 "mudg_gauss_blend_train: null argument");
-    MUDG_REQUIRE(aligned16(conic) && aligned8(uv), "mudg_gauss_blend_train: unaligned projections");
-    if (const int e = check_views("mudg_gauss_blend_train", n, V, H, W)) return e;
-    MUDG_REQUIRE(entries_ok(E), "mudg_gauss_blend_train: %lld entries (1 .. 2^31 - 1)", (long long)E);
-    const GaussGrid grid(H, W);
-    hipLaunchKernelGGL(gauss_blend_train_kernel, dim3((unsigned)((int64_t)V * grid.NT)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), colour,
-                       reinterpret_cast<const f32x2*>(uv), reinterpret_cast<const f32x4*>(conic), depth, values_sorted, ranges, n, E, grid.TX, grid.NT, H, W,
-                       rgb, depth_out, alpha, state);
-    return mudg_check_launch("mudg_gauss_blend_train");
+    return blend_train("mudg_gauss_blend_train", colour, 0, uv, conic, depth, values_sorted, ranges, n, E, V, H, W, rgb, depth_out, alpha, state,
+                       true, stream);
 }
 
 extern "C" int mudg_gauss_blend_bwd(const float* colour, const float* uv, const float* conic, const float* depth, const int32_t* values_sorted,
                                     const int64_t* order, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, const float* state,
                                     const float* d_rgb, const float* d_depth, const float* d_alpha, float* partial, void* stream) {
-    MUDG_REQUIRE(colour && uv && conic && depth && values_sorted && order && ranges && state && d_rgb && d_depth && d_alpha && partial,
-                 "mudg_gauss_blend_bwd: null argument");
-    MUDG_REQUIRE(aligned16(conic) && aligned8(uv) && aligned8(order), "mudg_gauss_blend_bwd: unaligned projections or order");
-    if (const int e = check_views("mudg_gauss_blend_bwd", n, V, H, W)) return e;
-    MUDG_REQUIRE(entries_ok(E), "mudg_gauss_blend_bwd: %lld entries (1 .. 2^31 - 1)", (long long)E);
-    const GaussGrid grid(H, W);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(partial, 0, (size_t)E * GAUSS_SUMS * sizeof(float), s) != hipSuccess) return mudg_check_launch("mudg_gauss_blend_bwd");
-    hipLaunchKernelGGL(gauss_blend_bwd_kernel, dim3((unsigned)((int64_t)V * grid.NT)), dim3(256), 0, s, colour, reinterpret_cast<const f32x2*>(uv),
-                       reinterpret_cast<const f32x4*>(conic), depth, values_sorted, order, ranges, n, E, grid.TX, grid.NT, H, W, state, d_rgb, d_depth,
-                       d_alpha, partial);
-    return mudg_check_launch("mudg_gauss_blend_bwd");
+    return blend_bwd("mudg_gauss_blend_bwd", colour, 0, uv, conic, depth, values_sorted, order, ranges, n, E, V, H, W, state, d_rgb, d_depth,
+                     d_alpha, partial, stream);
+}
+
+// §27: colours (V, n, 3), one colour per (view, Gaussian); everything else as the three blends above
+extern "C" int mudg_gauss_blend_views(const float* colours, const float* uv, const float* conic, const float* depth,
+                                      const int32_t* values_sorted, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, float* rgb,
+                                      float* depth_out, float* alpha, void* stream) {
+    return blend_train("mudg_gauss_blend_views", colours, 3 * n, uv, conic, depth, values_sorted, ranges, n, E, V, H, W, rgb, depth_out, alpha,
+                       nullptr, false, stream);
+}
+
+extern "C" int mudg_gauss_blend_train_views(const float* colours, const float* uv, const float* conic, const float* depth,
+                                            const int32_t* values_sorted, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W,
+                                            float* rgb, float* depth_out, float* alpha, float* state, void* stream) {
+    return blend_train("mudg_gauss_blend_train_views", colours, 3 * n, uv, conic, depth, values_sorted, ranges, n, E, V, H, W, rgb, depth_out,
+                       alpha, state, true, stream);
+}
+
+extern "C" int mudg_gauss_blend_bwd_views(const float* colours, const float* uv, const float* conic, const float* depth,
+                                          const int32_t* values_sorted, const int64_t* order, const int32_t* ranges, int64_t n, int64_t E, int V,
+                                          int H, int W, const float* state, const float* d_rgb, const float* d_depth, const float* d_alpha,
+                                          float* partial, void* stream) {
+    return blend_bwd("mudg_gauss_blend_bwd_views", colours, 3 * n, uv, conic, depth, values_sorted, order, ranges, n, E, V, H, W, state, d_rgb,
+                     d_depth, d_alpha, partial, stream);
 }
 
 extern "C" int mudg_gauss_project_bwd(const void* points, const float* cov, const int32_t* ids, int64_t n, const float* mats, int V, int nmat,

@@ -4,9 +4,11 @@ MuDG's generated views end up in a scene of 3D Gaussians that is rendered at pos
 sparse on purpose (its images are the model's conditions): it has no opacity, no footprint that grows towards the camera, and leaves
 holes.  Here every point of a PointCloud carries a covariance and an opacity; a call projects them with EWA covariances, bins them into
 16 x 16 tiles, sorts each tile by depth and blends front to back.  The rule is stated operation by operation in DESIGN.md §23 and
-the numpy definition that the tests keep reproduces it bit for bit.  Colour is one constant per Gaussian.  `render` is the inference path;
-`render_differentiable`, `GaussianModel` and `fit` optimise position, covariance, opacity and colour against images
-through the backward kernels of csrc/gaussians_bwd.hip; `DensityControl`, `DensityStats` and `densify_and_prune` let a
+the numpy definition that the tests keep reproduces it bit for bit.  Colour is one constant per Gaussian, or, with coefficients `sh`
+(csrc/gaussians_sh.hip), that constant plus real spherical harmonics of degrees 1 .. 3 of the direction the Gaussian is
+seen from.  `render` is the inference path; `render_differentiable`, `GaussianModel` and `fit` optimise position,
+covariance, opacity and colour (with `sh_degree` also the harmonics) against images through the backward kernels of
+csrc/gaussians_bwd.hip; `DensityControl`, `DensityStats` and `densify_and_prune` let a
 fit clone, split and prune its Gaussians through csrc/gaussians_density.hip; `image_loss` is 3DGS's L1 + D-SSIM loss with
 its backward in csrc/gaussians_loss.hip, which `fit(..., ssim_weight=0.2)` minimises.  There is no CPU path: tensors that are not on the GPU are
 an error.
@@ -56,9 +58,13 @@ def _on_gpu(name, t, dtype, shape):
 class Gaussians:
     """A PointCloud (positions and colours), `cov` (n, 6) fp32 = (xx, xy, xz, yy, yz, zz) in the point's own frame (the world for the
     background, the object's frame for an object), `opacity` (n,) fp32 in [0, 1] and `ids` (n,) int32 or None: the matrix a point goes
-    through, 0 for the background and 1 + object for an object."""
+    through, 0 for the background and 1 + object for an object.  `sh` (n, K - 1, 3) fp32 in byte units or None: the coefficients of the
+    real spherical harmonics of degrees 1 .. L, K = (L + 1)^2, L = 1, 2 or 3; with them `colour` (n, 3) fp32 in byte units
+    is the direction-independent term (default: the cloud's bytes), and render draws max(0, colour + sum B_k(d) sh[k - 1]) per view."""
+    sh = colour = None
 
-    def __init__(self, cloud: PointCloud, cov: torch.Tensor, opacity: torch.Tensor, ids: Optional[torch.Tensor] = None):
+    def __init__(self, cloud: PointCloud, cov: torch.Tensor, opacity: torch.Tensor, ids: Optional[torch.Tensor] = None,
+                 sh: Optional[torch.Tensor] = None, colour: Optional[torch.Tensor] = None):
         if not isinstance(cloud, PointCloud) or not cloud.points.is_cuda:
             raise hip.MudgError("Gaussians: the cloud is a PointCloud on the GPU (there is no CPU path)")
         n = len(cloud)
@@ -66,6 +72,12 @@ class Gaussians:
         self.cov = _on_gpu("Gaussians: cov", cov, torch.float32, (n, 6))
         self.opacity = _on_gpu("Gaussians: opacity", opacity, torch.float32, (n,))
         self.ids = None if ids is None else _on_gpu("Gaussians: ids", ids, torch.int32, (n,))
+        self.sh = self.colour = None
+        if sh is not None:
+            self.sh = _on_gpu("Gaussians: sh", sh, torch.float32, (n, _sh_rows_of("Gaussians", sh), 3))
+            self.colour = _byte_colours(cloud.points) if colour is None else _on_gpu("Gaussians: colour", colour, torch.float32, (n, 3))
+        elif colour is not None:
+            raise hip.MudgError("Gaussians: colour comes with sh; without harmonics the colour is the cloud's bytes")
 
     def __len__(self):
         return len(self.cloud)
@@ -114,6 +126,25 @@ class Gaussians:
         return cls.from_cloud(PointCloud.concatenated(background, objects.cloud), s, opacity, ids)
 
 
+def _sh_rows_of(name, sh):
+    """K - 1 of coefficients (n, K - 1, 3), refused in `name`'s words unless L is 1, 2 or 3."""
+    rows = sh.shape[1] if torch.is_tensor(sh) and sh.dim() == 3 else -1
+    if rows not in [ops.gauss_sh_rows(d) for d in range(1, ops.GAUSS_SH_MAX_DEGREE + 1)]:
+        got = tuple(sh.shape) if torch.is_tensor(sh) else type(sh).__name__
+        raise hip.MudgError(f"{name}: sh is an (n, K - 1, 3) fp32 tensor on the GPU with K = 4, 9 or 16 (degrees 1 .. 3), got {got}")
+    return rows
+
+
+def _sh_degree_of(sh):
+    return {ops.gauss_sh_rows(d): d for d in range(1, ops.GAUSS_SH_MAX_DEGREE + 1)}[sh.shape[1]]
+
+
+def _byte_colours(pts):
+    """The colour words of packed points as (n, 3) fp32 in byte units."""
+    word = pts[:, 3]
+    return torch.stack([word & 0xff, (word >> 8) & 0xff, (word >> 16) & 0xff], dim=1).to(torch.float32)
+
+
 def _bin(name, pts, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries):
     """Project, scan the tile counts, read the entry count E (the one host synchronisation) and refuse too many in `name`'s words, then
     keys, the stable sort and the tiles' ranges.  Returns a namespace of uv, conic, depth, rect, count, offsets, entries (E), values
@@ -147,7 +178,8 @@ def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=
     shared by the views; hw: (H, W).  Returns {"rgb": (V, 3, H, W) in [0, 1] on black, "depth": (V, H, W) alpha-weighted metres, "alpha":
     (V, H, W)}, fp32.  stats: a dict that receives "entries" (E, the (tile, Gaussian) pairs), "longest_tile" and the tensors "count",
     "rect", "values" (sorted) and "ranges"; a (V NT,) int32 tensor put under "walked" beforehand is filled with the entries each tile's
-    workgroup staged (tools).  One host synchronisation reads E (a second one, for the longest tile, only with stats); more than
+    workgroup staged (tools; not with harmonics).  With g.sh the colours of every (view, Gaussian) are evaluated first
+    and the blend reads those; without, nothing changes.  One host synchronisation reads E (a second one, for the longest tile, only with stats); more than
     max_entries (or 2^31 - 1) entries are refused."""
     if not isinstance(g, Gaussians):
         raise hip.MudgError("render: expected Gaussians")
@@ -168,7 +200,13 @@ def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=
     if b.entries == 0:
         return dict(zip(("rgb", "depth", "alpha"), _blank(views, h, w, dev)))
     walked = stats.get("walked") if stats is not None else None
-    rgb, out_depth, alpha = ops.gauss_blend(pts, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w), walked=walked)
+    if g.sh is not None:
+        if walked is not None:
+            raise hip.MudgError("render: the blend that reads per-view colours does not count the entries it walked")
+        colours = ops.gauss_sh_colour(pts, mats.contiguous(), b.count, g.colour, g.sh, ids=g.ids)
+        rgb, out_depth, alpha = ops.gauss_blend_views(colours, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w))
+    else:
+        rgb, out_depth, alpha = ops.gauss_blend(pts, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w), walked=walked)
     if stats is not None:
         stats.update(longest_tile=int((b.ranges[:, 1] - b.ranges[:, 0]).max().item()), values=b.values, ranges=b.ranges)
     return {"rgb": rgb, "depth": out_depth, "alpha": alpha}
@@ -224,16 +262,24 @@ def _pack_xyz(xyz):
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density=None):
+    def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density=None, sh=None, sh_degree=None):
         h, w = hw
         ctx.density = density
+        ctx.sh_degree = sh_degree if sh is not None else None
         pts = _pack_xyz(xyz)
         cov, opacity, colour = cov.detach().contiguous(), opacity.detach().contiguous(), colour.detach().contiguous()
         b = _bin("render_differentiable", pts, cov, opacity, mats, cams, (h, w), ids, znear, zfar, max_entries)
         ctx.meta = (cams, (h, w), ids, znear, zfar, b.entries)
         if b.entries == 0:
-            ctx.save_for_backward(xyz)
+            ctx.save_for_backward(xyz, *(() if sh is None else (sh,)))
             return _blank(mats.shape[0], h, w, xyz.device)
+        if sh is not None:                                                  # §27: one colour per (view, Gaussian)
+            sh = sh.detach().contiguous()
+            colours = ops.gauss_sh_colour(pts, mats, b.count, colour, sh, ids=ids, active=sh_degree)
+            rgb, out_depth, alpha, state = ops.gauss_blend_train_views(colours, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w))
+            ctx.save_for_backward(pts, colour, cov, mats, b.uv, b.conic, b.depth, b.values, b.order, b.offsets, b.count, b.ranges, state, sh,
+                                  colours)
+            return rgb, out_depth, alpha
         rgb, out_depth, alpha, state = ops.gauss_blend_train(colour, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w))
         ctx.save_for_backward(pts, colour, cov, mats, b.uv, b.conic, b.depth, b.values, b.order, b.offsets, b.count, b.ranges, state)
         return rgb, out_depth, alpha
@@ -244,26 +290,40 @@ class _Render(torch.autograd.Function):
         if entries == 0:                                                    # nothing was drawn: no launch
             n, dev = ctx.saved_tensors[0].shape[0], ctx.saved_tensors[0].device
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-            return (z(n, 3), z(n, 3), z(n, 6), z(n)) + (None,) * 8
-        pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state = ctx.saved_tensors
+            tail = (torch.zeros_like(ctx.saved_tensors[1]), None) if len(ctx.saved_tensors) > 1 else ()
+            return (z(n, 3), z(n, 3), z(n, 6), z(n)) + (None,) * 8 + tail
+        pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state = ctx.saved_tensors[:13]
+        sh, colours = ctx.saved_tensors[13:] if len(ctx.saved_tensors) > 13 else (None, None)
         views, (h, w) = mats.shape[0], hw
         grad = lambda g, shape: torch.zeros(shape, dtype=torch.float32, device=pts.device) if g is None else g.to(torch.float32).contiguous()
-        partial = ops.gauss_blend_bwd(colour, uv, conic, depth, values, order, ranges, hw, state, grad(d_rgb, (views, 3, h, w)),
-                                      grad(d_depth, (views, h, w)), grad(d_alpha, (views, h, w)))
+        ups = (grad(d_rgb, (views, 3, h, w)), grad(d_depth, (views, h, w)), grad(d_alpha, (views, h, w)))
+        if sh is None:
+            partial = ops.gauss_blend_bwd(colour, uv, conic, depth, values, order, ranges, hw, state, *ups)
+        else:
+            partial = ops.gauss_blend_bwd_views(colours, uv, conic, depth, values, order, ranges, hw, state, *ups)
         d_xyz, d_cov, d_opacity, d_colour = ops.gauss_project_bwd(pts, cov, mats, cams, hw, count, offsets, partial, ids=ids, znear=znear,
                                                                   zfar=zfar)
+        tail = ()                                                           # as many gradients as forward was given arguments
+        if sh is not None:                                                  # §27: the colour columns again, through the harmonics
+            d_colour, d_sh, d_xyz_dir = ops.gauss_sh_bwd(pts, mats, count, offsets, partial, colour, sh, ids=ids, active=ctx.sh_degree)
+            d_xyz = d_xyz + d_xyz_dir
+            tail = (d_sh, None)
         if ctx.density is not None:                                         # §25: a second pass over the partials' columns 8 and 9
             ops.gauss_density_accumulate(partial, count, offsets, hw, ctx.density.grad_sum, ctx.density.seen)
-        return (d_xyz, d_colour, d_cov, d_opacity) + (None,) * 8
+        return (d_xyz, d_colour, d_cov, d_opacity) + (None,) * 8 + tail
 
 
 def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES,
-                          density=None):
+                          density=None, sh=None, sh_degree=None):
     """`render` with gradients.  xyz (n, 3), colour (n, 3) in byte units (0 .. 255, not necessarily whole), cov (n, 6) and
     opacity (n,): fp32 on the GPU; mats, cams, hw and ids as `render` takes them.  Returns (rgb (V, 3, H, W), depth (V, H, W), alpha
     (V, H, W)); backward gives gradients for the first four arguments, none for the matrices or the camera.  One host synchronisation reads
     the entry count.  density: a DensityStats of n Gaussians; backward then adds every Gaussian's screen-space gradient norm and the
-    views that counted it.  With None nothing else happens: the same launches, the same bits."""
+    views that counted it.  With None nothing else happens: the same launches, the same bits.  sh: (n, K - 1, 3) fp32
+    coefficients in byte units of the harmonics of degrees 1 .. L, K = (L + 1)^2, L = 1, 2 or 3: `colour` is then the
+    direction-independent term, every (view, Gaussian) gets max(0, colour + sum B_k(d) sh[k - 1]), backward also gives the gradient of sh
+    and adds to xyz's what reaches it through the direction; sh_degree (default L) is the highest degree that takes part, and the
+    coefficients above it get a zero gradient.  With sh None nothing else happens: the same launches, the same bits."""
     n = xyz.shape[0] if torch.is_tensor(xyz) and xyz.dim() == 2 else -1
     if density is not None and (not isinstance(density, DensityStats) or density.grad_sum.shape[0] != n):
         raise hip.MudgError(f"render_differentiable: density is a DensityStats of {n} Gaussians")
@@ -281,12 +341,23 @@ def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None
     tx, ty = ops.gauss_tiles(h, w)
     if h <= 0 or w <= 0 or mats.shape[0] * tx * ty >= 2 ** 31:
         raise hip.MudgError(f"render_differentiable: {mats.shape[0]} views of {h} x {w} (V NT < 2^31)")
-    return _Render.apply(xyz, colour, cov, opacity, mats.contiguous(), tuple(float(c) for c in cams), (h, w), ids, float(znear), float(zfar),
-                         int(max_entries), density)
+    args = (xyz, colour, cov, opacity, mats.contiguous(), tuple(float(c) for c in cams), (h, w), ids, float(znear), float(zfar), int(max_entries),
+            density)
+    if sh is None:
+        if sh_degree is not None:
+            raise hip.MudgError("render_differentiable: sh_degree comes with sh")
+        return _Render.apply(*args)
+    sh = _on_gpu("render_differentiable: sh", sh, torch.float32, (n, _sh_rows_of("render_differentiable", sh), 3))
+    degree = _sh_degree_of(sh)
+    active = degree if sh_degree is None else int(sh_degree)
+    if not 0 <= active <= degree:
+        raise hip.MudgError(f"render_differentiable: sh_degree {active} of coefficients of degree {degree}")
+    return _Render.apply(*args, sh, active)
 
 
 PARAMETERS = ("xyz", "colour", "log_scale", "quat", "opacity_logit")
 LEARNING_RATES = {"xyz": 2e-3, "colour": 2.0, "log_scale": 5e-3, "quat": 1e-3, "opacity_logit": 5e-2}      # metres, bytes, log metres, -, logits
+LEARNING_RATES["sh"] = LEARNING_RATES["colour"] / 20       # bytes; 3DGS's ratio of the two rates, not tuned here
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-15
 MAX_SEED_OPACITY = 0.999                       # a seed opacity of 1 would be an infinite logit
 
@@ -295,20 +366,43 @@ class GaussianModel:
     """Gaussians as the tensors an optimiser moves: `xyz` (n, 3) metres, `colour` (n, 3) in byte units, `log_scale` (n, 3) (the logarithm
     of the per-axis standard deviation), `quat` (n, 4) = (w, x, y, z), `opacity_logit` (n,), all fp32 leaves on the GPU that require
     gradients, and `ids` (n,) int32 or None as Gaussians has them.  Covariance R exp(log_scale)^2 R^T and opacity sigmoid(opacity_logit)
-    are torch expressions, so autograd carries the kernels' gradients to the parameters."""
+    are torch expressions, so autograd carries the kernels' gradients to the parameters.  `sh` (n, K - 1, 3) fp32 in byte units or None:
+    the coefficients of the harmonics of degrees 1 .. L, a sixth leaf when present; enable_sh(L) creates zeros."""
+    sh = None
 
-    def __init__(self, xyz, colour, log_scale, quat, opacity_logit, ids=None):
+    def __init__(self, xyz, colour, log_scale, quat, opacity_logit, ids=None, sh=None):
         n = xyz.shape[0] if torch.is_tensor(xyz) and xyz.dim() == 2 else -1
         shapes = {"xyz": (n, 3), "colour": (n, 3), "log_scale": (n, 3), "quat": (n, 4), "opacity_logit": (n,)}
         for name, t in zip(PARAMETERS, (xyz, colour, log_scale, quat, opacity_logit)):
             setattr(self, name, _on_gpu(f"GaussianModel: {name}", t, torch.float32, shapes[name]).detach().clone().requires_grad_(True))
         self.ids = None if ids is None else _on_gpu("GaussianModel: ids", ids, torch.int32, (n,))
+        self.sh = None
+        if sh is not None:
+            self.sh = _on_gpu("GaussianModel: sh", sh, torch.float32, (n, _sh_rows_of("GaussianModel", sh), 3)).detach().clone().requires_grad_(True)
 
     def __len__(self):
         return self.xyz.shape[0]
 
+    @property
+    def sh_degree(self):
+        """L of the model's harmonics, 0 without."""
+        return 0 if self.sh is None else _sh_degree_of(self.sh)
+
+    def enable_sh(self, degree):
+        """Give the model zero coefficients of degrees 1 .. `degree` (1, 2 or 3).  A model that has harmonics keeps them if the degree is
+        theirs and refuses another."""
+        degree = int(degree)
+        if not 1 <= degree <= ops.GAUSS_SH_MAX_DEGREE:
+            raise hip.MudgError(f"GaussianModel.enable_sh: degree {degree} (1, 2 or 3)")
+        if self.sh is None:
+            self.sh = torch.zeros((len(self), ops.gauss_sh_rows(degree), 3), dtype=torch.float32, device=self.xyz.device).requires_grad_(True)
+        elif self.sh_degree != degree:
+            raise hip.MudgError(f"GaussianModel.enable_sh: the model has harmonics of degree {self.sh_degree}, not {degree}")
+        return self
+
     def parameters(self):
-        return {name: getattr(self, name) for name in PARAMETERS}
+        """The leaves by name: PARAMETERS, and "sh" when the model has harmonics."""
+        return {name: getattr(self, name) for name in PARAMETERS + (("sh",) if self.sh is not None else ())}
 
     def covariance(self):
         return covariance_from_scales_rotations(torch.exp(self.log_scale), self.quat)
@@ -342,12 +436,16 @@ class GaussianModel:
 
     def gaussians(self) -> Gaussians:
         """The inference set: positions as they are, colours rounded (floor(c + 0.5)) and clamped to bytes, covariance and opacity
-        evaluated.  render, render_scene and render_cloud_views' renderer draw it."""
+        evaluated.  render, render_scene and render_cloud_views' renderer draw it.  With harmonics the set also carries `sh` and, beside
+        the byte word, `colour`, both unrounded: what the fit optimised is what is drawn."""
         with torch.no_grad():
             byte = torch.floor(self.colour + 0.5).clamp_(0.0, 255.0).to(torch.int32)
             word = byte[:, 0] | (byte[:, 1] << 8) | (byte[:, 2] << 16)
             pts = torch.cat([self.xyz.contiguous().view(torch.int32), word[:, None]], dim=1).contiguous()
-            return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids)
+            if self.sh is None:
+                return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids)
+            return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids,
+                             sh=self.sh.detach().clone(), colour=self.colour.detach().clone())
 
 
 # ------------------------------------------------------------------------------------------------ growing and pruning while fitting (§25)
@@ -408,10 +506,26 @@ class DensityControl:
         return self.reset_every is not None and self.gathers(it) and (it + 1) % self.reset_every == 0
 
 
+def density_rows(action, rows, value, m, v):
+    """colour's rule of DESIGN.md §25 for any per-Gaussian tensor, in torch: `action` (n,) and `rows` (n,) int32 are the plan's; a kept
+    Gaussian's row is copied with its moments, a cloned one's is copied with its moments and once more with zero moments, a split one's
+    twice with zero moments, a pruned one's not at all; children are adjacent and the survivors keep their order.  Returns (value, m, v)
+    with sum(rows) rows.  densify_and_prune moves `sh` with it: once per `every` iterations, so no kernel."""
+    n = action.shape[0]
+    rows = rows.to(torch.int64)
+    src = torch.repeat_interleave(torch.arange(n, device=action.device), rows)
+    start = torch.cumsum(rows, 0) - rows
+    first = torch.arange(src.shape[0], device=action.device) == start[src]
+    act = action[src]
+    carries = (act == ops.GAUSS_KEEP) | ((act == ops.GAUSS_CLONE) & first)
+    carries = carries.reshape((-1,) + (1,) * (value.dim() - 1))
+    return value[src], torch.where(carries, m[src], torch.zeros_like(m[src])), torch.where(carries, v[src], torch.zeros_like(v[src]))
+
+
 def densify_and_prune(model: GaussianModel, stats: DensityStats, moments: dict, control: DensityControl, *, grow=True) -> dict:
     """One step of density control: plan, exclusive sum, apply.  moments: {name: (m, v)}, the Adam moments of the model's
     parameters (a missing name: zeros).  Replaces the model's five leaves (fresh leaves that require gradients), its ids and the
-    entries of `moments`, and zeroes `stats` at the new size; survivors keep their order and a Gaussian's children are adjacent.  If growing
+    entries of `moments` (with harmonics also `sh` and its moments, by colour's rule: density_rows), and zeroes `stats` at the new size; survivors keep their order and a Gaussian's children are adjacent.  If growing
     would exceed control.max_gaussians the step is planned again without it.  A step that would leave no Gaussian raises MudgError and
     leaves everything as it was.  Two host synchronisations: the new count, and the counts returned: {"before", "after", "kept",
     "pruned", "cloned", "split", "grew"}."""
@@ -443,6 +557,13 @@ def densify_and_prune(model: GaussianModel, stats: DensityStats, moments: dict, 
         outs, ids = ops.gauss_density_apply(action, ends - rows, total, scale, rot, tensors, split_offset=control.split_offset,
                                             log_shrink=control.log_shrink, ids=model.ids)
         kept, pruned, cloned, split = torch.bincount(action, minlength=4).tolist()
+        if model.sh is not None:                                            # §27: the harmonics follow colour's rule
+            p = model.sh.detach()
+            m, v = moments["sh"] if "sh" in moments else (torch.zeros_like(p), torch.zeros_like(p))
+            sh, sh_m, sh_v = density_rows(action, rows, p, m, v)
+    if model.sh is not None:
+        model.sh = sh.contiguous().requires_grad_(True)
+        moments["sh"] = (sh_m.contiguous(), sh_v.contiguous())
     for k, name in enumerate(PARAMETERS):
         setattr(model, name, outs[3 * k].requires_grad_(True))
         moments[name] = (outs[3 * k + 1], outs[3 * k + 2])
@@ -525,7 +646,7 @@ image_loss.terms = _image_loss_terms
 
 
 def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_per_step=None, depth_targets=None, depth_weight=0.0,
-        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None, ssim_weight=0.0):
+        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None, ssim_weight=0.0, sh_degree=0, sh_raise_every=None):
     """Optimise `model` in place against targets (V, 3, H, W) fp32 in [0, 1] seen through mats (V, nmat, 12) and cams.
     Iteration i renders the views_per_step (default: all) views (i views_per_step + k) mod V, takes the mean absolute difference of rgb,
     adds depth_weight times the mean absolute depth difference over the pixels where depth_targets (V, H, W) is positive, and takes one
@@ -537,8 +658,12 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
     window, the fit is the fixed-set fit bit for bit.  ssim_weight: with 0 (the default) the loss is the torch expression above, bit for
     bit what it was before the keyword existed; with a value in (0, 1] the iteration's loss is image_loss:
     (1 - ssim_weight) times the mean absolute difference plus ssim_weight (1 - mean SSIM) plus the same depth term, forward and backward
-    in the kernels of csrc/gaussians_loss.hip; 3DGS fits with 0.2.  No spherical harmonics or pose gradient.  Returns the loss of every
-    iteration."""
+    in the kernels of csrc/gaussians_loss.hip; 3DGS fits with 0.2.  sh_degree: L = 1, 2 or 3 fits view-dependent colour:
+    the model gets zero coefficients of degrees 1 .. L if it has none (one that has them must have that degree), "sh" moves with the
+    other parameters at its own rate LEARNING_RATES["sh"] (lr may name it), density control carries its rows and moments as it carries
+    colour's, and model.gaussians() hands the coefficients to render.  The active degree starts at 0 and rises by one every
+    sh_raise_every iterations until it is L; None: all degrees from the first iteration.  With sh_degree=0 (the default) nothing changes,
+    bit for bit, and a model that has harmonics is refused.  No pose gradient.  Returns the loss of every iteration."""
     from .train import kernels as K
     if not isinstance(model, GaussianModel):
         raise hip.MudgError("fit: expected a GaussianModel")
@@ -554,10 +679,19 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
     targets = _on_gpu("fit: targets", targets, torch.float32, (views, 3, h, w))
     if depth_targets is not None:
         depth_targets = _on_gpu("fit: depth_targets", depth_targets, torch.float32, (views, h, w))
+    sh_degree = int(sh_degree)
+    if not 0 <= sh_degree <= ops.GAUSS_SH_MAX_DEGREE or (sh_raise_every is not None and int(sh_raise_every) <= 0):
+        raise hip.MudgError(f"fit: sh_degree {sh_degree} is 0 .. {ops.GAUSS_SH_MAX_DEGREE} and sh_raise_every {sh_raise_every} positive or None")
+    if model.sh_degree != sh_degree and (sh_degree == 0 or model.sh is not None):
+        raise hip.MudgError(f"fit: sh_degree {sh_degree} for a model with harmonics of degree {model.sh_degree}")
+    known = PARAMETERS + ("sh",)
     rates = dict(LEARNING_RATES, **(lr or {}))
     names = [n for n in PARAMETERS if n in tuple(trainable)]
-    if not names or set(trainable) - set(PARAMETERS) or set(rates) - set(PARAMETERS) or int(iters) < 0:
+    if not names or set(trainable) - set(known) or set(rates) - set(known) or int(iters) < 0:
         raise hip.MudgError(f"fit: trainable and lr name parameters among {PARAMETERS}, got {tuple(trainable)} and {tuple(rates)}")
+    if sh_degree:
+        model.enable_sh(sh_degree)
+        names.append("sh")
     per = views if views_per_step is None else int(views_per_step)
     if not 1 <= per <= views:
         raise hip.MudgError(f"fit: {per} views per step of {views}")
@@ -584,9 +718,12 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
         if gathers and stats is None:
             stats = DensityStats(len(model), mats.device)
         pick = torch.tensor([(it * per + k) % views for k in range(per)], device=mats.device)
+        harmonics = {}
+        if sh_degree:                                                       # §27: the active degree rises by one every sh_raise_every
+            harmonics = dict(sh=model.sh, sh_degree=sh_degree if sh_raise_every is None else min(sh_degree, it // int(sh_raise_every)))
         rgb, depth, _ = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(), mats[pick], cams, (h, w),
                                               ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries,
-                                              density=stats if gathers else None)
+                                              density=stats if gathers else None, **harmonics)
         with_depth = depth_targets is not None and bool(depth_weight)
         if ssim_weight:                                                     # §26: the loss and its backward in csrc/gaussians_loss.hip
             loss = image_loss(rgb, targets[pick], depth if with_depth else None, depth_targets[pick] if with_depth else None,

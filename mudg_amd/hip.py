@@ -197,6 +197,11 @@ SIGNATURES = {
     "mudg_gauss_blend_train": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mudg_gauss_blend_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mudg_gauss_project_bwd": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P, _L, _P, _P, _P, _P, _P]),
+    "mudg_gauss_sh_colour": (_I, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "mudg_gauss_sh_bwd": (_I, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "mudg_gauss_blend_views": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P]),
+    "mudg_gauss_blend_train_views": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mudg_gauss_blend_bwd_views": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "mudg_gauss_density_accumulate": (_I, [_P, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P]),
     "mudg_gauss_density_plan": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _P, _P, _P]),
     "mudg_gauss_density_apply": (_I, [_P, _P, _L, _L, _P, _P, _F, _F, _P, _P, _P, _P, _P]),

@@ -1067,6 +1067,114 @@ def gauss_project_bwd(points, cov, mats, intr, hw, count, offsets, partial, *, i
     return d_xyz, d_cov, d_opacity, d_colour
 
 
+GAUSS_SH_MAX_DEGREE = 3
+
+
+def gauss_sh_rows(degree):
+    """K - 1 = (L + 1)^2 - 1: the coefficient rows of a Gaussian that carries harmonics of degrees 1 .. L."""
+    return (int(degree) + 1) ** 2 - 1
+
+
+def _gauss_sh(name, points, mats, ids, count, colour, sh, active):
+    """The operands gauss_sh_colour and its backward share -> (n, V, nmat, L, active)."""
+    _splat_tensor(f"{name}: points", points, torch.int32)
+    if points.dim() != 2 or points.shape[1] != 4 or points.shape[0] == 0:
+        raise hip.MudgError(f"{name}: expected packed points (n > 0, 4), got {tuple(points.shape)}")
+    n = points.shape[0]
+    _splat_tensor(f"{name}: mats", mats, torch.float32)
+    if mats.dim() != 3 or mats.shape[2] != 12 or mats.shape[0] == 0 or mats.shape[1] == 0:
+        raise hip.MudgError(f"{name}: expected matrices (V, nmat, 12), got {tuple(mats.shape)}")
+    v, nmat = mats.shape[:2]
+    if ids is not None:
+        _splat_tensor(f"{name}: ids", ids, torch.int32, (n,))
+    _splat_tensor(f"{name}: count", count, torch.int32, (v, n))
+    _splat_tensor(f"{name}: colour", colour, torch.float32, (n, 3))
+    _splat_tensor(f"{name}: sh", sh, torch.float32)
+    degrees = {gauss_sh_rows(d): d for d in range(1, GAUSS_SH_MAX_DEGREE + 1)}
+    if sh.dim() != 3 or sh.shape[0] != n or sh.shape[2] != 3 or sh.shape[1] not in degrees:
+        raise hip.MudgError(f"{name}: expected coefficients ({n}, K - 1, 3) with K - 1 in {tuple(degrees)}, got {tuple(sh.shape)}")
+    degree = degrees[sh.shape[1]]
+    active = degree if active is None else int(active)
+    if not 0 <= active <= degree:
+        raise hip.MudgError(f"{name}: active degree {active} of {degree}")
+    return n, v, nmat, degree, active
+
+
+def gauss_sh_colour(points, mats, count, colour, sh, *, ids=None, active=None):
+    """One colour per (view, Gaussian): colours (V, n, 3) fp32 = max(0, colour + sum B_k(d) sh[k - 1]) in byte units, d the
+    unit direction from the view's camera centre to the Gaussian in the Gaussian's own frame, +0 where count (V, n) is 0.  points, mats,
+    ids and count as gauss_project takes and returns them; colour (n, 3), sh (n, K - 1, 3) fp32 with K = (L + 1)^2, L = 1, 2 or 3;
+    active (default L): the highest degree the sum takes."""
+    n, v, nmat, degree, active = _gauss_sh("gauss_sh_colour", points, mats, ids, count, colour, sh, active)
+    colours = torch.empty((v, n, 3), dtype=torch.float32, device=points.device)
+    hip.check(hip.lib().mudg_gauss_sh_colour(points.data_ptr(), _ptr(ids), n, mats.data_ptr(), v, nmat, count.data_ptr(), colour.data_ptr(),
+                                             sh.data_ptr(), degree, active, colours.data_ptr(), _stream()), "mudg_gauss_sh_colour")
+    return colours
+
+
+def gauss_sh_bwd(points, mats, count, offsets, partial, colour, sh, *, ids=None, active=None):
+    """gauss_sh_colour's backward from the partials of gauss_blend_bwd_views: d_colour (n, 3), d_sh (n, K - 1, 3) (+0 above the active
+    degree) and d_xyz_dir (n, 3), the gradient that reaches the position through the direction; fp32, the views added in order."""
+    n, v, nmat, degree, active = _gauss_sh("gauss_sh_bwd", points, mats, ids, count, colour, sh, active)
+    _splat_tensor("gauss_sh_bwd: offsets", offsets, torch.int64, (v, n))
+    _gauss_partial("gauss_sh_bwd", partial)
+    d_colour = torch.empty_like(colour)
+    d_sh = torch.empty_like(sh)
+    d_xyz = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    hip.check(hip.lib().mudg_gauss_sh_bwd(points.data_ptr(), _ptr(ids), n, mats.data_ptr(), v, nmat, count.data_ptr(), offsets.data_ptr(),
+                                          partial.data_ptr(), partial.shape[0], colour.data_ptr(), sh.data_ptr(), degree, active,
+                                          d_colour.data_ptr(), d_sh.data_ptr(), d_xyz.data_ptr(), _stream()), "mudg_gauss_sh_bwd")
+    return d_colour, d_sh, d_xyz
+
+
+def _gauss_entries_views(name, colours, uv, conic, depth, values_sorted, ranges, hw):
+    """_gauss_entries for colours (V, n, 3): every view's slice is an (n, 3) colour tensor."""
+    _splat_tensor(f"{name}: colours", colours, torch.float32)
+    _splat_tensor(f"{name}: depth", depth, torch.float32)
+    if colours.dim() != 3 or depth.dim() != 2 or tuple(colours.shape) != (*depth.shape, 3) or colours.shape[0] == 0:
+        raise hip.MudgError(f"{name}: colours {tuple(colours.shape)} with depths {tuple(depth.shape)}")
+    return _gauss_entries(name, colours[0], _GAUSS_COLOURS, uv, conic, depth, values_sorted, ranges, hw)
+
+
+def gauss_blend_views(colours, uv, conic, depth, values_sorted, ranges, hw):
+    """gauss_blend with one fp32 colour per (view, Gaussian), colours (V, n, 3) in byte units: rgb, depth, alpha."""
+    v, n, h, w, _ = _gauss_entries_views("gauss_blend_views", colours, uv, conic, depth, values_sorted, ranges, hw)
+    rgb, out_depth, alpha = _gauss_images(v, h, w, colours.device)
+    hip.check(hip.lib().mudg_gauss_blend_views(colours.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(), values_sorted.data_ptr(),
+                                               ranges.data_ptr(), n, values_sorted.numel(), v, h, w, rgb.data_ptr(), out_depth.data_ptr(),
+                                               alpha.data_ptr(), _stream()), "mudg_gauss_blend_views")
+    return rgb, out_depth, alpha
+
+
+def gauss_blend_train_views(colours, uv, conic, depth, values_sorted, ranges, hw):
+    """gauss_blend_train with colours (V, n, 3): rgb, depth, alpha and state (V, 5, H, W)."""
+    v, n, h, w, _ = _gauss_entries_views("gauss_blend_train_views", colours, uv, conic, depth, values_sorted, ranges, hw)
+    rgb, out_depth, alpha = _gauss_images(v, h, w, colours.device)
+    state = torch.empty((v, 5, h, w), dtype=torch.float32, device=colours.device)
+    hip.check(hip.lib().mudg_gauss_blend_train_views(colours.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(),
+                                                     values_sorted.data_ptr(), ranges.data_ptr(), n, values_sorted.numel(), v, h, w,
+                                                     rgb.data_ptr(), out_depth.data_ptr(), alpha.data_ptr(), state.data_ptr(), _stream()),
+              "mudg_gauss_blend_train_views")
+    return rgb, out_depth, alpha, state
+
+
+def gauss_blend_bwd_views(colours, uv, conic, depth, values_sorted, order, ranges, hw, state, d_rgb, d_depth, d_alpha):
+    """gauss_blend_bwd with colours (V, n, 3): partial (E, 10), whose columns 0 .. 2 are the gradient of an entry's (view, Gaussian) colour."""
+    v, n, h, w, _ = _gauss_entries_views("gauss_blend_bwd_views", colours, uv, conic, depth, values_sorted, ranges, hw)
+    e = values_sorted.numel()
+    _splat_tensor("gauss_blend_bwd_views: order", order, torch.int64, (e,))
+    _splat_tensor("gauss_blend_bwd_views: state", state, torch.float32, (v, 5, h, w))
+    _splat_tensor("gauss_blend_bwd_views: d_rgb", d_rgb, torch.float32, (v, 3, h, w))
+    _splat_tensor("gauss_blend_bwd_views: d_depth", d_depth, torch.float32, (v, h, w))
+    _splat_tensor("gauss_blend_bwd_views: d_alpha", d_alpha, torch.float32, (v, h, w))
+    partial = torch.empty((e, GAUSS_SUMS), dtype=torch.float32, device=colours.device)
+    hip.check(hip.lib().mudg_gauss_blend_bwd_views(colours.data_ptr(), uv.data_ptr(), conic.data_ptr(), depth.data_ptr(), values_sorted.data_ptr(),
+                                                   order.data_ptr(), ranges.data_ptr(), n, e, v, h, w, state.data_ptr(), d_rgb.data_ptr(),
+                                                   d_depth.data_ptr(), d_alpha.data_ptr(), partial.data_ptr(), _stream()),
+              "mudg_gauss_blend_bwd_views")
+    return partial
+
+
 GAUSS_KEEP, GAUSS_PRUNE, GAUSS_CLONE, GAUSS_SPLIT = 0, 1, 2, 3      # the plan's action codes
 GAUSS_PARAMETER_WIDTHS = (3, 3, 3, 4, 1)                            # xyz, colour, log_scale, quat, opacity_logit
 
