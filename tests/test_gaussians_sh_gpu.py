@@ -3,7 +3,8 @@ against the CPU definition of DESIGN.md §27 (tests/gaussians_sh_reference.py): 
 state, the partial buffer and every gradient, since both sides perform the same rounded fp32 operations in the same order; the five
 entry points raw inside sentinels; the old path's bits where the harmonics take no part; and the fit against its float64 counterpart.
 The shapes are the smallest that can go wrong: 300 Gaussians (two workgroups, a ragged last wave), three views, two matrices a view
-with ids, a 40 x 56 image (not whole tiles), Gaussians behind the camera in one view only, colours negative enough to clamp."""
+with ids, a 40 x 56 image (not whole tiles), Gaussians behind the camera in one view only, colours negative enough to clamp.
+The size, active-degree, ids, clamp, guard and batch-edge cases of the raw kernels live in tests/test_gaussians_sh_kernels_gpu.py."""
 import functools
 
 import numpy as np
