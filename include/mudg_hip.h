@@ -680,6 +680,27 @@ int mudg_gauss_blend_bwd_views(const float* colours, const float* uv, const floa
                                const int64_t* order, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W, const float* state,
                                const float* d_rgb, const float* d_depth, const float* d_alpha, float* partial, void* stream);
 
+/* ------------------------------------------------------------------ pose gradients (csrc/gaussians_pose.hip, gaussians_sh.hip)
+ * The gradient of mats (V, nmat, 12): d_mats (V, nmat, 12) fp32, every element overwritten.  points, cov, ids, mats, the camera, count,
+ * offsets, partial and E are what mudg_gauss_project_bwd (pose_bwd) and mudg_gauss_sh_bwd (sh_pose_bwd) take, with their guards and
+ * refusals; V <= 65535.  stage: caller-allocated scratch of V nmat ceil(n / 256) 12 floats, cleared by the call.
+ * pose_bwd, a lane per (view, Gaussian).  Where project_bwd counts the pair, with m = mats[v][id] (id clamped), p the position and dxc,
+ *   dyc, dzc, dt0, dt1 project_bwd's chain quantities:
+ *     g[3] = dxc, g[7] = dyc, g[11] = dzc; for k = 0, 1, 2: g[k] = dxc p[k] + dt0[k] j00, g[4 + k] = dyc p[k] + dt1[k] j11,
+ *     g[8 + k] = dzc p[k] + (dt0[k] j02 + dt1[k] j12)
+ * sh_pose_bwd, likewise: with dv the view's addend to mudg_gauss_sh_bwd's d_xyz_dir, for r = 0, 1, 2:
+ *     g[4r + k] = dv[k] m[4r + 3], g[4r + 3] = (dv[0] m[4r] + dv[1] m[4r + 1]) + dv[2] m[4r + 2]
+ * The sum over the Gaussians of one (view, matrix), the same in both: chunks of 256 consecutive Gaussians; in a chunk a lane that holds
+ *   another id, is not counted or lies past n adds +0; the 256 values are added by the xor butterfly over 1 .. 32 inside each wave and the
+ *   four waves as ((w0 + w1) + w2) + w3.  Then lane l of a finishing workgroup adds the sums of chunks l, l + 256, ... in ascending order
+ *   from +0, and the 256 lane sums are added in the same butterfly-and-waves order.  A matrix nobody goes through gets twelve +0.  No atomics. */
+int mudg_gauss_pose_bwd(const void* points, const float* cov, const int32_t* ids, int64_t n, const float* mats, int V, int nmat, int H, int W,
+                        float fx, float fy, float cx, float cy, float znear, float zfar, const int32_t* count, const int64_t* offsets,
+                        const float* partial, int64_t E, float* stage, float* d_mats, void* stream);
+int mudg_gauss_sh_pose_bwd(const void* points, const int32_t* ids, int64_t n, const float* mats, int V, int nmat, const int32_t* count,
+                           const int64_t* offsets, const float* partial, int64_t E, const float* colour, const float* sh, int degree,
+                           int active, float* stage, float* d_mats_dir, void* stream);
+
 /* ------------------------------------------------------------------ density control for the fit (csrc/gaussians_density.hip)
  * Which Gaussians a fit clones, splits and prunes, and the pass that rewrites the parameters.  fp32, single rounded operations in the
  * order written, a lane per Gaussian, plain stores, no atomics, no generator state, no transcendental.

@@ -2,7 +2,8 @@
 // gaussians_bwd.hip, §24; gaussians_density.hip, §25; gaussians_loss.hip, §26; gaussians_sh.hip, §27), written once: the constants of the rule, the single
 // rounded operations, the polynomial exponential, a Gaussian's load and its projection into a view, a tile's prologue, the staging of an
 // entry, the blend step and the forward blend loop, the walk over a Gaussian's partials, the fixed-order tile reduction, and the checks
-// the entry points share.  One copy, so that the backward recomputes the forward's values bit for bit.
+// the entry points share, the chain rule of one (view, Gaussian) (§24) and the fixed-order reduction over all Gaussians of a (view, matrix)
+// (§28).  One copy, so that the backward recomputes the forward's values bit for bit.
 #pragma once
 #include "splat_shared.h"
 
@@ -298,6 +299,143 @@ __device__ __forceinline__ T butterfly_sum(T r) {
 template <class T>
 __device__ __forceinline__ T four_waves(T w0, T w1, T w2, T w3) { return plus(plus(plus(w0, w1), w2), w3); }
 
+// ------------------------------------------------------------------------------------------------ one view's chain rule (§24)
+// The sums `acc` of a (view, Gaussian)'s partials through the projection `w` = gauss_view(m, ...): what reaches xc, yc, zc (dzc with the
+// path through the Jacobian, a clamped tx or ty passing nothing through xc / zc), the rows of T = J R, and the view's addend to the
+// covariance's gradient in the order (xx, xy, xz, yy, yz, zz), off-diagonal entries with both halves.
+struct GaussViewBwd {
+    float dxc, dyc, dzc, dt0[3], dt1[3], dcov[6];
+};
+
+__device__ __forceinline__ void gauss_view_bwd(const float* __restrict__ m, const GaussView& w, const GaussCam& cam,
+                                               const float (&acc)[GAUSS_SUMS], GaussViewBwd& o) {
+    const float A = dvd(w.c, w.det), B = -dvd(w.b, w.det), C = dvd(w.a, w.det);
+    // conic -> (a, b, c): with K the conic and G = [[gA, gB / 2], [gB / 2, gC]], d(a, b, c) = -(K G K) read as (00, 2 x 01, 11)
+    const float gA = acc[SUM_A], hB = mul(0.5f, acc[SUM_B]), gC = acc[SUM_C];
+    const float x00 = add(mul(gA, A), mul(hB, B)), x01 = add(mul(gA, B), mul(hB, C));
+    const float x10 = add(mul(hB, A), mul(gC, B)), x11 = add(mul(hB, B), mul(gC, C));
+    const float da = -add(mul(A, x00), mul(B, x10));
+    const float db = mul(-2.0f, add(mul(A, x01), mul(B, x11)));
+    const float dc = -add(mul(B, x01), mul(C, x11));
+    const float da2 = mul(2.0f, da), dc2 = mul(2.0f, dc);
+    // (a, b, c) -> the covariance (off-diagonal entries: both halves) and T = J R
+    int e = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int k = r; k < 3; ++k, ++e) {
+            if (r == k)
+                o.dcov[e] = add(add(mul(da, mul(w.t0[r], w.t0[r])), mul(db, mul(w.t0[r], w.t1[r]))), mul(dc, mul(w.t1[r], w.t1[r])));
+            else
+                o.dcov[e] = add(add(mul(da2, mul(w.t0[r], w.t0[k])), mul(db, add(mul(w.t0[r], w.t1[k]), mul(w.t0[k], w.t1[r])))),
+                                mul(dc2, mul(w.t1[r], w.t1[k])));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o.dt0[k] = add(mul(da2, w.v0[k]), mul(db, w.v1[k]));
+        o.dt1[k] = add(mul(dc2, w.v1[k]), mul(db, w.v0[k]));
+    }
+    // T -> j00, j02, j11, j12
+    const float dj00 = add(add(mul(o.dt0[0], m[0]), mul(o.dt0[1], m[1])), mul(o.dt0[2], m[2]));
+    const float dj02 = add(add(mul(o.dt0[0], m[8]), mul(o.dt0[1], m[9])), mul(o.dt0[2], m[10]));
+    const float dj11 = add(add(mul(o.dt1[0], m[4]), mul(o.dt1[1], m[5])), mul(o.dt1[2], m[6]));
+    const float dj12 = add(add(mul(o.dt1[0], m[8]), mul(o.dt1[1], m[9])), mul(o.dt1[2], m[10]));
+    // j -> xc, yc, zc
+    const float dtx = -dvd(mul(dj02, cam.fx), w.zz), dty = -dvd(mul(dj12, cam.fy), w.zz);
+    const float dzz = -add(dvd(mul(dj02, w.j02), w.zz), dvd(mul(dj12, w.j12), w.zz));
+    float dzc = acc[SUM_ZC];                                                // the depth term
+    dzc = sub(dzc, dvd(mul(dj00, w.j00), w.zc));
+    dzc = sub(dzc, dvd(mul(dj11, w.j11), w.zc));
+    dzc = add(dzc, mul(mul(2.0f, w.zc), dzz));
+    dzc = add(dzc, mul(dtx, w.kx));
+    dzc = add(dzc, mul(dty, w.ky));
+    float dqx = mul(acc[SUM_U], cam.fx), dqy = mul(acc[SUM_V], cam.fy);
+    if (w.kx == w.qx) dqx = add(dqx, mul(dtx, w.zc));                       // a clamped tx passes nothing through xc / zc
+    if (w.ky == w.qy) dqy = add(dqy, mul(dty, w.zc));
+    o.dxc = dvd(dqx, w.zc); o.dyc = dvd(dqy, w.zc);
+    dzc = sub(dzc, dvd(mul(dqx, w.qx), w.zc));
+    dzc = sub(dzc, dvd(mul(dqy, w.qy), w.zc));
+    o.dzc = dzc;
+}
+
+// ------------------------------------------------------------------------------------------------ a sum over all Gaussians (§28)
+// The gradient of a view's matrices sums over every Gaussian that goes through the matrix.  A workgroup of 256 lanes owns chunk
+// blockIdx.x of 256 consecutive Gaussians in view blockIdx.y; a lane holds POSE_SUMS values g, its matrix id and whether it takes part.
+// Per id present among the lanes that take part, smallest first, the 256 values (+0.0 for a lane that holds another id or takes no
+// part) go through the tile's order (butterfly_sum, four_waves) and are stored plainly at stage[view][id][chunk]; the entry point has
+// zeroed stage (view, nmat, chunks, POSE_SUMS), so an id absent from a chunk reads as +0.0.  pose_finish then adds a (view, matrix)'s chunks.
+constexpr int POSE_SUMS = 12;
+
+struct PoseScratch {                                // LDS
+    float wsum[4 * POSE_SUMS];
+    int least[4];
+};
+
+__device__ __forceinline__ void pose_reduce_one(const float (&g)[POSE_SUMS], bool mine, float* __restrict__ out, PoseScratch& lds) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int c = 0; c < POSE_SUMS; ++c) {
+        const float r = butterfly_sum(mine ? g[c] : 0.0f);
+        if (lane == 0) lds.wsum[wave * POSE_SUMS + c] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < POSE_SUMS) {
+        const float* w = lds.wsum + threadIdx.x;
+        out[threadIdx.x] = four_waves(w[0], w[POSE_SUMS], w[2 * POSE_SUMS], w[3 * POSE_SUMS]);
+    }
+    __syncthreads();                                                        // wsum may be written again
+}
+
+// stage_view: the view's (nmat, chunks, POSE_SUMS) piece.  Every lane of the workgroup calls it.
+__device__ __forceinline__ void pose_reduce(const float (&g)[POSE_SUMS], bool takes_part, int id, int nmat, float* __restrict__ stage_view,
+                                            int64_t chunks, PoseScratch& lds) {
+    if (nmat == 1) {
+        if (__syncthreads_or(takes_part)) pose_reduce_one(g, takes_part, stage_view + (int64_t)blockIdx.x * POSE_SUMS, lds);
+        return;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int prev = -1;;) {                                                 // the ids present, ascending; absent ones are skipped
+        int cur = takes_part && id > prev ? id : 0x7fffffff;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) cur = min(cur, __shfl_xor(cur, s));
+        if (lane == 0) lds.least[wave] = cur;
+        __syncthreads();
+        cur = min(min(lds.least[0], lds.least[1]), min(lds.least[2], lds.least[3]));
+        __syncthreads();                                                    // least may be written again
+        if (cur == 0x7fffffff) return;                                      // the same for every lane
+        pose_reduce_one(g, takes_part && id == cur, stage_view + ((int64_t)cur * chunks + blockIdx.x) * POSE_SUMS, lds);
+        prev = cur;
+    }
+}
+
+// Workgroup (matrix, view): lane l adds chunks l, l + 256, ... in ascending order from +0.0, the 256 lane sums go through the tile's
+// order, and d_mats[view][matrix] is overwritten.  A template only so that the translation units that never launch it do not carry it.
+template <int N>
+__global__ __launch_bounds__(256) void pose_finish_kernel(const float* __restrict__ stage, int64_t chunks, float* __restrict__ d_mats) {
+    __shared__ float wsum[4 * N];
+    const int64_t row = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;       // view nmat + matrix
+    const float* src = stage + row * chunks * N;
+    float acc[N];
+#pragma unroll
+    for (int c = 0; c < N; ++c) acc[c] = 0.0f;
+    for (int64_t k = threadIdx.x; k < chunks; k += 256) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) acc[c] = add(acc[c], src[k * N + c]);
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        const float r = butterfly_sum(acc[c]);
+        if (lane == 0) wsum[wave * N + c] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const float* w = wsum + threadIdx.x;
+        d_mats[row * N + threadIdx.x] = four_waves(w[0], w[N], w[2 * N], w[3 * N]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ what the entry points check
 inline bool grid_ok(int64_t lanes) { return (lanes + 255) / 256 <= 0x7fffffffLL; }
 inline bool entries_ok(int64_t E) { return E >= 1 && E <= 0x7fffffffLL; }
@@ -324,4 +462,17 @@ inline int check_camera(const char* name, float fx, float fy, float cx, float cy
     MUDG_REQUIRE(std::isfinite(fx) && std::isfinite(fy) && fx > 0.0f && fy > 0.0f && std::isfinite(cx) && std::isfinite(cy),
                  "%s: intrinsics %g %g %g %g", name, (double)fx, (double)fy, (double)cx, (double)cy);
     return MUDG_OK;
+}
+
+// §28: the stage buffer of a pose gradient, (V, nmat, ceil(n / 256), POSE_SUMS) floats, cleared; then, after the caller's kernel has
+// stored the chunk sums, the finishing launch.
+__host__ __device__ inline int64_t pose_chunks(int64_t n) { return (n + 255) / 256; }
+
+inline bool pose_clear(float* stage, int64_t n, int V, int nmat, hipStream_t s) {
+    return hipMemsetAsync(stage, 0, (size_t)V * nmat * pose_chunks(n) * POSE_SUMS * sizeof(float), s) == hipSuccess;
+}
+
+template <int N = POSE_SUMS>                        // a template for the kernel's reason: instantiated where it is called
+inline void pose_finish(const float* stage, int64_t n, int V, int nmat, float* d_mats, hipStream_t s) {
+    hipLaunchKernelGGL(pose_finish_kernel<N>, dim3((unsigned)nmat, (unsigned)V), dim3(256), 0, s, stage, pose_chunks(n), d_mats);
 }

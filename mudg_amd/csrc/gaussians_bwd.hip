@@ -151,56 +151,11 @@ __global__ __launch_bounds__(256) void gauss_project_bwd_kernel(const u32x4* __r
         gc1 = add(gc1, acc[SUM_COLOUR + 1]);
         gc2 = add(gc2, acc[SUM_COLOUR + 2]);
         gop = add(gop, acc[SUM_OPACITY]);
-        const float A = dvd(w.c, w.det), B = -dvd(w.b, w.det), C = dvd(w.a, w.det);
-        // conic -> (a, b, c): with K the conic and G = [[gA, gB / 2], [gB / 2, gC]], d(a, b, c) = -(K G K) read as (00, 2 x 01, 11)
-        const float gA = acc[SUM_A], hB = mul(0.5f, acc[SUM_B]), gC = acc[SUM_C];
-        const float x00 = add(mul(gA, A), mul(hB, B)), x01 = add(mul(gA, B), mul(hB, C));
-        const float x10 = add(mul(hB, A), mul(gC, B)), x11 = add(mul(hB, B), mul(gC, C));
-        const float da = -add(mul(A, x00), mul(B, x10));
-        const float db = mul(-2.0f, add(mul(A, x01), mul(B, x11)));
-        const float dc = -add(mul(B, x01), mul(C, x11));
-        const float da2 = mul(2.0f, da), dc2 = mul(2.0f, dc);
-        // (a, b, c) -> the covariance (off-diagonal entries: both halves) and T = J R
-        int e = 0;
+        GaussViewBwd b;                                                     // the chain rule, written once (gauss_shared.h)
+        gauss_view_bwd(m, w, cam, acc, b);
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int k = r; k < 3; ++k, ++e) {
-                float g;
-                if (r == k)
-                    g = add(add(mul(da, mul(w.t0[r], w.t0[r])), mul(db, mul(w.t0[r], w.t1[r]))), mul(dc, mul(w.t1[r], w.t1[r])));
-                else
-                    g = add(add(mul(da2, mul(w.t0[r], w.t0[k])), mul(db, add(mul(w.t0[r], w.t1[k]), mul(w.t0[k], w.t1[r])))),
-                            mul(dc2, mul(w.t1[r], w.t1[k])));
-                gs[e] = add(gs[e], g);
-            }
-        }
-        float dt0[3], dt1[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            dt0[k] = add(mul(da2, w.v0[k]), mul(db, w.v1[k]));
-            dt1[k] = add(mul(dc2, w.v1[k]), mul(db, w.v0[k]));
-        }
-        // T -> j00, j02, j11, j12
-        const float dj00 = add(add(mul(dt0[0], m[0]), mul(dt0[1], m[1])), mul(dt0[2], m[2]));
-        const float dj02 = add(add(mul(dt0[0], m[8]), mul(dt0[1], m[9])), mul(dt0[2], m[10]));
-        const float dj11 = add(add(mul(dt1[0], m[4]), mul(dt1[1], m[5])), mul(dt1[2], m[6]));
-        const float dj12 = add(add(mul(dt1[0], m[8]), mul(dt1[1], m[9])), mul(dt1[2], m[10]));
-        // j -> xc, yc, zc
-        const float dtx = -dvd(mul(dj02, cam.fx), w.zz), dty = -dvd(mul(dj12, cam.fy), w.zz);
-        const float dzz = -add(dvd(mul(dj02, w.j02), w.zz), dvd(mul(dj12, w.j12), w.zz));
-        float dzc = acc[SUM_ZC];                                            // the depth term
-        dzc = sub(dzc, dvd(mul(dj00, w.j00), w.zc));
-        dzc = sub(dzc, dvd(mul(dj11, w.j11), w.zc));
-        dzc = add(dzc, mul(mul(2.0f, w.zc), dzz));
-        dzc = add(dzc, mul(dtx, w.kx));
-        dzc = add(dzc, mul(dty, w.ky));
-        float dqx = mul(acc[SUM_U], cam.fx), dqy = mul(acc[SUM_V], cam.fy);
-        if (w.kx == w.qx) dqx = add(dqx, mul(dtx, w.zc));                   // a clamped tx passes nothing through xc / zc
-        if (w.ky == w.qy) dqy = add(dqy, mul(dty, w.zc));
-        const float dxc = dvd(dqx, w.zc), dyc = dvd(dqy, w.zc);
-        dzc = sub(dzc, dvd(mul(dqx, w.qx), w.zc));
-        dzc = sub(dzc, dvd(mul(dqy, w.qy), w.zc));
+        for (int e = 0; e < 6; ++e) gs[e] = add(gs[e], b.dcov[e]);
+        const float dxc = b.dxc, dyc = b.dyc, dzc = b.dzc;
         gx = add(gx, add(add(mul(dxc, m[0]), mul(dyc, m[4])), mul(dzc, m[8])));
         gy = add(gy, add(add(mul(dxc, m[1]), mul(dyc, m[5])), mul(dzc, m[9])));
         gz = add(gz, add(add(mul(dxc, m[2]), mul(dyc, m[6])), mul(dzc, m[10])));

@@ -4,6 +4,8 @@
 //   gauss_sh_bwd     a lane owns a Gaussian and walks the views in order: the colour columns of the blend's partials (§24) summed as
 //                    gauss_project_bwd sums them, the forward recomputed bit for bit, and the gradients of colour, of the coefficients and,
 //                    through the normalisation of the direction, of the position.  Plain stores, no atomics
+//   gauss_sh_pose_bwd  a lane owns a (view, Gaussian): the same view's backward (sh_view_bwd, written once for both kernels), and what the
+//                    position's share says about the view's matrix through c = -R^T t; summed over the Gaussians as DESIGN.md §28 orders it
 // A workgroup's 256 coefficient rows are one contiguous piece of the (n, K - 1, 3) tensor.  It is fetched in whole 16-byte pieces, lane
 // after lane, and handed out through LDS with an odd row stride (a lane's row then starts on its own bank); the backward's d_sh leaves
 // the same way.  Everything is fp32, each operation a single rounded one in the order DESIGN.md §27 writes it, so both kernels are
@@ -193,6 +195,41 @@ __device__ __forceinline__ void sh_sum(const float (&B)[ShShape<L>::K], const fl
     }
 }
 
+// One view's backward: the colour gradient g of a (view, Gaussian) through the clamp (ge), the basis B at the view's direction, and dv,
+// what reaches the Gaussian's position through the normalisation of the direction.  gauss_sh_bwd adds ge, B ge and dv over the views;
+// gauss_sh_pose_bwd takes dv on to the view's matrix (§28).
+template <int L>
+struct ShViewBwd {
+    float ge[3], B[ShShape<L>::K], dv[3];
+};
+
+template <int L>
+__device__ __forceinline__ void sh_view_bwd(const float* __restrict__ m, const ShPoint& p, const float* row, int Ka,
+                                            const float* __restrict__ colour, const float (&g)[3], ShViewBwd<L>& o) {
+    constexpr int K = ShShape<L>::K;
+    const ShDir d = sh_direction(m, p);
+    float c[3], s[K];
+    sh_basis<L>(d, o.B);
+    sh_sum<L>(o.B, row, Ka, colour, c);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) o.ge[ch] = c[ch] < 0.0f ? 0.0f : g[ch];  // where the clamp cut, nothing passes
+    s[0] = 0.0f;
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+        s[k] = 0.0f;
+        if (k < Ka) {
+            const float* r = row + 3 * (k - 1);
+            s[k] = add(add(mul(o.ge[0], r[0]), mul(o.ge[1], r[1])), mul(o.ge[2], r[2]));
+        }
+    }
+    float ax, ay, az;
+    sh_basis_grad<L>(d, s, ax, ay, az);
+    const float dot = add(add(mul(d.x, ax), mul(d.y, ay)), mul(d.z, az));
+    o.dv[0] = dvd(sub(ax, mul(d.x, dot)), d.len);
+    o.dv[1] = dvd(sub(ay, mul(d.y, dot)), d.len);
+    o.dv[2] = dvd(sub(az, mul(d.z, dot)), d.len);
+}
+
 // ------------------------------------------------------------------------------------------------ the kernels
 // grid: (workgroups of 256 Gaussians, views).  A workgroup none of whose Gaussians the view draws reads no coefficients.
 template <int L>
@@ -244,32 +281,20 @@ __global__ __launch_bounds__(256) void gauss_sh_bwd_kernel(const u32x4* __restri
         const ShPoint p = sh_point(pts, ids, nmat, idx);
         int view = 0;
         const auto chain = [&](const float (&g)[3]) {                      // the view's colour gradient through the rule
-            const ShDir d = sh_direction(mats + ((int64_t)view * nmat + p.id) * 12, p);
-            float B[K], c[3], ge[3], s[K];
-            sh_basis<L>(d, B);
-            sh_sum<L>(B, row, Ka, colour + 3 * idx, c);
+            ShViewBwd<L> b;
+            sh_view_bwd<L>(mats + ((int64_t)view * nmat + p.id) * 12, p, row, Ka, colour + 3 * idx, g, b);
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                ge[ch] = c[ch] < 0.0f ? 0.0f : g[ch];                       // where the clamp cut, nothing passes
-                gc[ch] = add(gc[ch], ge[ch]);
-            }
-            s[0] = 0.0f;
+            for (int ch = 0; ch < 3; ++ch) gc[ch] = add(gc[ch], b.ge[ch]);
 #pragma unroll
             for (int k = 1; k < K; ++k) {
-                s[k] = 0.0f;
                 if (k < Ka) {
-                    const float* r = row + 3 * (k - 1);
-                    s[k] = add(add(mul(ge[0], r[0]), mul(ge[1], r[1])), mul(ge[2], r[2]));
 #pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) gsh[3 * (k - 1) + ch] = add(gsh[3 * (k - 1) + ch], mul(B[k], ge[ch]));
+                    for (int ch = 0; ch < 3; ++ch) gsh[3 * (k - 1) + ch] = add(gsh[3 * (k - 1) + ch], mul(b.B[k], b.ge[ch]));
                 }
             }
-            float ax, ay, az;
-            sh_basis_grad<L>(d, s, ax, ay, az);
-            const float dot = add(add(mul(d.x, ax), mul(d.y, ay)), mul(d.z, az));
-            gx = add(gx, dvd(sub(ax, mul(d.x, dot)), d.len));
-            gy = add(gy, dvd(sub(ay, mul(d.y, dot)), d.len));
-            gz = add(gz, dvd(sub(az, mul(d.z, dot)), d.len));
+            gx = add(gx, b.dv[0]);
+            gy = add(gy, b.dv[1]);
+            gz = add(gz, b.dv[2]);
         };
         for (; view < V; ++view) with_partials<SUM_COLOUR, 3>(partial, count, offsets, (int64_t)view * n + idx, E, chain);
     }
@@ -281,6 +306,42 @@ __global__ __launch_bounds__(256) void gauss_sh_bwd_kernel(const u32x4* __restri
         d_colour[3 * idx] = gc[0]; d_colour[3 * idx + 1] = gc[1]; d_colour[3 * idx + 2] = gc[2];
         d_xyz[3 * idx] = gx; d_xyz[3 * idx + 1] = gy; d_xyz[3 * idx + 2] = gz;
     }
+}
+
+// §28: what the direction says about the view's matrices.  grid: (chunks of 256 Gaussians, views), a lane per (view, Gaussian); the
+// coefficients staged as above, the twelve values reduced per matrix id as gauss_pose_bwd reduces its own (pose_reduce).
+template <int L>
+__global__ __launch_bounds__(256) void gauss_sh_pose_bwd_kernel(const u32x4* __restrict__ pts, const int32_t* __restrict__ ids,
+                                                                 const float* __restrict__ mats, int64_t n, int nmat,
+                                                                 const int32_t* __restrict__ count, const int64_t* __restrict__ offsets,
+                                                                 const float* __restrict__ partial, int64_t E, const float* __restrict__ colour,
+                                                                 const float* __restrict__ sh, int active, float* __restrict__ stage) {
+    __shared__ __attribute__((aligned(16))) float rows[256 * ShShape<L>::PAD];
+    __shared__ PoseScratch lds;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, view = blockIdx.y;
+    const bool live = idx < n;
+    float g[POSE_SUMS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    bool drawn = false;
+    int id = 0;
+    if (!__syncthreads_or(live && count[view * n + idx] > 0)) return;       // the same for every lane: stage keeps the entry point's zeros
+    stage_rows<L>(sh, n, rows);
+    if (live) {
+        with_partials<SUM_COLOUR, 3>(partial, count, offsets, view * n + idx, E, [&](const float (&up)[3]) {
+            const ShPoint p = sh_point(pts, ids, nmat, idx);
+            const float* m = mats + (view * nmat + p.id) * 12;
+            ShViewBwd<L> b;
+            sh_view_bwd<L>(m, p, rows + threadIdx.x * ShShape<L>::PAD, (active + 1) * (active + 1), colour + 3 * idx, up, b);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) g[4 * r + k] = mul(b.dv[k], m[4 * r + 3]);
+                g[4 * r + 3] = add(add(mul(b.dv[0], m[4 * r]), mul(b.dv[1], m[4 * r + 1])), mul(b.dv[2], m[4 * r + 2]));
+            }
+            id = p.id;
+            drawn = true;
+        });
+    }
+    pose_reduce(g, drawn, id, nmat, stage + view * nmat * pose_chunks(n) * POSE_SUMS, pose_chunks(n), lds);
 }
 
 int check_sh(const char* name, int64_t n, int V, int nmat, const int32_t* ids, int degree, int active) {
@@ -332,4 +393,30 @@ extern "C" int mudg_gauss_sh_bwd(const void* points, const int32_t* ids, int64_t
         hipLaunchKernelGGL(gauss_sh_bwd_kernel<3>, grid, dim3(256), 0, s, pts, ids, mats, n, V, nmat, count, offsets, partial, E, colour, sh, active,
                            d_colour, d_sh, d_xyz_dir);
     return mudg_check_launch("mudg_gauss_sh_bwd");
+}
+
+extern "C" int mudg_gauss_sh_pose_bwd(const void* points, const int32_t* ids, int64_t n, const float* mats, int V, int nmat, const int32_t* count,
+                                      const int64_t* offsets, const float* partial, int64_t E, const float* colour, const float* sh, int degree,
+                                      int active, float* stage, float* d_mats_dir, void* stream) {
+    MUDG_REQUIRE(points && mats && count && offsets && partial && colour && sh && stage && d_mats_dir, "mudg_gauss_sh_pose_bwd: null argument");
+    MUDG_REQUIRE(aligned16(points) && aligned16(sh), "mudg_gauss_sh_pose_bwd: unaligned points or coefficients");
+    MUDG_REQUIRE(aligned8(offsets), "mudg_gauss_sh_pose_bwd: unaligned offsets");
+    if (const int e = check_sh("mudg_gauss_sh_pose_bwd", n, V, nmat, ids, degree, active)) return e;
+    MUDG_REQUIRE(V <= 65535, "mudg_gauss_sh_pose_bwd: %d views (the grid's second axis holds 65535)", V);
+    MUDG_REQUIRE(entries_ok(E), "mudg_gauss_sh_pose_bwd: %lld entries (1 .. 2^31 - 1)", (long long)E);
+    const dim3 grid((unsigned)pose_chunks(n), (unsigned)V);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const u32x4* pts = reinterpret_cast<const u32x4*>(points);
+    if (!pose_clear(stage, n, V, nmat, s)) return mudg_check_launch("mudg_gauss_sh_pose_bwd");
+    if (degree == 1)
+        hipLaunchKernelGGL(gauss_sh_pose_bwd_kernel<1>, grid, dim3(256), 0, s, pts, ids, mats, n, nmat, count, offsets, partial, E, colour, sh, active,
+                           stage);
+    else if (degree == 2)
+        hipLaunchKernelGGL(gauss_sh_pose_bwd_kernel<2>, grid, dim3(256), 0, s, pts, ids, mats, n, nmat, count, offsets, partial, E, colour, sh, active,
+                           stage);
+    else
+        hipLaunchKernelGGL(gauss_sh_pose_bwd_kernel<3>, grid, dim3(256), 0, s, pts, ids, mats, n, nmat, count, offsets, partial, E, colour, sh, active,
+                           stage);
+    pose_finish(stage, n, V, nmat, d_mats_dir, s);
+    return mudg_check_launch("mudg_gauss_sh_pose_bwd");
 }

@@ -10,7 +10,8 @@ seen from.  `render` is the inference path; `render_differentiable`, `GaussianMo
 covariance, opacity and colour (with `sh_degree` also the harmonics) against images through the backward kernels of
 csrc/gaussians_bwd.hip; `DensityControl`, `DensityStats` and `densify_and_prune` let a
 fit clone, split and prune its Gaussians through csrc/gaussians_density.hip; `image_loss` is 3DGS's L1 + D-SSIM loss with
-its backward in csrc/gaussians_loss.hip, which `fit(..., ssim_weight=0.2)` minimises.  There is no CPU path: tensors that are not on the GPU are
+its backward in csrc/gaussians_loss.hip, which `fit(..., ssim_weight=0.2)` minimises; `render_differentiable` also differentiates its
+matrices (csrc/gaussians_pose.hip), and `CameraPoses` with `fit(..., poses=)` refines the cameras.  There is no CPU path: tensors that are not on the GPU are
 an error.
 """
 from __future__ import annotations
@@ -270,6 +271,7 @@ class _Render(torch.autograd.Function):
         cov, opacity, colour = cov.detach().contiguous(), opacity.detach().contiguous(), colour.detach().contiguous()
         b = _bin("render_differentiable", pts, cov, opacity, mats, cams, (h, w), ids, znear, zfar, max_entries)
         ctx.meta = (cams, (h, w), ids, znear, zfar, b.entries)
+        ctx.mats_shape = tuple(mats.shape)
         if b.entries == 0:
             ctx.save_for_backward(xyz, *(() if sh is None else (sh,)))
             return _blank(mats.shape[0], h, w, xyz.device)
@@ -291,7 +293,8 @@ class _Render(torch.autograd.Function):
             n, dev = ctx.saved_tensors[0].shape[0], ctx.saved_tensors[0].device
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
             tail = (torch.zeros_like(ctx.saved_tensors[1]), None) if len(ctx.saved_tensors) > 1 else ()
-            return (z(n, 3), z(n, 3), z(n, 6), z(n)) + (None,) * 8 + tail
+            d_mats = z(*ctx.mats_shape) if ctx.needs_input_grad[4] else None
+            return (z(n, 3), z(n, 3), z(n, 6), z(n), d_mats) + (None,) * 7 + tail
         pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state = ctx.saved_tensors[:13]
         sh, colours = ctx.saved_tensors[13:] if len(ctx.saved_tensors) > 13 else (None, None)
         views, (h, w) = mats.shape[0], hw
@@ -304,21 +307,28 @@ class _Render(torch.autograd.Function):
         d_xyz, d_cov, d_opacity, d_colour = ops.gauss_project_bwd(pts, cov, mats, cams, hw, count, offsets, partial, ids=ids, znear=znear,
                                                                   zfar=zfar)
         tail = ()                                                           # as many gradients as forward was given arguments
+        d_mats = None                                                       # §28: only when the matrices ask; else nothing is launched
+        if ctx.needs_input_grad[4]:
+            d_mats = ops.gauss_pose_bwd(pts, cov, mats, cams, hw, count, offsets, partial, ids=ids, znear=znear, zfar=zfar)
         if sh is not None:                                                  # §27: the colour columns again, through the harmonics
             d_colour, d_sh, d_xyz_dir = ops.gauss_sh_bwd(pts, mats, count, offsets, partial, colour, sh, ids=ids, active=ctx.sh_degree)
             d_xyz = d_xyz + d_xyz_dir
             tail = (d_sh, None)
+            if d_mats is not None:
+                d_mats = d_mats + ops.gauss_sh_pose_bwd(pts, mats, count, offsets, partial, colour, sh, ids=ids, active=ctx.sh_degree)
         if ctx.density is not None:                                         # §25: a second pass over the partials' columns 8 and 9
             ops.gauss_density_accumulate(partial, count, offsets, hw, ctx.density.grad_sum, ctx.density.seen)
-        return (d_xyz, d_colour, d_cov, d_opacity) + (None,) * 8 + tail
+        return (d_xyz, d_colour, d_cov, d_opacity, d_mats) + (None,) * 7 + tail
 
 
 def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES,
                           density=None, sh=None, sh_degree=None):
     """`render` with gradients.  xyz (n, 3), colour (n, 3) in byte units (0 .. 255, not necessarily whole), cov (n, 6) and
     opacity (n,): fp32 on the GPU; mats, cams, hw and ids as `render` takes them.  Returns (rgb (V, 3, H, W), depth (V, H, W), alpha
-    (V, H, W)); backward gives gradients for the first four arguments, none for the matrices or the camera.  One host synchronisation reads
-    the entry count.  density: a DensityStats of n Gaussians; backward then adds every Gaussian's screen-space gradient norm and the
+    (V, H, W)); backward gives gradients for the first four arguments and, when `mats` requires one, for the matrices (DESIGN.md §28:
+    d_mats (V, nmat, 12), the sum over every Gaussian that goes through a matrix in one fixed order, two more launches and with harmonics
+    four; zeros when nothing was drawn); none for the camera.  With matrices that do not require a gradient nothing else happens: the same
+    launches, the same bits.  One host synchronisation reads the entry count.  density: a DensityStats of n Gaussians; backward then adds every Gaussian's screen-space gradient norm and the
     views that counted it.  With None nothing else happens: the same launches, the same bits.  sh: (n, K - 1, 3) fp32
     coefficients in byte units of the harmonics of degrees 1 .. L, K = (L + 1)^2, L = 1, 2 or 3: `colour` is then the
     direction-independent term, every (view, Gaussian) gets max(0, colour + sum B_k(d) sh[k - 1]), backward also gives the gradient of sh
@@ -355,9 +365,92 @@ def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None
     return _Render.apply(*args, sh, active)
 
 
+# ------------------------------------------------------------------------------------------------ camera poses that move (§28)
+SMALL_ANGLE = 1e-2               # below this |omega| Rodrigues' coefficients come from their series (the next term is below 1e-11 of them)
+
+
+def rodrigues(omega):
+    """(V, 3) rotation vectors -> (V, 3, 3) rotations exp([omega]x) = I + a K + b K^2 with a = sin(t) / t and b = (1 - cos(t)) / t^2, t =
+    |omega|; below SMALL_ANGLE a and b come from their series in t^2, which are also differentiable at zero.  In torch, in omega's dtype."""
+    t2 = (omega * omega).sum(1)
+    small = t2 < SMALL_ANGLE ** 2
+    t = torch.sqrt(torch.where(small, torch.ones_like(t2), t2))            # the branch not taken stays finite, and so does its gradient
+    a = torch.where(small, 1 - t2 / 6 + t2 * t2 / 120, torch.sin(t) / t)
+    b = torch.where(small, 0.5 - t2 / 24 + t2 * t2 / 720, (1 - torch.cos(t)) / (t * t))
+    x, y, z = omega.unbind(1)
+    zero = torch.zeros_like(x)
+    k = torch.stack([zero, -z, y, z, zero, -x, -y, x, zero], dim=1).reshape(-1, 3, 3)
+    eye = torch.eye(3, dtype=omega.dtype, device=omega.device)
+    kk = omega[:, :, None] * omega[:, None, :] - t2[:, None, None] * eye    # K^2 = omega omega^T - |omega|^2 I: elementwise, no BLAS call
+    return eye + a[:, None, None] * k + b[:, None, None] * kk
+
+
+class CameraPoses:
+    """A correction to the camera poses of `views` views that an optimiser moves: one leaf `twist` (V, 6) fp32 = (omega,
+    tau) per view, zero at the start.  apply(mats) returns [R(omega_v) | tau_v] o mats[v][o] for every matrix o of view v: a rotation
+    (Rodrigues' formula) and a translation applied on the left, in the camera's frame, so that a view's background and object matrices
+    move together.  It is torch, so autograd carries render_differentiable's d_mats to `twist`.  The views in `fixed` get the identity
+    and no gradient: with Gaussians that move too, one fixed view is the gauge.  The translation is not coupled to the rotation as a
+    proper SE(3) exponential would couple it."""
+
+    def __init__(self, views, *, fixed=(), device="cuda"):
+        self.views = int(views)
+        self.fixed = tuple(sorted({int(v) for v in fixed}))
+        if self.views <= 0 or any(not 0 <= v < self.views for v in self.fixed):
+            raise hip.MudgError(f"CameraPoses: {self.views} views with {self.fixed} fixed (views > 0, fixed views among them)")
+        self.twist = torch.zeros((self.views, 6), dtype=torch.float32, device=device).requires_grad_(True)
+        free = torch.ones((self.views, 1), dtype=torch.float32, device=device)
+        free[list(self.fixed)] = 0.0
+        self._free = free
+
+    def __len__(self):
+        return self.views
+
+    def apply(self, mats, pick=None):
+        """mats (P, nmat, 12) fp32 on the twist's device, view pick[k] (default: k, and then P = V) behind mats[k] -> the corrected (P,
+        nmat, 12).  A zero twist returns the same values: R is exactly the identity and the products with its zeros vanish (the one bit
+        that can change is the sign of a matrix entry that is -0.0, which comes back +0.0)."""
+        if not torch.is_tensor(mats) or mats.dtype != torch.float32 or mats.dim() != 3 or mats.shape[2] != 12:
+            raise hip.MudgError("CameraPoses.apply: the matrices are a (P, nmat, 12) fp32 tensor")
+        twist = self.twist * self._free                                     # a fixed view: exactly zero, and no gradient
+        if pick is not None:
+            twist = twist[torch.as_tensor(pick, device=twist.device).long()]
+        if twist.shape[0] != mats.shape[0]:
+            raise hip.MudgError(f"CameraPoses.apply: {mats.shape[0]} views of matrices for {twist.shape[0]} poses")
+        m = mats.reshape(mats.shape[0], mats.shape[1], 3, 4)
+        out = (rodrigues(twist[:, :3])[:, None, :, :, None] * m[:, :, None, :, :]).sum(3)      # R m, elementwise: no BLAS, one order
+        out = torch.cat([out[..., :3], out[..., 3:] + twist[:, None, 3:, None]], dim=-1)
+        return out.reshape(mats.shape)
+
+    def _corrections(self):
+        """(V, 4, 4) float64 on the host."""
+        with torch.no_grad():
+            twist = (self.twist * self._free).detach().to("cpu", torch.float64)
+            c = torch.eye(4, dtype=torch.float64).repeat(self.views, 1, 1)
+            c[:, :3, :3] = rodrigues(twist[:, :3])
+            c[:, :3, 3] = twist[:, 3:]
+        return c.numpy()
+
+    def world_to_camera(self, w2c):
+        """(V, 4, 4) world-to-camera matrices -> the corrected ones, float64 on the host."""
+        w2c = np.asarray(w2c, dtype=np.float64)
+        if w2c.shape != (self.views, 4, 4):
+            raise hip.MudgError(f"CameraPoses.world_to_camera: expected ({self.views}, 4, 4), got {w2c.shape}")
+        return self._corrections() @ w2c
+
+    def camera_to_world(self, c2w):
+        """(V, 4, 4) camera-to-world matrices -> the corrected ones, float64 on the host: what render_scene takes as poses."""
+        c2w = np.asarray(c2w, dtype=np.float64)
+        if c2w.shape != (self.views, 4, 4):
+            raise hip.MudgError(f"CameraPoses.camera_to_world: expected ({self.views}, 4, 4), got {c2w.shape}")
+        return c2w @ np.linalg.inv(self._corrections())
+
+
 PARAMETERS = ("xyz", "colour", "log_scale", "quat", "opacity_logit")
 LEARNING_RATES = {"xyz": 2e-3, "colour": 2.0, "log_scale": 5e-3, "quat": 1e-3, "opacity_logit": 5e-2}      # metres, bytes, log metres, -, logits
 LEARNING_RATES["sh"] = LEARNING_RATES["colour"] / 20       # bytes; 3DGS's ratio of the two rates, not tuned here (DESIGN.md §27)
+POSE_LEARNING_RATE = 1e-3                                  # radians and metres of a CameraPoses twist; not tuned here (DESIGN.md §28).  Beside
+#                                                            LEARNING_RATES, not in it: that table is the model's leaves, and the twist is not one
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-15
 MAX_SEED_OPACITY = 0.999                       # a seed opacity of 1 would be an infinite logit
 
@@ -646,7 +739,8 @@ image_loss.terms = _image_loss_terms
 
 
 def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_per_step=None, depth_targets=None, depth_weight=0.0,
-        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None, ssim_weight=0.0, sh_degree=0, sh_raise_every=None):
+        trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None, ssim_weight=0.0, sh_degree=0, sh_raise_every=None,
+        poses=None):
     """Optimise `model` in place against targets (V, 3, H, W) fp32 in [0, 1] seen through mats (V, nmat, 12) and cams.
     Iteration i renders the views_per_step (default: all) views (i views_per_step + k) mod V, takes the mean absolute difference of rgb,
     adds depth_weight times the mean absolute depth difference over the pixels where depth_targets (V, H, W) is positive, and takes one
@@ -663,7 +757,11 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
     other parameters at its own rate LEARNING_RATES["sh"] (lr may name it), density control carries its rows and moments as it carries
     colour's, and model.gaussians() hands the coefficients to render.  The active degree starts at 0 and rises by one every
     sh_raise_every iterations until it is L; None: all degrees from the first iteration.  With sh_degree=0 (the default) nothing changes,
-    bit for bit, and a model that has harmonics is refused.  No pose gradient.  Returns the loss of every iteration."""
+    bit for bit, and a model that has harmonics is refused.  poses: a CameraPoses of V views or None.  With one, every
+    iteration renders through poses.apply(mats[pick], pick), the matrices' gradient reaches poses.twist, and the twist is one more tensor
+    of the Adam step at POSE_LEARNING_RATE (lr may name "pose"; the rate is not tuned); trainable=() is then allowed and is pure
+    registration against fixed Gaussians; density control does not touch the twist.  With None nothing changes, bit for bit.  Returns the
+    loss of every iteration."""
     from .train import kernels as K
     if not isinstance(model, GaussianModel):
         raise hip.MudgError("fit: expected a GaussianModel")
@@ -684,14 +782,19 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
         raise hip.MudgError(f"fit: sh_degree {sh_degree} is 0 .. {ops.GAUSS_SH_MAX_DEGREE} and sh_raise_every {sh_raise_every} positive or None")
     if model.sh_degree != sh_degree and (sh_degree == 0 or model.sh is not None):
         raise hip.MudgError(f"fit: sh_degree {sh_degree} for a model with harmonics of degree {model.sh_degree}")
-    known = PARAMETERS + ("sh",)
-    rates = dict(LEARNING_RATES, **(lr or {}))
+    if poses is not None and (not isinstance(poses, CameraPoses) or len(poses) != views or poses.twist.device != mats.device):
+        raise hip.MudgError(f"fit: poses is a CameraPoses of {views} views on the matrices' device, or None")
+    known = PARAMETERS + ("sh", "pose")
+    rates = {**LEARNING_RATES, "pose": POSE_LEARNING_RATE, **(lr or {})}
     names = [n for n in PARAMETERS if n in tuple(trainable)]
-    if not names or set(trainable) - set(known) or set(rates) - set(known) or int(iters) < 0:
+    if (not names and poses is None) or "pose" in tuple(trainable) or set(trainable) - set(known) or set(rates) - set(known) or int(iters) < 0:
         raise hip.MudgError(f"fit: trainable and lr name parameters among {PARAMETERS}, got {tuple(trainable)} and {tuple(rates)}")
     if sh_degree:
         model.enable_sh(sh_degree)
         names.append("sh")
+    if poses is not None:
+        names.append("pose")
+    leaf = lambda n: poses.twist if n == "pose" else getattr(model, n)
     per = views if views_per_step is None else int(views_per_step)
     if not 1 <= per <= views:
         raise hip.MudgError(f"fit: {per} views per step of {views}")
@@ -699,7 +802,7 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
 
     def bind():
         """The optimiser's view of the model's leaves: again after every step that replaced them (their addresses changed)."""
-        params = [getattr(model, n) for n in names]
+        params = [leaf(n) for n in names]
         grads = [torch.zeros_like(p) for p in params]
         for n, p in zip(names, params):
             if n not in moments:
@@ -721,7 +824,8 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
         harmonics = {}
         if sh_degree:                                                       # §27: the active degree rises by one every sh_raise_every
             harmonics = dict(sh=model.sh, sh_degree=sh_degree if sh_raise_every is None else min(sh_degree, it // int(sh_raise_every)))
-        rgb, depth, _ = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(), mats[pick], cams, (h, w),
+        rgb, depth, _ = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(),
+                                              mats[pick] if poses is None else poses.apply(mats[pick], pick), cams, (h, w),
                                               ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries,
                                               density=stats if gathers else None, **harmonics)
         with_depth = depth_targets is not None and bool(depth_weight)

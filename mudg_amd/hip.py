@@ -199,6 +199,8 @@ SIGNATURES = {
     "mudg_gauss_project_bwd": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P, _L, _P, _P, _P, _P, _P]),
     "mudg_gauss_sh_colour": (_I, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
     "mudg_gauss_sh_bwd": (_I, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "mudg_gauss_pose_bwd": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P, _L, _P, _P, _P]),
+    "mudg_gauss_sh_pose_bwd": (_I, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _L, _P, _P, _I, _I, _P, _P, _P]),
     "mudg_gauss_blend_views": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P]),
     "mudg_gauss_blend_train_views": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mudg_gauss_blend_bwd_views": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

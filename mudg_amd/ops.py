@@ -1127,6 +1127,53 @@ def gauss_sh_bwd(points, mats, count, offsets, partial, colour, sh, *, ids=None,
     return d_colour, d_sh, d_xyz
 
 
+GAUSS_POSE_CHUNK = 256           # Gaussians a workgroup of the pose gradient reduces
+GAUSS_POSE_MAX_VIEWS = 65535     # the grid's second axis
+
+
+def _gauss_pose_buffers(name, n, v, nmat, device):
+    """The stage buffer (V, nmat, ceil(n / 256), 12) and d_mats (V, nmat, 12) of a pose gradient; more views than a grid holds are refused."""
+    if v > GAUSS_POSE_MAX_VIEWS:
+        raise hip.MudgError(f"{name}: {v} views (at most {GAUSS_POSE_MAX_VIEWS} a call)")
+    chunks = (n + GAUSS_POSE_CHUNK - 1) // GAUSS_POSE_CHUNK
+    return (torch.empty((v, nmat, chunks, 12), dtype=torch.float32, device=device),
+            torch.empty((v, nmat, 12), dtype=torch.float32, device=device))
+
+
+def gauss_pose_bwd(points, cov, mats, intr, hw, count, offsets, partial, *, ids=None, znear=0.2, zfar=200.0):
+    """The gradient of the matrices: d_mats (V, nmat, 12) fp32 from the operands of gauss_project_bwd, the sum over every
+    Gaussian that goes through a (view, matrix) in one fixed order; +0 for a matrix nobody goes through.  Without harmonics this is the
+    whole gradient; with them gauss_sh_pose_bwd's tensor is added."""
+    n, v, nmat = _gauss_cloud("gauss_pose_bwd", points, cov, mats, ids)
+    if ids is None and nmat != 1:
+        raise hip.MudgError(f"gauss_pose_bwd: {nmat} matrices per view need ids")
+    _splat_tensor("gauss_pose_bwd: count", count, torch.int32, (v, n))
+    _splat_tensor("gauss_pose_bwd: offsets", offsets, torch.int64, (v, n))
+    _gauss_partial("gauss_pose_bwd", partial)
+    h, w = (int(s) for s in hw)
+    fx, fy, cx, cy = (float(s) for s in intr)
+    stage, d_mats = _gauss_pose_buffers("gauss_pose_bwd", n, v, nmat, points.device)
+    hip.check(hip.lib().mudg_gauss_pose_bwd(points.data_ptr(), cov.data_ptr(), _ptr(ids), n, mats.data_ptr(), v, nmat, h, w, fx, fy, cx, cy,
+                                            float(znear), float(zfar), count.data_ptr(), offsets.data_ptr(), partial.data_ptr(),
+                                            partial.shape[0], stage.data_ptr(), d_mats.data_ptr(), _stream()), "mudg_gauss_pose_bwd")
+    return d_mats
+
+
+def gauss_sh_pose_bwd(points, mats, count, offsets, partial, colour, sh, *, ids=None, active=None):
+    """What reaches the matrices through the harmonics' direction: d_mats_dir (V, nmat, 12) fp32 from the operands of
+    gauss_sh_bwd, summed as gauss_pose_bwd sums."""
+    n, v, nmat, degree, active = _gauss_sh("gauss_sh_pose_bwd", points, mats, ids, count, colour, sh, active)
+    if ids is None and nmat != 1:
+        raise hip.MudgError(f"gauss_sh_pose_bwd: {nmat} matrices per view need ids")
+    _splat_tensor("gauss_sh_pose_bwd: offsets", offsets, torch.int64, (v, n))
+    _gauss_partial("gauss_sh_pose_bwd", partial)
+    stage, d_mats = _gauss_pose_buffers("gauss_sh_pose_bwd", n, v, nmat, points.device)
+    hip.check(hip.lib().mudg_gauss_sh_pose_bwd(points.data_ptr(), _ptr(ids), n, mats.data_ptr(), v, nmat, count.data_ptr(), offsets.data_ptr(),
+                                               partial.data_ptr(), partial.shape[0], colour.data_ptr(), sh.data_ptr(), degree, active,
+                                               stage.data_ptr(), d_mats.data_ptr(), _stream()), "mudg_gauss_sh_pose_bwd")
+    return d_mats
+
+
 def _gauss_entries_views(name, colours, uv, conic, depth, values_sorted, ranges, hw):
     """_gauss_entries for colours (V, n, 3): every view's slice is an (n, 3) colour tensor."""
     _splat_tensor(f"{name}: colours", colours, torch.float32)

@@ -242,7 +242,9 @@ def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, **k
     mudg_amd.gaussians.DensityControl: the fit then clones, splits and prunes Gaussians, DESIGN.md §25, so that the result need not have
     the cloud's size; ssim_weight, default 0: above it the fit minimises mudg_amd.gaussians.image_loss, L1 + D-SSIM, DESIGN.md §26, and
     3DGS's value is 0.2; sh_degree, default 0, and sh_raise_every: with L = 1, 2 or 3 every Gaussian also learns spherical harmonics of
-    degrees 1 .. L, DESIGN.md §27, so that its colour may differ between the poses a fit sees).  Returns the fitted
+    degrees 1 .. L, DESIGN.md §27, so that its colour may differ between the poses a fit sees; poses, default None: a mudg_amd.gaussians.CameraPoses
+    of t views, one per frame, whose twist the fit then moves with the Gaussians, DESIGN.md §28, because a scenario's camera poses and
+    tracked boxes carry calibration and tracking error; its world_to_camera gives the corrected cameras afterwards).  Returns the fitted
     mudg_amd.gaussians.Gaussians, which render, render_scene and the renderer of render_cloud_views draw; one fitted with harmonics
     carries them, and its colour then depends on the pose it is drawn at."""
     import numpy as np
