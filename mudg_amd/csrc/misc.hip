@@ -1,6 +1,6 @@
 // misc.hip — the small kernels around the UNet: sinusoidal embeddings, the tiny fp32 MLPs on them, the
 // (b c t h w) <-> channels-last conversions at the API boundary and the fused DDIM update.
-#include "common.h"
+#include "rows_shared.h"
 
 namespace {
 
@@ -56,12 +56,6 @@ __global__ void ncthw_to_rows_kernel(const ST* __restrict__ src, h16* __restrict
         store1_operand(dst + i * ld + coff + c, ld / PLANES, (float)src[(((int64_t)b * C + c) * Ttot + t0 + t) * HW + p]);
 }
 
-// A rows-matrix element as fp32: operand storage (PLANES pieces) or plain fp32.
-__device__ __forceinline__ float row_value(const h16* p, int ld) { return load1_operand(p, ld / PLANES); }
-__device__ __forceinline__ float row_value(const float* p, int) { return *p; }
-struct StreamH { _Float16 v; };       // fp16 residual-stream storage (KIND_F16); a type of its own since h16 may be _Float16 too
-__device__ __forceinline__ float row_value(const StreamH* p, int) { return (float)p->v; }
-
 template <typename ST, typename DT>
 __global__ void rows_to_ncthw_kernel(const ST* __restrict__ src, int ld, int coff, DT* __restrict__ dst, int B, int C,
                                      int T, int HW, float scale, int Ttot, int t0) {
@@ -72,7 +66,7 @@ __global__ void rows_to_ncthw_kernel(const ST* __restrict__ src, int ld, int cof
     const int64_t bt = i / HW;
     const int t = (int)(bt % T), b = (int)(bt / T);
     for (int c = 0; c < C; ++c)
-        dst[(((int64_t)b * C + c) * Ttot + t0 + t) * HW + p] = (DT)(row_value(src + i * ld + coff + c, ld) * scale);
+        dst[(((int64_t)b * C + c) * Ttot + t0 + t) * HW + p] = (DT)(Kind<ST>::load1(src + i * ld + coff + c, ld) * scale);
 }
 
 __global__ void zero_channels_kernel(h16* __restrict__ dst, int64_t rows, int ld, int c0, int c1) {
@@ -101,31 +95,7 @@ __global__ void copy_rows_kernel(const h16* __restrict__ src, int64_t lds, h16* 
 }
 
 // dst[r][c] = src[r][c] between rows matrices of any storage kind, any direction.  VEC: 8 consecutive columns per thread
-// with 16-byte accesses (cols, both row strides and both bases 8-element aligned).
-template <typename T> struct Row8;
-template <> struct Row8<h16> {
-    static __device__ __forceinline__ void get(const h16* p, int64_t ld, float (&v)[8]) { load8_operand(p, ld / PLANES, v); }
-    static __device__ __forceinline__ void put(h16* p, int64_t ld, const float (&v)[8]) { store8_operand(p, ld / PLANES, v); }
-};
-template <> struct Row8<float> {
-    static __device__ __forceinline__ void get(const float* p, int64_t, float (&v)[8]) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
-    }
-    static __device__ __forceinline__ void put(float* p, int64_t, const float (&v)[8]) {
-        f32x4 a, b;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { a[e] = v[e]; b[e] = v[4 + e]; }
-        *reinterpret_cast<f32x4*>(p) = a;
-        *reinterpret_cast<f32x4*>(p + 4) = b;
-    }
-};
-template <> struct Row8<StreamH> {
-    static __device__ __forceinline__ void get(const StreamH* p, int64_t, float (&v)[8]) { load8_f16(reinterpret_cast<const _Float16*>(p), v); }
-    static __device__ __forceinline__ void put(StreamH* p, int64_t, const float (&v)[8]) { store8_f16(reinterpret_cast<_Float16*>(p), v); }
-};
-
+// with 16-byte accesses (cols, both row strides and both bases 8-element aligned).  The storage kinds: Kind<T>, rows_shared.h.
 template <typename ST, typename DT, bool VEC>
 __global__ void cast_rows_kernel(const ST* __restrict__ src, int64_t lds, DT* __restrict__ dst, int64_t ldd, int64_t rows,
                                  int64_t cols) {
@@ -135,15 +105,12 @@ __global__ void cast_rows_kernel(const ST* __restrict__ src, int64_t lds, DT* __
         if (i >= rows * cv) return;
         const int64_t r = i / cv, c = (i - r * cv) << 3;
         float v[8];
-        Row8<ST>::get(src + r * lds + c, lds, v);
-        Row8<DT>::put(dst + r * ldd + c, ldd, v);
+        Kind<ST>::get(src + r * lds + c, lds, v);
+        Kind<DT>::put(dst + r * ldd + c, ldd, v);
     } else {
         if (i >= rows * cols) return;
         const int64_t r = i / cols, c = i - r * cols;
-        const float v = row_value(src + r * lds + c, (int)lds);
-        if constexpr (sizeof(DT) == 4) dst[r * ldd + c] = v;
-        else if constexpr (__is_same(DT, StreamH)) dst[r * ldd + c].v = f16_sat(v);
-        else store1_operand(dst + r * ldd + c, ldd / PLANES, v);
+        Kind<DT>::store1(dst + r * ldd + c, ldd, Kind<ST>::load1(src + r * lds + c, (int)lds));
     }
 }
 
@@ -214,7 +181,7 @@ __global__ __launch_bounds__(256) void ddim_stats_kernel(const float* __restrict
     if (lane == 0) { red[wave][0] = sc; red[wave][1] = qc; red[wave][2] = sv; red[wave][3] = qv; }
     __syncthreads();
     if (tid < 4)
-        ws[((int64_t)b * DDIM_BLK + blockIdx.x) * 4 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+        ws[((int64_t)b * DDIM_BLK + blockIdx.x) * 4 + tid] = fold4(red, tid);
 }
 
 struct DdimCoef { float cfg, phi, sqrt_ac, sqrt_1mac, rescale, sqrt_a_prev, dir_coef, sigma, cfg_img, eps_form; };
@@ -317,16 +284,11 @@ extern "C" int mudg_rows_to_ncthw(const void* src, int src_is_fp32, int ld, int 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t n = (int64_t)B * T * HW;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (src_is_fp32 == KIND_F16) {
-        if (dst_is_fp32) hipLaunchKernelGGL((rows_to_ncthw_kernel<StreamH, float>), grid, dim3(256), 0, s, (const StreamH*)src, ld, coff, (float*)dst, B, C, T, HW, scale, Ttot, t0);
-        else hipLaunchKernelGGL((rows_to_ncthw_kernel<StreamH, h16>), grid, dim3(256), 0, s, (const StreamH*)src, ld, coff, (h16*)dst, B, C, T, HW, scale, Ttot, t0);
-    } else if (src_is_fp32) {
-        if (dst_is_fp32) hipLaunchKernelGGL((rows_to_ncthw_kernel<float, float>), grid, dim3(256), 0, s, (const float*)src, ld, coff, (float*)dst, B, C, T, HW, scale, Ttot, t0);
-        else hipLaunchKernelGGL((rows_to_ncthw_kernel<float, h16>), grid, dim3(256), 0, s, (const float*)src, ld, coff, (h16*)dst, B, C, T, HW, scale, Ttot, t0);
-    } else {
-        if (dst_is_fp32) hipLaunchKernelGGL((rows_to_ncthw_kernel<h16, float>), grid, dim3(256), 0, s, (const h16*)src, ld, coff, (float*)dst, B, C, T, HW, scale, Ttot, t0);
-        else hipLaunchKernelGGL((rows_to_ncthw_kernel<h16, h16>), grid, dim3(256), 0, s, (const h16*)src, ld, coff, (h16*)dst, B, C, T, HW, scale, Ttot, t0);
-    }
+    with_kind(src_is_fp32, [&](auto tag) {
+        using ST = typename decltype(tag)::type;
+        if (dst_is_fp32) hipLaunchKernelGGL((rows_to_ncthw_kernel<ST, float>), grid, dim3(256), 0, s, (const ST*)src, ld, coff, (float*)dst, B, C, T, HW, scale, Ttot, t0);
+        else hipLaunchKernelGGL((rows_to_ncthw_kernel<ST, h16>), grid, dim3(256), 0, s, (const ST*)src, ld, coff, (h16*)dst, B, C, T, HW, scale, Ttot, t0);
+    });
     return mudg_check_launch("mudg_rows_to_ncthw");
 }
 
@@ -339,7 +301,7 @@ extern "C" int mudg_zero_channels(void* dst, int rows, int ld, int c0, int c1, v
 }
 
 template <typename ST, typename DT>
-static void launch_cast_rows2(const ST* src, int64_t lds, DT* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s) {
+static void launch_cast_rows(const ST* src, int64_t lds, DT* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s) {
     const int sg = __is_same(ST, h16) ? 8 * PLANES : 8, dg = __is_same(DT, h16) ? 8 * PLANES : 8;      // row-stride granules
     const bool vec = (cols & 7) == 0 && lds % sg == 0 && ldd % dg == 0 && aligned16(src) && aligned16(dst);
     if (vec) {
@@ -351,13 +313,6 @@ static void launch_cast_rows2(const ST* src, int64_t lds, DT* dst, int64_t ldd, 
     }
 }
 
-template <typename ST>
-static void launch_cast_rows(const ST* src, int64_t lds, void* dst, int dst_kind, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s) {
-    if (dst_kind == KIND_F32) launch_cast_rows2(src, lds, (float*)dst, ldd, rows, cols, s);
-    else if (dst_kind == KIND_F16) launch_cast_rows2(src, lds, (StreamH*)dst, ldd, rows, cols, s);
-    else launch_cast_rows2(src, lds, (h16*)dst, ldd, rows, cols, s);
-}
-
 extern "C" int mudg_cast_rows(const void* src, int src_fp32, int64_t lds, void* dst, int dst_fp32, int64_t ldd, int64_t rows,
                               int64_t cols, void* stream) {
     MUDG_REQUIRE(src && dst && rows > 0 && cols > 0, "mudg_cast_rows: bad arguments");
@@ -365,9 +320,11 @@ extern "C" int mudg_cast_rows(const void* src, int src_fp32, int64_t lds, void* 
     MUDG_REQUIRE(src_fp32 ? lds >= cols : (lds % PLANES == 0 && lds / PLANES >= cols), "mudg_cast_rows: lds=%lld", (long long)lds);
     MUDG_REQUIRE(dst_fp32 ? ldd >= cols : (ldd % PLANES == 0 && ldd / PLANES >= cols), "mudg_cast_rows: ldd=%lld", (long long)ldd);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (src_fp32 == KIND_F32) launch_cast_rows((const float*)src, lds, dst, dst_fp32, ldd, rows, cols, s);
-    else if (src_fp32 == KIND_F16) launch_cast_rows((const StreamH*)src, lds, dst, dst_fp32, ldd, rows, cols, s);
-    else launch_cast_rows((const h16*)src, lds, dst, dst_fp32, ldd, rows, cols, s);
+    with_kind(src_fp32, [&](auto st) {
+        with_kind(dst_fp32, [&](auto dt) {
+            launch_cast_rows((const typename decltype(st)::type*)src, lds, (typename decltype(dt)::type*)dst, ldd, rows, cols, s);
+        });
+    });
     return mudg_check_launch("mudg_cast_rows");
 }
 

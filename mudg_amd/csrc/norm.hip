@@ -1,56 +1,11 @@
 // norm.hip — GroupNorm(+SiLU), LayerNorm and row softmax on channels-last h16 data.  All HBM-bound:
 // every pass moves 16 bytes per lane, statistics are fp32 partials combined in fp64 in a fixed order
 // (no atomics: results are bit-reproducible run to run).
-#include "common.h"
+#include "rows_shared.h"
 
 namespace {
 
 constexpr int GN_CMAX = 4096;
-
-// Eight consecutive channels of one pixel as fp32, from operand (h16, PLANES pieces `ld / PLANES` apart) or fp32 storage.
-// `raw` only issues the 16-byte requests and `decode` turns them into values, so a kernel can put several vectors' requests in
-// flight before it touches any of them.
-template <typename T> struct Load8;
-template <> struct Load8<h16> {
-    static constexpr int NR = PLANES;
-    static __device__ __forceinline__ void get(const h16* p, int ld, float (&x)[8]) { load8_operand(p, ld / PLANES, x); }
-    static __device__ __forceinline__ void raw(const h16* p, int ld, u32x4 (&r)[NR]) {
-#pragma unroll
-        for (int k = 0; k < PLANES; ++k) r[k] = ld16(p + (int64_t)k * (ld / PLANES));
-    }
-    static __device__ __forceinline__ void decode(const u32x4 (&r)[NR], float (&x)[8]) {
-#pragma unroll
-        for (int k = 0; k < PLANES; ++k) {
-            const h16x8 t = as_h16x8(r[k]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = k ? x[e] + (float)t[e] : (float)t[e];
-        }
-    }
-};
-struct StreamH { _Float16 v; };       // fp16 residual-stream storage (KIND_F16): a type of its own, h16 may be _Float16 too
-template <> struct Load8<StreamH> {
-    static constexpr int NR = 1;
-    static __device__ __forceinline__ void get(const StreamH* p, int, float (&x)[8]) { load8_f16(reinterpret_cast<const _Float16*>(p), x); }
-    static __device__ __forceinline__ void raw(const StreamH* p, int, u32x4 (&r)[NR]) { r[0] = ld16(p); }
-    static __device__ __forceinline__ void decode(const u32x4 (&r)[NR], float (&x)[8]) {
-        union { u32x4 u; f16x8 h; } t; t.u = r[0];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = (float)t.h[e];
-    }
-};
-template <> struct Load8<float> {
-    static constexpr int NR = 2;
-    static __device__ __forceinline__ void get(const float* p, int, float (&x)[8]) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[e] = a[e]; x[4 + e] = b[e]; }
-    }
-    static __device__ __forceinline__ void raw(const float* p, int, u32x4 (&r)[NR]) { r[0] = ld16(p); r[1] = ld16(p + 4); }
-    static __device__ __forceinline__ void decode(const u32x4 (&r)[NR], float (&x)[8]) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { x[e] = __uint_as_float(r[0][e]); x[4 + e] = __uint_as_float(r[1][e]); }
-    }
-};
 
 // Row chunks per sample of the statistics pass.  A function of `rows` only: the partition decides the order of the
 // fp32 partial sums, and a sample's result must not depend on how many other samples share the launch (clip-level data
@@ -94,7 +49,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ X, 
     const int RP = 256 / nvp;                           // row classes (nvp: vectors per sweep, a divisor of nvec chosen by the host)
     const int rsub = tid / nvp, vl = tid - rsub * nvp;
     const int64_t srow = (int64_t)smp * rows;
-    constexpr int NR = Load8<T>::NR;
+    constexpr int NR = Kind<T>::NR;
 
     for (int vbase = 0; vbase < nvec; vbase += nvp) {
         const int v = vbase + vl;
@@ -110,19 +65,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ X, 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int rr = (r + u * RP < r1) ? r + u * RP : r;
-                    Load8<T>::raw(base + (srow + rr) * ld + cc, ld, raw[u]);
+                    Kind<T>::raw(base + (srow + rr) * ld + cc, ld, raw[u]);
                 }
-                if constexpr (NR == 1) asm volatile("" : "+v"(raw[0][0]), "+v"(raw[1][0]), "+v"(raw[2][0]), "+v"(raw[3][0]));
-                else if constexpr (NR == 2) asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[1][0]), "+v"(raw[1][1]), "+v"(raw[2][0]),
-                                                         "+v"(raw[2][1]), "+v"(raw[3][0]), "+v"(raw[3][1]));
-                else asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[0][2]), "+v"(raw[1][0]), "+v"(raw[1][1]), "+v"(raw[1][2]),
-                                  "+v"(raw[2][0]), "+v"(raw[2][1]), "+v"(raw[2][2]), "+v"(raw[3][0]), "+v"(raw[3][1]), "+v"(raw[3][2]));
-                static_assert(NR <= 3, "the pin above lists its operands");
+                pin_requests(raw);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (r + u * RP >= r1) break;
                     float xv[8];
-                    Load8<T>::decode(raw[u], xv);
+                    Kind<T>::decode(raw[u], xv);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { s[e] += xv[e]; q[e] = fmaf(xv[e], xv[e], q[e]); }
                 }
@@ -164,13 +114,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
         a += (double)p[0]; b += (double)p[1];
     }
     a = wave_sum_d(a); b = wave_sum_d(b);
-    if (lane == 0) {
-        const double mean = a / count;
-        double var = b / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        stat[i * 2] = (float)mean;
-        stat[i * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+    if (lane == 0) store_mean_rstd(a, b, count, eps, stat + i * 2);
 }
 
 // Pass 2': the same fold over the per-(128-row block, channel) partials a producing GEMM / conv epilogue wrote
@@ -216,15 +160,7 @@ __global__ __launch_bounds__(256) void gn_finalize_ch_kernel(const float* __rest
     a = wave_sum_d(a); b = wave_sum_d(b);
     if (lane == 0) { red[wave][0] = a; red[wave][1] = b; }
     __syncthreads();
-    if (tid == 0) {
-        a = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        b = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-        const double mean = a / count;
-        double var = b / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        stat[i * 2] = (float)mean;
-        stat[i * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+    if (tid == 0) store_mean_rstd(fold4(red, 0), fold4(red, 1), count, eps, stat + i * 2);
 }
 
 // Pass 3: y = (x - mean) * rstd * gamma + beta, optional SiLU.  HBM-bound (2 B in + 2 B out per element on the 16-bit builds).
@@ -253,7 +189,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ X, 
     const int n = (r1 - r0) * nvec;                        // <= 256 * GN_UNROLL (the host sizes RB)
     const int dr = 256 / nvec, dv = 256 - dr * nvec;       // entry i + 256 is dr rows and dv vectors further (with carry)
     int r = r0 + tid / nvec, v = tid - (tid / nvec) * nvec;
-    constexpr int NR = Load8<T>::NR;
+    constexpr int NR = Kind<T>::NR;
     u32x4 raw[GN_UNROLL][NR];
     int64_t yoff[GN_UNROLL];
     int c0s[GN_UNROLL];
@@ -267,7 +203,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ X, 
         yoff[u] = (srow + rr) * ldy + c0;
         const T* base = X; int cc = c0, ld = ldx;
         if (c0 >= csplit) { base = X2; cc = c0 - csplit; ld = ldx2; }
-        Load8<T>::raw(base + (srow + rr) * ld + cc, ld, raw[u]);
+        Kind<T>::raw(base + (srow + rr) * ld + cc, ld, raw[u]);
         r += dr; v += dv;
         if (v >= nvec) { v -= nvec; ++r; }
     }
@@ -281,28 +217,16 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ X, 
         sh[cl] = beta[c] - mean * a;
     }
     __syncthreads();
-    // every request is pinned here, in straight-line code, before any value is decoded: without it the compiler sinks each
-    // load into the conditional block that stores its result, and the requests go out one at a time
-    if constexpr (NR == 1) asm volatile("" : "+v"(raw[0][0]), "+v"(raw[1][0]), "+v"(raw[2][0]), "+v"(raw[3][0]));
-    else if constexpr (NR == 2) asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[1][0]), "+v"(raw[1][1]), "+v"(raw[2][0]),
-                                             "+v"(raw[2][1]), "+v"(raw[3][0]), "+v"(raw[3][1]));
-    else asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[0][2]), "+v"(raw[1][0]), "+v"(raw[1][1]), "+v"(raw[1][2]),
-                      "+v"(raw[2][0]), "+v"(raw[2][1]), "+v"(raw[2][2]), "+v"(raw[3][0]), "+v"(raw[3][1]), "+v"(raw[3][2]));
-    static_assert(GN_UNROLL == 4 && NR <= 3, "the pin above lists its operands");
+    pin_requests(raw);                                     // in straight-line code, before any value is decoded
 #pragma unroll
     for (int u = 0; u < GN_UNROLL; ++u) {
         if (tid + 256 * u >= n) break;
         float xv[8];
-        Load8<T>::decode(raw[u], xv);
+        Kind<T>::decode(raw[u], xv);
         const int cl = c0s[u];
         float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float y = fmaf(xv[e], sc[cl + e], sh[cl + e]);
-            if (silu) y = PLANES > 1 ? y / (1.0f + expf(-y))                   // split builds: IEEE division, full-precision exp
-                                     : y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));      // 1-ulp reciprocal: the result is rounded to h16
-            o[e] = y;
-        }
+        for (int e = 0; e < 8; ++e) o[e] = gn_affine_act(xv[e], sc[cl + e], sh[cl + e], silu);
         store8_operand(Y + yoff[u], ldy / PLANES, o);
     }
 }
@@ -328,16 +252,16 @@ __global__ __launch_bounds__(256) void gn_apply_reg_kernel(const T* __restrict__
     const int64_t srow = (int64_t)smp * rows;
     const T* base = X; int cc = c0, ld = ldx;
     if (c0 >= csplit) { base = X2; cc = c0 - csplit; ld = ldx2; }
-    constexpr int NR = Load8<T>::NR;
+    constexpr int NR = Kind<T>::NR;
     u32x4 raw[GN_UNROLL][NR];
 #pragma unroll
     for (int u = 0; u < GN_UNROLL; ++u) {
         const int r = r0 + RP * u;
-        Load8<T>::raw(base + (srow + (r < rows ? r : rows - 1)) * ld + cc, ld, raw[u]);
+        Kind<T>::raw(base + (srow + (r < rows ? r : rows - 1)) * ld + cc, ld, raw[u]);
     }
     const int cpg = C / groups;
-    const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + c0), g1 = *reinterpret_cast<const f32x4*>(gamma + c0 + 4);
-    const f32x4 b0 = *reinterpret_cast<const f32x4*>(beta + c0), b1 = *reinterpret_cast<const f32x4*>(beta + c0 + 4);
+    f32x4 g[2], b[2];
+    load_affine8(gamma, beta, c0, g, b);
     const f32x2* st = reinterpret_cast<const f32x2*>(stat) + smp * groups;
     f32x2 mr[8];
     const int gq = c0 / cpg, rem = c0 - gq * cpg;
@@ -353,33 +277,23 @@ __global__ __launch_bounds__(256) void gn_apply_reg_kernel(const T* __restrict__
     // requests between the uses to save registers: three round trips).  The pin keeps the payload loads out of the conditional
     // blocks that consume them (the IR-level sinking the scheduling barrier does not see).
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (NR == 1) asm volatile("" : "+v"(raw[0][0]), "+v"(raw[1][0]), "+v"(raw[2][0]), "+v"(raw[3][0]));
-    else if constexpr (NR == 2) asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[1][0]), "+v"(raw[1][1]), "+v"(raw[2][0]),
-                                             "+v"(raw[2][1]), "+v"(raw[3][0]), "+v"(raw[3][1]));
-    else asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[0][2]), "+v"(raw[1][0]), "+v"(raw[1][1]), "+v"(raw[1][2]),
-                      "+v"(raw[2][0]), "+v"(raw[2][1]), "+v"(raw[2][2]), "+v"(raw[3][0]), "+v"(raw[3][1]), "+v"(raw[3][2]));
-    static_assert(GN_UNROLL == 4 && NR <= 3, "the pin above lists its operands");
+    pin_requests(raw);
     float sc[8], sh[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float a = mr[e][1] * (e < 4 ? g0[e & 3] : g1[e & 3]);
+        const float a = mr[e][1] * g[e >> 2][e & 3];
         sc[e] = a;
-        sh[e] = (e < 4 ? b0[e & 3] : b1[e & 3]) - mr[e][0] * a;
+        sh[e] = b[e >> 2][e & 3] - mr[e][0] * a;
     }
 #pragma unroll
     for (int u = 0; u < GN_UNROLL; ++u) {
         const int r = r0 + RP * u;
         if (u > 0 && r >= rows) break;
         float xv[8];
-        Load8<T>::decode(raw[u], xv);
+        Kind<T>::decode(raw[u], xv);
         float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float y = fmaf(xv[e], sc[e], sh[e]);
-            if (silu) y = PLANES > 1 ? y / (1.0f + expf(-y))
-                                     : y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));
-            o[e] = y;
-        }
+        for (int e = 0; e < 8; ++e) o[e] = gn_affine_act(xv[e], sc[e], sh[e], silu);
         store8_operand(Y + (srow + r) * ldy + c0, ldy / PLANES, o);
     }
 }
@@ -403,30 +317,22 @@ void launch_gn_apply(int x_fp32, const void* X, const void* X2, int csplit, int 
     if (reg_table && nvec <= 256 && aligned16(gamma) && aligned16(beta)) {
         const int RB = (256 / nvec) * GN_UNROLL;
         const dim3 grid((rows + RB - 1) / RB, samples, C / CS);
-        if (x_fp32 == KIND_F16)
-            hipLaunchKernelGGL(gn_apply_reg_kernel<StreamH>, grid, dim3(256), 0, s, (const StreamH*)X, (const StreamH*)X2,
-                               csplit, ldx, ldx2, gamma, beta, (h16*)Y, ldy, rows, C, groups, CS, silu, stat);
-        else if (x_fp32)
-            hipLaunchKernelGGL(gn_apply_reg_kernel<float>, grid, dim3(256), 0, s, (const float*)X, (const float*)X2,
-                               csplit, ldx, ldx2, gamma, beta, (h16*)Y, ldy, rows, C, groups, CS, silu, stat);
-        else
-            hipLaunchKernelGGL(gn_apply_reg_kernel<h16>, grid, dim3(256), 0, s, (const h16*)X, (const h16*)X2,
-                               csplit, ldx, ldx2, gamma, beta, (h16*)Y, ldy, rows, C, groups, CS, silu, stat);
+        with_kind(x_fp32, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            hipLaunchKernelGGL(gn_apply_reg_kernel<T>, grid, dim3(256), 0, s, (const T*)X, (const T*)X2, csplit, ldx, ldx2, gamma, beta,
+                               (h16*)Y, ldy, rows, C, groups, CS, silu, stat);
+        });
         return;
     }
     int RB = (256 * GN_UNROLL) / nvec;
     if (RB < 1) RB = 1;
     const dim3 grid((rows + RB - 1) / RB, samples, C / CS);
     const size_t lds = 2 * (size_t)CS * sizeof(float);
-    if (x_fp32 == KIND_F16)
-        hipLaunchKernelGGL(gn_apply_kernel<StreamH>, grid, dim3(256), lds, s, (const StreamH*)X, (const StreamH*)X2,
-                           csplit, ldx, ldx2, gamma, beta, (h16*)Y, ldy, rows, C, groups, CS, RB, silu, stat);
-    else if (x_fp32)
-        hipLaunchKernelGGL(gn_apply_kernel<float>, grid, dim3(256), lds, s, (const float*)X, (const float*)X2,
-                           csplit, ldx, ldx2, gamma, beta, (h16*)Y, ldy, rows, C, groups, CS, RB, silu, stat);
-    else
-        hipLaunchKernelGGL(gn_apply_kernel<h16>, grid, dim3(256), lds, s, (const h16*)X, (const h16*)X2,
-                           csplit, ldx, ldx2, gamma, beta, (h16*)Y, ldy, rows, C, groups, CS, RB, silu, stat);
+    with_kind(x_fp32, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(gn_apply_kernel<T>, grid, dim3(256), lds, s, (const T*)X, (const T*)X2, csplit, ldx, ldx2, gamma, beta,
+                           (h16*)Y, ldy, rows, C, groups, CS, RB, silu, stat);
+    });
 }
 
 // LayerNorm: one wave per row, up to VMAX 16-byte vectors per lane kept in registers (C <= 512 * VMAX).
@@ -444,7 +350,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const T* __restrict__ X, int ld
     for (int i = 0; i < VMAX; ++i) {
         const int v = lane + 64 * i;
         if (v < nvec) {
-            Load8<T>::get(X + row * ldx + v * 8, ldx, x[i]);
+            Kind<T>::get(X + row * ldx + v * 8, ldx, x[i]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) s += x[i][e];
         } else {
@@ -467,16 +373,10 @@ __global__ __launch_bounds__(256) void ln_kernel(const T* __restrict__ X, int ld
     for (int i = 0; i < VMAX; ++i) {
         const int v = lane + 64 * i;
         if (v < nvec) {
-            const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + v * 8);
-            const f32x4 g1 = *reinterpret_cast<const f32x4*>(gamma + v * 8 + 4);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(beta + v * 8);
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(beta + v * 8 + 4);
+            f32x4 g[2], b[2];
+            load_affine8(gamma, beta, v * 8, g, b);
             float o[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[e] = fmaf((x[i][e] - mean) * rstd, g0[e], b0[e]);
-                o[4 + e] = fmaf((x[i][4 + e] - mean) * rstd, g1[e], b1[e]);
-            }
+            ln_apply8(x[i], mean, rstd, g, b, o);
             store8_operand(Y + row * ldy + v * 8, ldy / PLANES, o);
         }
     }
@@ -508,7 +408,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const T* __restrict__ X, i
                                                        int rows, float eps) {
     constexpr int RPW = 64 / LPR;                       // rows per wave
     constexpr int C = LPR * NV * 8;
-    constexpr int NR = Load8<T>::NR;
+    constexpr int NR = Kind<T>::NR;
     const int lane = threadIdx.x & 63;
     const int sub = lane & (LPR - 1);
     int64_t row = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
@@ -517,13 +417,9 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const T* __restrict__ X, i
     u32x4 raw[NV][NR];
     f32x4 g[NV][2], b[NV][2];
 #pragma unroll
-    for (int i = 0; i < NV; ++i) Load8<T>::raw(X + row * ldx + (sub + LPR * i) * 8, ldx, raw[i]);
+    for (int i = 0; i < NV; ++i) Kind<T>::raw(X + row * ldx + (sub + LPR * i) * 8, ldx, raw[i]);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (sub + LPR * i) * 8;
-        g[i][0] = *reinterpret_cast<const f32x4*>(gamma + c); g[i][1] = *reinterpret_cast<const f32x4*>(gamma + c + 4);
-        b[i][0] = *reinterpret_cast<const f32x4*>(beta + c); b[i][1] = *reinterpret_cast<const f32x4*>(beta + c + 4);
-    }
+    for (int i = 0; i < NV; ++i) load_affine8(gamma, beta, (sub + LPR * i) * 8, g[i], b[i]);
     __builtin_amdgcn_sched_barrier(0);                  // requests above, arithmetic below
     // (and pinned in this unconditional block: left alone, the gamma / beta loads sink into the `live` branch that consumes them)
 #pragma unroll
@@ -536,7 +432,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const T* __restrict__ X, i
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         float x[8];
-        Load8<T>::decode(raw[i], x);
+        Kind<T>::decode(raw[i], x);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += x[e];
     }
@@ -545,7 +441,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const T* __restrict__ X, i
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         float x[8];
-        Load8<T>::decode(raw[i], x);
+        Kind<T>::decode(raw[i], x);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = x[e] - mean; q = fmaf(d, d, q); }
     }
@@ -554,12 +450,9 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const T* __restrict__ X, i
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         float x[8], o[8];
-        Load8<T>::decode(raw[i], x);
+        Kind<T>::decode(raw[i], x);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            o[e] = fmaf((x[e] - mean) * rstd, g[i][0][e], b[i][0][e]);
-            o[4 + e] = fmaf((x[4 + e] - mean) * rstd, g[i][1][e], b[i][1][e]);
-        }
+        for (int e = 0; e < 4; ++e) { o[e] = ln_apply1(x[e], mean, rstd, g[i][0][e], b[i][0][e]); o[4 + e] = ln_apply1(x[4 + e], mean, rstd, g[i][1][e], b[i][1][e]); }
         store8_operand(Y + row * ldy + (sub + LPR * i) * 8, ldy / PLANES, o);
     }
 }
@@ -568,33 +461,44 @@ template <int LPR, int NV>
 void launch_ln_rows(int x_fp32, const void* X, int ldx, const float* gamma, const float* beta, void* Y, int ldy, int rows,
                     float eps, hipStream_t s) {
     const dim3 grid((rows + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)));
-    if (x_fp32 == KIND_F16) hipLaunchKernelGGL((ln_rows_kernel<LPR, NV, StreamH>), grid, dim3(256), 0, s, (const StreamH*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, eps);
-    else if (x_fp32) hipLaunchKernelGGL((ln_rows_kernel<LPR, NV, float>), grid, dim3(256), 0, s, (const float*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, eps);
-    else hipLaunchKernelGGL((ln_rows_kernel<LPR, NV, h16>), grid, dim3(256), 0, s, (const h16*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, eps);
+    with_kind(x_fp32, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((ln_rows_kernel<LPR, NV, T>), grid, dim3(256), 0, s, (const T*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, eps);
+    });
+}
+template <int VMAX>
+void launch_ln(int x_fp32, const void* X, int ldx, const float* gamma, const float* beta, void* Y, int ldy, int rows, int C, float eps,
+               hipStream_t s) {
+    with_kind(x_fp32, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((ln_kernel<VMAX, T>), dim3((rows + 3) / 4), dim3(256), 0, s, (const T*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, C, eps);
+    });
 }
 
-// Row softmax fp32 -> h16, one workgroup per row, three passes over the row (second and third hit L2).
+// Row softmax fp32 -> h16 (softmax_row_walk; the exponential is the hardware's on the 16-bit builds).
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ S, int lds, h16* __restrict__ P,
                                                             int ldp, int cols) {
     __shared__ float red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* s = S + (int64_t)blockIdx.x * lds;
     h16* p = P + (int64_t)blockIdx.x * ldp;
-    float mx = -INFINITY;
-    for (int c = tid; c < cols; c += 256) mx = fmaxf(mx, s[c]);
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-    for (int c = tid; c < cols; c += 256) sum += PLANES > 1 ? expf(s[c] - mx) : __expf(s[c] - mx);
-    sum = wave_sum(sum);
-    if (lane == 0) red[wave] = sum;
-    __syncthreads();
-    sum = ((red[0] + red[1]) + red[2]) + red[3];
-    const float inv = 1.f / sum;
-    for (int c = tid; c < cols; c += 256) store1_operand(p + c, ldp / PLANES, (PLANES > 1 ? expf(s[c] - mx) : __expf(s[c] - mx)) * inv);
+    softmax_row_walk<PLANES == 1>(S + (int64_t)blockIdx.x * lds, cols, red, [&](int c, float v) { store1_operand(p + c, ldp / PLANES, v); });
+}
+
+// The argument checks both GroupNorm entry points share (`who`: the entry point's name in the message); without a second source,
+// csplit / ldx2 are set so that every channel comes from X.
+int gn_check_args(const char* who, const void* X, const void* X2, int& csplit, int ldx, int& ldx2, int x_fp32, const float* gamma,
+                  const float* beta, const void* Y, int ldy, int samples, int rows, int C, int groups, const float* ws) {
+    MUDG_REQUIRE(X && Y && gamma && beta && ws, "%s: null pointer", who);
+    MUDG_REQUIRE(samples > 0 && rows > 0 && C > 0 && groups > 0, "%s: empty problem", who);
+    MUDG_REQUIRE(C % groups == 0 && (C & 7) == 0 && C <= GN_CMAX, "%s: C=%d groups=%d unsupported", who, C, groups);
+    MUDG_REQUIRE(groups <= 256, "%s: groups=%d > 256", who, groups);
+    MUDG_REQUIRE(x_fp32 >= 0 && x_fp32 <= 2, "%s: x_fp32 is 0 (operand), 1 (fp32) or 2 (fp16)", who);
+    const int xq = kind_granule(x_fp32);
+    MUDG_REQUIRE(ldx % xq == 0 && ldy % (8 * PLANES) == 0 && aligned16(X) && aligned16(Y), "%s: alignment", who);
+    MUDG_REQUIRE(ldy / PLANES >= C, "%s: ldy=%d too small for %d plane(s) of %d channels", who, ldy, PLANES, C);
+    MUDG_REQUIRE(samples <= 65535, "%s: too many samples", who);
+    if (!X2) { csplit = C; ldx2 = ldx; }
+    else MUDG_REQUIRE(csplit > 0 && csplit < C && (csplit & 7) == 0 && ldx2 % xq == 0 && aligned16(X2), "%s: X2/csplit", who);
+    return MUDG_OK;
 }
 
 }  // namespace
@@ -607,17 +511,8 @@ extern "C" int64_t mudg_groupnorm_ws_floats(int samples, int groups, int rows) {
 extern "C" int mudg_groupnorm(const void* X, const void* X2, int csplit, int ldx, int ldx2, int x_fp32, const float* gamma,
                               const float* beta, void* Y, int ldy, int samples, int rows, int C, int groups, float eps,
                               int silu, float* ws, void* stream) {
-    MUDG_REQUIRE(X && Y && gamma && beta && ws, "mudg_groupnorm: null pointer");
-    MUDG_REQUIRE(samples > 0 && rows > 0 && C > 0 && groups > 0, "mudg_groupnorm: empty problem");
-    MUDG_REQUIRE(C % groups == 0 && (C & 7) == 0 && C <= GN_CMAX, "mudg_groupnorm: C=%d groups=%d unsupported", C, groups);
-    MUDG_REQUIRE(groups <= 256, "mudg_groupnorm: groups=%d > 256", groups);
-    MUDG_REQUIRE(x_fp32 >= 0 && x_fp32 <= 2, "mudg_groupnorm: x_fp32 is 0 (operand), 1 (fp32) or 2 (fp16)");
-    const int xq = x_fp32 == KIND_F32 ? 4 : (x_fp32 == KIND_F16 ? 8 : 8 * PLANES);      // row stride granule so that every 8-channel vector (of every plane) is 16-byte aligned
-    MUDG_REQUIRE(ldx % xq == 0 && ldy % (8 * PLANES) == 0 && aligned16(X) && aligned16(Y), "mudg_groupnorm: alignment");
-    MUDG_REQUIRE(ldy / PLANES >= C, "mudg_groupnorm: ldy=%d too small for %d plane(s) of %d channels", ldy, PLANES, C);
-    MUDG_REQUIRE(samples <= 65535, "mudg_groupnorm: too many samples");
-    if (!X2) { csplit = C; ldx2 = ldx; }
-    else MUDG_REQUIRE(csplit > 0 && csplit < C && (csplit & 7) == 0 && ldx2 % xq == 0 && aligned16(X2), "mudg_groupnorm: X2/csplit");
+    const int bad = gn_check_args("mudg_groupnorm", X, X2, csplit, ldx, ldx2, x_fp32, gamma, beta, Y, ldy, samples, rows, C, groups, ws);
+    if (bad != MUDG_OK) return bad;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int nchunks = gn_chunks(samples, rows);
     float* part = ws;
@@ -625,15 +520,11 @@ extern "C" int mudg_groupnorm(const void* X, const void* X2, int csplit, int ldx
     const int slot = mudg_prof_begin(MUDG_FAM_GNORM, s);
     const size_t stats_lds = (256 * 16 + 2 * (size_t)C) * sizeof(float);
     const int nvp = gn_stats_sweep(C >> 3);
-    if (x_fp32 == KIND_F16)
-        hipLaunchKernelGGL(gn_stats_kernel<StreamH>, dim3(nchunks, samples), dim3(256), stats_lds, s, (const StreamH*)X, (const StreamH*)X2,
-                           csplit, ldx, ldx2, rows, C, groups, nchunks, nvp, part);
-    else if (x_fp32)
-        hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(nchunks, samples), dim3(256), stats_lds, s, (const float*)X, (const float*)X2,
-                           csplit, ldx, ldx2, rows, C, groups, nchunks, nvp, part);
-    else
-        hipLaunchKernelGGL(gn_stats_kernel<h16>, dim3(nchunks, samples), dim3(256), stats_lds, s, (const h16*)X, (const h16*)X2,
-                           csplit, ldx, ldx2, rows, C, groups, nchunks, nvp, part);
+    with_kind(x_fp32, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(gn_stats_kernel<T>, dim3(nchunks, samples), dim3(256), stats_lds, s, (const T*)X, (const T*)X2, csplit, ldx, ldx2,
+                           rows, C, groups, nchunks, nvp, part);
+    });
     const int ng = samples * groups;
     hipLaunchKernelGGL(gn_finalize_kernel, dim3((ng + 3) / 4), dim3(256), 0, s, part, stat, samples, groups, nchunks,
                        (double)rows * (C / groups), eps);
@@ -646,31 +537,14 @@ extern "C" int mudg_groupnorm(const void* X, const void* X2, int csplit, int ldx
 extern "C" int mudg_groupnorm_fused_rows(const void* X, const void* X2, int csplit, int ldx, int ldx2, int x_fp32,
                                          const float* gamma, const float* beta, void* Y, int ldy, int samples, int rows, int C,
                                          int groups, float eps, int silu, const float* P1, int p1_rows, const float* P2, int p2_rows,
-                                         float* ws, void* stream);
-extern "C" int mudg_groupnorm_fused(const void* X, const void* X2, int csplit, int ldx, int ldx2, int x_fp32,
-                                    const float* gamma, const float* beta, void* Y, int ldy, int samples, int rows, int C,
-                                    int groups, float eps, int silu, const float* P1, const float* P2, float* ws, void* stream) {
-    return mudg_groupnorm_fused_rows(X, X2, csplit, ldx, ldx2, x_fp32, gamma, beta, Y, ldy, samples, rows, C, groups, eps, silu, P1, 128, P2, 128,
-                                     ws, stream);
-}
-extern "C" int mudg_groupnorm_fused_rows(const void* X, const void* X2, int csplit, int ldx, int ldx2, int x_fp32,
-                                         const float* gamma, const float* beta, void* Y, int ldy, int samples, int rows, int C,
-                                         int groups, float eps, int silu, const float* P1, int p1_rows, const float* P2, int p2_rows,
                                          float* ws, void* stream) {
-    MUDG_REQUIRE(X && Y && gamma && beta && ws && P1, "mudg_groupnorm_fused: null pointer");
+    MUDG_REQUIRE(P1 && (!X2 || P2), "mudg_groupnorm_fused: null partials");
     MUDG_REQUIRE((p1_rows == 128 || p1_rows == 160 || p1_rows == 288) && (!X2 || p2_rows == 128 || p2_rows == 160 || p2_rows == 288),
                  "mudg_groupnorm_fused: partial blocks are 128, 160 or 288 rows high");
-    if (!X2) p2_rows = p1_rows;
+    if (!X2) { p2_rows = p1_rows; P2 = P1; }
     MUDG_REQUIRE(rows % p1_rows == 0 && rows % p2_rows == 0, "mudg_groupnorm_fused: rows=%d per sample must be whole partial blocks (%d / %d rows)", rows, p1_rows, p2_rows);
-    MUDG_REQUIRE(samples > 0 && rows > 0 && C > 0 && groups > 0, "mudg_groupnorm_fused: empty problem");
-    MUDG_REQUIRE(C % groups == 0 && (C & 7) == 0 && C <= GN_CMAX && groups <= 256, "mudg_groupnorm_fused: C=%d groups=%d unsupported", C, groups);
-    MUDG_REQUIRE(x_fp32 >= 0 && x_fp32 <= 2, "mudg_groupnorm_fused: x_fp32 is 0 (operand), 1 (fp32) or 2 (fp16)");
-    const int xq = x_fp32 == KIND_F32 ? 4 : (x_fp32 == KIND_F16 ? 8 : 8 * PLANES);
-    MUDG_REQUIRE(ldx % xq == 0 && ldy % (8 * PLANES) == 0 && aligned16(X) && aligned16(Y), "mudg_groupnorm_fused: alignment");
-    MUDG_REQUIRE(ldy / PLANES >= C, "mudg_groupnorm_fused: ldy=%d too small for %d plane(s) of %d channels", ldy, PLANES, C);
-    MUDG_REQUIRE(samples <= 65535, "mudg_groupnorm_fused: too many samples");
-    if (!X2) { csplit = C; ldx2 = ldx; P2 = P1; }
-    else MUDG_REQUIRE(P2 && csplit > 0 && csplit < C && (csplit & 7) == 0 && ldx2 % xq == 0 && aligned16(X2), "mudg_groupnorm_fused: X2/csplit/P2");
+    const int bad = gn_check_args("mudg_groupnorm_fused", X, X2, csplit, ldx, ldx2, x_fp32, gamma, beta, Y, ldy, samples, rows, C, groups, ws);
+    if (bad != MUDG_OK) return bad;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* stat = ws;
     const int slot = mudg_prof_begin(MUDG_FAM_GNORM, s);
@@ -682,18 +556,23 @@ extern "C" int mudg_groupnorm_fused_rows(const void* X, const void* X2, int cspl
     mudg_prof_end(slot, s, 0.0, (double)samples * rows * C * (x_fp32 == KIND_F32 ? 6.0 : 4.0));
     return rc;
 }
+extern "C" int mudg_groupnorm_fused(const void* X, const void* X2, int csplit, int ldx, int ldx2, int x_fp32,
+                                    const float* gamma, const float* beta, void* Y, int ldy, int samples, int rows, int C,
+                                    int groups, float eps, int silu, const float* P1, const float* P2, float* ws, void* stream) {
+    return mudg_groupnorm_fused_rows(X, X2, csplit, ldx, ldx2, x_fp32, gamma, beta, Y, ldy, samples, rows, C, groups, eps, silu, P1, 128, P2, 128,
+                                     ws, stream);
+}
 
 extern "C" int mudg_layernorm(const void* X, int ldx, int x_fp32, const float* gamma, const float* beta, void* Y, int ldy,
                               int rows, int C, float eps, void* stream) {
     MUDG_REQUIRE(X && Y && gamma && beta, "mudg_layernorm: null pointer");
     MUDG_REQUIRE(rows > 0 && C > 0 && (C & 7) == 0 && C <= 4096, "mudg_layernorm: rows=%d C=%d unsupported", rows, C);
     MUDG_REQUIRE(x_fp32 >= 0 && x_fp32 <= 2, "mudg_layernorm: x_fp32 is 0 (operand), 1 (fp32) or 2 (fp16)");
-    MUDG_REQUIRE(ldx % (x_fp32 == KIND_F32 ? 4 : (x_fp32 == KIND_F16 ? 8 : 8 * PLANES)) == 0 && ldy % (8 * PLANES) == 0 && aligned16(X) && aligned16(Y) && aligned16(gamma) &&
+    MUDG_REQUIRE(ldx % kind_granule(x_fp32) == 0 && ldy % (8 * PLANES) == 0 && aligned16(X) && aligned16(Y) && aligned16(gamma) &&
                  aligned16(beta), "mudg_layernorm: alignment");
     MUDG_REQUIRE(ldy / PLANES >= C, "mudg_layernorm: ldy=%d too small for %d plane(s) of %d channels", ldy, PLANES, C);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int slot = mudg_prof_begin(MUDG_FAM_LNORM, s);
-    const dim3 grid((rows + 3) / 4);
     const int nvec = C >> 3;
     static int rows_kernel = -1;            // MUDG_LN_ROWS=0: the one-wave-per-row kernel for every width (A/B, tests)
     if (rows_kernel < 0) rows_kernel = mudg_variant("LN_ROWS", 1);
@@ -702,15 +581,8 @@ extern "C" int mudg_layernorm(const void* X, int ldx, int x_fp32, const float* g
     else if (rows_kernel && C == 640) launch_ln_rows<16, 5>(x_fp32, X, ldx, gamma, beta, Y, ldy, rows, eps, s);
     else if (rows_kernel && C == 1024) launch_ln_rows<32, 4>(x_fp32, X, ldx, gamma, beta, Y, ldy, rows, eps, s);
     else if (rows_kernel && C == 1280) launch_ln_rows<32, 5>(x_fp32, X, ldx, gamma, beta, Y, ldy, rows, eps, s);
-    else if (nvec <= 64 * 3) {
-        if (x_fp32 == KIND_F16) hipLaunchKernelGGL((ln_kernel<3, StreamH>), grid, dim3(256), 0, s, (const StreamH*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, C, eps);
-        else if (x_fp32) hipLaunchKernelGGL((ln_kernel<3, float>), grid, dim3(256), 0, s, (const float*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, C, eps);
-        else hipLaunchKernelGGL((ln_kernel<3, h16>), grid, dim3(256), 0, s, (const h16*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, C, eps);
-    } else {
-        if (x_fp32 == KIND_F16) hipLaunchKernelGGL((ln_kernel<8, StreamH>), grid, dim3(256), 0, s, (const StreamH*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, C, eps);
-        else if (x_fp32) hipLaunchKernelGGL((ln_kernel<8, float>), grid, dim3(256), 0, s, (const float*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, C, eps);
-        else hipLaunchKernelGGL((ln_kernel<8, h16>), grid, dim3(256), 0, s, (const h16*)X, ldx, gamma, beta, (h16*)Y, ldy, rows, C, eps);
-    }
+    else if (nvec <= 64 * 3) launch_ln<3>(x_fp32, X, ldx, gamma, beta, Y, ldy, rows, C, eps, s);
+    else launch_ln<8>(x_fp32, X, ldx, gamma, beta, Y, ldy, rows, C, eps, s);
     const int rc = mudg_check_launch("mudg_layernorm");
     mudg_prof_end(slot, s, 0.0, (double)rows * C * (x_fp32 == KIND_F32 ? 6.0 : 4.0));
     return rc;

@@ -6,17 +6,13 @@
 // the forward GEMM kernels (gemm.hip) — see mudg_amd/train/functions.py for how each one is expressed.
 // Gradients and the training stream are fp32 rows matrices; operands for the MFMA kernels are made by mudg_cast_rows /
 // mudg_transpose_gather.  Every reduction has a fixed order: no atomics, bit-reproducible gradients.
-#include "common.h"
+#include "rows_shared.h"
 
 namespace {
 
 __device__ __forceinline__ float gelu_grad(float x) {        // d/dx [x Phi(x)] = Phi(x) + x phi(x)
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
     return cdf + x * 0.39894228040143267794f * expf(-0.5f * x * x);
-}
-__device__ __forceinline__ float silu_grad(float z) {        // d/dz [z sigma(z)] = sigma (1 + z (1 - sigma))
-    const float s = 1.0f / (1.0f + expf(-z));
-    return s * (1.0f + z * (1.0f - s));
 }
 
 // ---------------------------------------------------------------------------------------------- transpose / gather
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(256) void group_colsum_kernel(const float* __restri
         }
     part[wave][lane] = s;
     __syncthreads();
-    if (wave == 0 && c < cols) out[(int64_t)blockIdx.y * cols + c] = (float)(((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]);
+    if (wave == 0 && c < cols) out[(int64_t)blockIdx.y * cols + c] = (float)fold4(part, lane);
 }
 
 // ---------------------------------------------------------------------------------------------- GroupNorm backward
@@ -176,9 +172,8 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
         const float ga = gamma[c], be = beta[c];
         for (int r = r0 + wave; r < r1; r += 4) {
             const int64_t row = (int64_t)smp * rows + r;
-            const float xh = (X[row * ldx + c] - mean) * rstd;
-            float dz = dY[row * ldy + c];
-            if (silu) dz *= silu_grad(fmaf(xh, ga, be));
+            float xh;
+            const float dz = gn_bwd_dz(X[row * ldx + c], dY[row * ldy + c], mean, rstd, ga, be, silu, xh);
             a += dz; b = fmaf(dz, xh, b);
         }
     }
@@ -186,8 +181,8 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
     __syncthreads();
     if (wave == 0 && c < C) {
         float* o = part + (((int64_t)smp * nchunks + chunk) * C + c) * 2;
-        o[0] = ((pa[0][lane] + pa[1][lane]) + pa[2][lane]) + pa[3][lane];
-        o[1] = ((pb[0][lane] + pb[1][lane]) + pb[2][lane]) + pb[3][lane];
+        o[0] = fold4(pa, lane);
+        o[1] = fold4(pb, lane);
     }
 }
 
@@ -230,9 +225,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     const int smp = (int)(row / rows), g = c / (C / groups);
     const float mean = stat[(smp * groups + g) * 2], rstd = stat[(smp * groups + g) * 2 + 1];
     const float res = dRes ? dRes[row * lddres + c] : 0.f;       // the gradient of the residual branch that bypassed the norm
-    const float xh = (X[row * ldx + c] - mean) * rstd;
-    float dz = dY[row * ldy + c];
-    if (silu) dz *= silu_grad(fmaf(xh, gamma[c], beta[c]));
+    float xh;
+    const float dz = gn_bwd_dz(X[row * ldx + c], dY[row * ldy + c], mean, rstd, gamma[c], beta[c], silu, xh);
     dX[row * lddx + c] = rstd * (dz * gamma[c] - m12[(smp * groups + g) * 2] - xh * m12[(smp * groups + g) * 2 + 1]) + res;
 }
 
@@ -381,37 +375,19 @@ __global__ __launch_bounds__(256) void geglu_drop_bwd_kernel(const float* __rest
 // P = softmax(S) row-wise, fp32 in place-capable; dS = scale * P (dP - sum_j dP_j P_j).  One workgroup per row.
 __global__ __launch_bounds__(256) void softmax_f32_kernel(const float* __restrict__ S, int64_t lds, float* __restrict__ P, int64_t ldp, int cols) {
     __shared__ float red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* s = S + (int64_t)blockIdx.x * lds;
     float* p = P + (int64_t)blockIdx.x * ldp;
-    float mx = -INFINITY;
-    for (int c = tid; c < cols; c += 256) mx = fmaxf(mx, s[c]);
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-    for (int c = tid; c < cols; c += 256) sum += expf(s[c] - mx);
-    sum = wave_sum(sum);
-    if (lane == 0) red[wave] = sum;
-    __syncthreads();
-    const float inv = 1.f / (((red[0] + red[1]) + red[2]) + red[3]);
-    for (int c = tid; c < cols; c += 256) p[c] = expf(s[c] - mx) * inv;
+    softmax_row_walk<false>(S + (int64_t)blockIdx.x * lds, cols, red, [&](int c, float v) { p[c] = v; });
 }
 __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restrict__ P, int64_t ldp, const float* __restrict__ dP, int64_t lddp,
                                                            float* __restrict__ dS, int64_t ldds, int cols, float scale) {
     __shared__ float red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const float* p = P + (int64_t)blockIdx.x * ldp;
     const float* dp = dP + (int64_t)blockIdx.x * lddp;
     float* ds = dS + (int64_t)blockIdx.x * ldds;
     float dot = 0.f;
     for (int c = tid; c < cols; c += 256) dot = fmaf(p[c], dp[c], dot);
-    dot = wave_sum(dot);
-    if (lane == 0) red[wave] = dot;
-    __syncthreads();
-    dot = ((red[0] + red[1]) + red[2]) + red[3];
+    dot = block_sum4(wave_sum(dot), red);
     for (int c = tid; c < cols; c += 256) ds[c] = scale * p[c] * (dp[c] - dot);
 }
 
@@ -480,10 +456,8 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restric
     const float* tt = target + (int64_t)b * n;
     double s = 0.0;
     for (int64_t i = (int64_t)blk * 256 + tid; i < n; i += (int64_t)nblk * 256) { const float d = pp[i] - tt[i]; s += (double)(d * d); }
-    s = wave_sum_d(s);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) part[(int64_t)b * nblk + blk] = ((red[0] + red[1]) + red[2]) + red[3];
+    s = block_sum4(wave_sum_d(s), red);
+    if (tid == 0) part[(int64_t)b * nblk + blk] = s;
 }
 __global__ void mse_finish_kernel(const double* __restrict__ part, int nblk, int64_t n, float* __restrict__ loss, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -547,7 +521,7 @@ __global__ void silu_kernel(const float* __restrict__ x, const float* __restrict
 // (mean, rstd) per (sample, group) of fp32 rows — the statistics the GroupNorm forward used, for the backward pass.
 __global__ __launch_bounds__(256) void gn_stat_f32_kernel(const float* __restrict__ X, int64_t ldx, int rows, int C, int groups, float eps,
                                                            float* __restrict__ stat) {
-    __shared__ double ra[4], rb[4];
+    __shared__ double red[4][2];
     const int smp = blockIdx.x / groups, g = blockIdx.x - smp * groups, cpg = C / groups, tid = threadIdx.x;
     double a = 0.0, b = 0.0;
     const int64_t n = (int64_t)rows * cpg;
@@ -557,16 +531,9 @@ __global__ __launch_bounds__(256) void gn_stat_f32_kernel(const float* __restric
         a += (double)x; b += (double)x * (double)x;
     }
     a = wave_sum_d(a); b = wave_sum_d(b);
-    if ((tid & 63) == 0) { ra[tid >> 6] = a; rb[tid >> 6] = b; }
+    if ((tid & 63) == 0) { red[tid >> 6][0] = a; red[tid >> 6][1] = b; }
     __syncthreads();
-    if (tid == 0) {
-        a = ((ra[0] + ra[1]) + ra[2]) + ra[3]; b = ((rb[0] + rb[1]) + rb[2]) + rb[3];
-        const double mean = a / (double)n;
-        double var = b / (double)n - mean * mean;
-        if (var < 0.0) var = 0.0;
-        stat[blockIdx.x * 2] = (float)mean;
-        stat[blockIdx.x * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+    if (tid == 0) store_mean_rstd(fold4(red, 0), fold4(red, 1), (double)n, eps, stat + blockIdx.x * 2);
 }
 // Inverted dropout with a counter-based mask: keep(i) depends on (seed, i) only, so the backward pass regenerates the mask
 // instead of storing it.  splitmix64 finaliser; 24 random bits against the keep probability.

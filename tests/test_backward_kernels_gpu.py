@@ -1,7 +1,9 @@
 """Every backward kernel of the training step (csrc/wgrad.hip, attention_bwd.hip, train.hip, optim.hip) called through its own C-ABI entry
 and held to the plain fp64 definition in tests/backward_reference.py — evaluated on the very operands the kernel reads (made on the
 CPU, rounded to the operand type once, the same values widened to fp64 for the reference), at shapes read off each kernel's dispatch
-and tiling code.
+and tiling code.  What reaches what in csrc/rows_shared.h, the steps train.hip shares with norm.hip and misc.hip: fold4 through
+group_colsum_kernel and gn_bwd_partial_kernel, block_sum4 through softmax_bwd_kernel and mse_partial_kernel, softmax_row_walk through
+softmax_f32_kernel, store_mean_rstd through gn_stat_f32_kernel, gn_bwd_dz / silu_grad through gn_bwd_partial_kernel and gn_bwd_apply_kernel.
 
   exact      small-integer operands (-3 .. 3) make every product and every partial sum an integer below 2^24, which fp32 holds
              exactly: torch.equal, so one misplaced, dropped or doubled term fails.  Each test asserts its magnitude condition.

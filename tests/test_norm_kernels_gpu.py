@@ -6,7 +6,9 @@ bf16 directly, in fp16 / bf16x3 / bf16x6 in the mode children (tests/test_precis
 the variant children (tests/test_gemm_variants_gpu.py, VARIANTS_NORM).  tests/test_norm_reference_cpu.py proves, without a GPU, that the
 exact cases are exact and that every row of the case tables reaches the clause written next to it.
 
-What reaches what (norm.hip):
+What reaches what (norm.hip; the steps its kernels share with misc.hip and train.hip — the storage kinds Kind<h16 | float | StreamH>, the
+host's with_kind dispatch, pin_requests, fold4 / block_sum4 / block_max4, store_mean_rstd, gn_affine_act, load_affine8, ln_apply1 / 8,
+softmax_row_walk — are written once in csrc/rows_shared.h and are reached through every kernel below that uses them):
   gn_stats_kernel<h16 | float | StreamH>   test_groupnorm_exact: GN_EXACT (kind column): empty trailing chunks r1000 / r2047, the 1024-chunk
                                            clamp r70000, idle row classes nvp 40 / 80 / 120 (c320, c2560, c960), nvp 1 (c2056), nvp 240 with
                                            one row class (c1920), nvp 7 (c4088), two sources x2_*; ragged shapes in all three kinds.
@@ -672,7 +674,7 @@ def test_layout_conversions(cuda):
         assert bool(torch.isnan(got[:, :, :t0].float()).all() and torch.isnan(got[:, :, t0 + t:].float()).all()), (name, "frames outside the window")
 
 
-# (name, cols, source gap, destination gap, source offset, destination offset): the clause of launch_cast_rows2 that decides VEC
+# (name, cols, source gap, destination gap, source offset, destination offset): the clause of launch_cast_rows that decides VEC
 CAST_FORMS = [("vec", 24, 8, 16, 0, 0), ("cols % 8", 21, 8, 8, 0, 0), ("source base + 1", 24, 8, 8, 1, 0), ("destination base + 1", 24, 8, 8, 0, 1),
               ("ld % 8", 24, 3, 8, 0, 0)]
 CAST_VEC = {"vec": True, "cols % 8": False, "source base + 1": False, "destination base + 1": False, "ld % 8": False}
