@@ -332,8 +332,8 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
     // DMA geometry (dma_offsets): wave w stages rows [16w, 16w + 16) of both tiles, two 1-KiB instructions each.
     // (F8 K tile: ONE instruction per wave, row 16w + (l >> 2), slot l & 3.)
     const __amdgpu_buffer_rsrc_t rK = F8 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(K8p), 0, (int)0x80000000u, 0x00020000)
-                                         : attn_rsrc(kv.Kp);
-    const __amdgpu_buffer_rsrc_t rV = attn_rsrc(kv.Vp);
+                                         : make_rsrc(kv.Kp);
+    const __amdgpu_buffer_rsrc_t rV = make_rsrc(kv.Vp);
     unsigned vk[2], vv[2];
     dma_offsets(wave, lane, p.ldk, p.ldvt, vk, vv);
     int kscale_off[2] = {0, 0};      // F8: byte offsets (inside a tile) of this lane's K scales for sub-tiles 0 / 1
@@ -349,13 +349,13 @@ __global__ __launch_bounds__(256, 2) void attn64d_kernel(const MudgAttnDesc p, c
         const int sv = kt * 128;
         if constexpr (F8) {
             unsigned char* ks8 = reinterpret_cast<unsigned char*>(Ks);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (attn_lptr_t)(ks8 + buf * 4096 + (16 * wave) * 64), 16, (int)vk[0], kt * 64 * p.ldk8, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (lptr_t)(ks8 + buf * 4096 + (16 * wave) * 64), 16, (int)vk[0], kt * 64 * p.ldk8, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if constexpr (!F8)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (attn_lptr_t)(Ks + buf * DTILE + (16 * wave + 8 * i) * 64), 16, (int)vk[i], kt * 64 * p.ldk * 2, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rV, (attn_lptr_t)(Vs + buf * DTILE + (16 * wave + 8 * i) * 64), 16, (int)vv[i], sv, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (lptr_t)(Ks + buf * DTILE + (16 * wave + 8 * i) * 64), 16, (int)vk[i], kt * 64 * p.ldk * 2, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rV, (lptr_t)(Vs + buf * DTILE + (16 * wave + 8 * i) * 64), 16, (int)vv[i], sv, 0, 0);
         }
     };
     const int sw = (l31 >> 1) & 7;          // read-side swizzle (row bases are multiples of 32)
@@ -988,7 +988,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_dma_kernel(const MudgAttnDe
     for (int pl = 0; pl < 2; ++pl) load_q_frags(qf[pl], Qp, q, p.ldq, pl * psq, qok, hi);
 
     // DMA geometry (dma_offsets): wave w stages rows [16w, 16w + 16) of the four tiles, two 1-KiB instructions each
-    const __amdgpu_buffer_rsrc_t rK = attn_rsrc(kv.Kp), rV = attn_rsrc(kv.Vp);
+    const __amdgpu_buffer_rsrc_t rK = make_rsrc(kv.Kp), rV = make_rsrc(kv.Vp);
     unsigned vk[2], vv[2];
     dma_offsets(wave, lane, p.ldk, p.ldvt, vk, vv);
     auto request = [&](int kt, int buf) {
@@ -996,9 +996,9 @@ __global__ __launch_bounds__(256, 2) void attn_split_dma_kernel(const MudgAttnDe
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (attn_lptr_t)(Ks + (buf * 2 + pl) * SDT + (16 * wave + 8 * i) * 64), 16, (int)vk[i],
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rK, (lptr_t)(Ks + (buf * 2 + pl) * SDT + (16 * wave + 8 * i) * 64), 16, (int)vk[i],
                                                          (kt * 64 * p.ldk + pl * kv.psk) * 2, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rV, (attn_lptr_t)(Vs + (buf * 2 + pl) * SDT + (16 * wave + 8 * i) * 64), 16, (int)vv[i],
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rV, (lptr_t)(Vs + (buf * 2 + pl) * SDT + (16 * wave + 8 * i) * 64), 16, (int)vv[i],
                                                          (kt * 64 + pl * kv.psv) * 2, 0, 0);
             }
     };

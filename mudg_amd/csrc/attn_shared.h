@@ -271,11 +271,7 @@ __device__ __forceinline__ void finish_block16(const MudgAttnDesc& p, int f, int
     if (qok) store_o16(o, inv, Op + (int64_t)q * p.ldo, hi, p.accumulate);
 }
 
-// ---- LDS-DMA staging (attn64d_kernel, attn_split_dma_kernel; the layout is described at attn64d_kernel) ----
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t attn_rsrc(const h16* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(base), 0, (int)0x80000000u, 0x00020000);
-}
-typedef __attribute__((address_space(3))) void* attn_lptr_t;
+// ---- LDS-DMA staging (attn64d_kernel, attn_split_dma_kernel; the layout is described at attn64d_kernel; make_rsrc, lptr_t: common.h) ----
 // The involution that swaps the two middle 4-blocks of every 16 rows: LDS row `row` of a K tile holds key swap_mid4(row).
 __device__ __forceinline__ int swap_mid4(int row) {
     const int i16 = row & 15;

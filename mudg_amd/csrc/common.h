@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mudg_hip.h"
+#include "tile_order.h"
 
 // h16 = the 16-bit MFMA operand type of this build: bfloat16 by default (libmudg_hip.so), IEEE half when compiled
 // with -DMUDG_OPERAND_FP16 (libmudg_hip_fp16.so).  Same MFMA rate, same bytes; fp16 has three more mantissa bits
@@ -171,12 +172,19 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
-// XCD-aware numbering of a 1-D grid of `total` workgroups: hardware places block b on XCD b % 8; give each XCD a contiguous
-// range of work items, so that neighbouring items (the query tiles of one (frame, head)) run on one XCD and share its L2.
+// XCD-aware numbering of a 1-D grid of `total` workgroups, one work item each (xcd_range, tile_order.h): neighbouring items (the
+// query tiles of one (frame, head), the tiles of an 8-row group) run on one XCD and share its L2.
 __device__ __forceinline__ int xcd_work_item(int total) {
-    const int q8 = total >> 3, r8 = total & 7;
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    return xcd_range(total, xcd).first + idx;
+}
+
+// ---- LDS-DMA (buffer_load ... lds) plumbing of every kernel that stages through it ----
+typedef __attribute__((address_space(3))) void* lptr_t;
+// voffset of a lane whose source row / tap does not exist: at num_records, so the buffer load returns 0 into the LDS.
+constexpr unsigned OOB = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const h16* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(base), 0, (int)0x80000000u, 0x00020000);
 }
 
 // ---- host side ---------------------------------------------------------------------------------

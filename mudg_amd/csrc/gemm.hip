@@ -113,25 +113,10 @@ __global__ __launch_bounds__(G::NTH, G::WIDE ? 2 : ((SB && !fused_planes(FAST)) 
     const int wm = wave % G::WM, wn = wave / G::WM;
     const int l31 = lane & 31, hi = lane >> 5;
 
-    // XCD-aware tile numbering: hardware puts workgroup b on XCD b % 8; give every XCD a contiguous tile range.
+    // XCD-aware tile numbering, 8-row groups inside an XCD's range (tile_order.h)
     const int ntn = (p.N + BN - 1) / BN;
-    int tile;
-    {
-        const int total = gridDim.x, q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
-    // Tile order inside the XCD's range: groups of 8 tile rows, column by column, so that the ~64 tiles an XCD runs at
-    // once form an 8 x 8 patch (16 operand panels through its L2) instead of one 1 x 64 strip (65 panels) when N is wide.
-    int tm, tn;
-    {
-        const int ntm = (p.M + BM - 1) / BM;
-        const int per = 8 * ntn, g = tile / per, first = g * 8;
-        const int gsz = (ntm - first) < 8 ? (ntm - first) : 8;
-        const int r = tile - g * per;
-        tn = r / gsz;
-        tm = first + (r - tn * gsz);
-    }
+    const TileMN tl = group8_tile(xcd_work_item(gridDim.x), (p.M + BM - 1) / BM, ntn);
+    const int tm = tl.tm, tn = tl.tn;
     const int m0 = tm * BM, n0 = tn * BN;
     // TMAP (temporal convs of 16-frame clips, slab-major K; host flag VF_TM): tile tm is NOT 128 consecutive rows but 8 pixels x 16
     // frames of one clip — logical row r of the tile is frame r / 8, pixel r % 8 — so that the three temporal taps of an output row

@@ -1,6 +1,6 @@
-// gemm_shared.h — what the contraction kernels of gemm.hip, pgemm.hip, wgemm.hip and sgemm.hip have in common: K-tile geometry, the buffer-descriptor
-// helpers of the LDS-DMA loader, the GELU forms and the row steps of the epilogues (one site per rule), and the kernel plan (GemmPlan) that
-// gemm.hip makes and the launchers take.
+// gemm_shared.h — what the contraction kernels of gemm.hip, pgemm.hip, wgemm.hip and sgemm.hip have in common: K-tile geometry, the GELU forms
+// and the row steps of the epilogues (one site per rule), and the kernel plan (GemmPlan) that gemm.hip makes and the launchers take.
+// The tile order is tile_order.h's, the LDS-DMA descriptor helpers are common.h's, the main-loop steps of the DMA-staged tiles tile_shared.h's.
 #pragma once
 #include "common.h"
 #include <type_traits>
@@ -12,7 +12,6 @@ constexpr int VF_TM = 8;                        // temporal conv: a tile is 8 pi
 constexpr int VF_XS = 4;                        // 3x3 conv: the three dx taps of a dy share one staged activation tile (gemm.hip, XSHARE)
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // bf16x3 build, descriptor loader (FUSED): ONE K-tile stage holds both pieces of both operands (see gemm.hip).
 constexpr bool fused_planes(bool fast) { return PLANES == 2 && fast; }
@@ -30,13 +29,6 @@ __device__ __forceinline__ float gelu_fast(float x) {
     p = fmaf(p, t, 0.254829592f);
     const float e = 1.0f - p * t * __expf(-z * z);          // erf(|x| / sqrt 2)
     return 0.5f * x * (1.0f + copysignf(e, x));
-}
-
-// voffset of a lane whose source row / tap does not exist: at num_records, so the buffer load returns 0 into the LDS.
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const h16* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(base), 0, (int)0x80000000u, 0x00020000);
 }
 
 // GEGLU's gate: gelu(x) = x Phi(x) with Phi linearly interpolated from a 1025-entry table over [-8, 8] held in LDS

@@ -105,9 +105,11 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
         const int total = per_batch * p.batch;
         const int q8 = total >> 3, r8 = total & 7;
         const int xcd = blockIdx.x & 7;
-        const int lo = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+        const int lo = xcd_range(total, xcd).first;
         t_step = ((int)gridDim.x - xcd + 7) >> 3;
         t_next = lo + (int)(blockIdx.x >> 3);
+        // = lo + xcd_range's count, kept in THIS summation order: as lo + (q8 + ..) the compiler moves its own vmcnt waits across DMA
+        // issues in six bf16x3 instances (profiles/tile_shared/isa.txt)
         t_end = lo + q8 + (xcd < r8 ? 1 : 0);
     }
     if (t_next >= t_end) return;
@@ -132,14 +134,8 @@ __global__ __launch_bounds__(256, FUSEDP ? 2 : WGS) void pgemm_kernel(const Mudg
     auto setup = [&](int t) {
         const int z = t / per_batch;
         const int tile = t - z * per_batch;
-        int tm, tn;
-        {
-            const int per = 8 * ntn, g = tile / per, first = g * 8;
-            const int gsz = (ntm - first) < 8 ? (ntm - first) : 8;
-            const int r = tile - g * per;
-            tn = r / gsz;
-            tm = first + (r - tn * gsz);
-        }
+        const TileMN tl = group8_tile(tile, ntm, ntn);
+        const int tm = tl.tm, tn = tl.tn;
         m0 = tm * 128; n0 = tn * 128; zb = z;
         dy0 = subp ? (z >> 1) : 0; dx0 = subp ? (z & 1) : 0;
         const h16* X = reinterpret_cast<const h16*>(p.X) + (int64_t)z * p.sX;

@@ -6,11 +6,11 @@
 //
 // Workgroup: persistent, one per CU, four waves (one per SIMD, 512 registers each); it owns one contiguous range of 64-row tiles and never
 // talks to another workgroup.  Wave w owns 80 output columns — the two fragment pairs at 64 w (a lane's 2 x 4 accumulator registers of a
-// pair are 8 consecutive channels: W's rows are fetched with the row permutation of wgemm.hip) and the unpaired fragment at 256 + 16 w —
+// pair are 8 consecutive channels: W's rows are fetched with the row permutation of tile_shared.h) and the unpaired fragment at 256 + 16 w —
 // as 5 column blocks x 10 k steps of v_mfma_f32_16x16x32 = 200 registers of W fragments, loaded once (behind the requests for the range's
 // first two tiles, so that both are in flight together).  N = 640: two such slices of W, each with half the workgroups (work numbering below).
 //
-// X: an LDS ring of three 64 x 320 tiles (40 KiB each), filled by LDS-DMA with the source-side XOR swizzle of wgemm.hip (a 16 x 32
+// X: an LDS ring of three 64 x 320 tiles (40 KiB each), filled by LDS-DMA with the source-side XOR swizzle of tile_shared.h (a 16 x 32
 // subtile of 1 KiB = one DMA piece = one fragment, conflict-free ds_read_b128); wave w stages row block w of a tile (10 pieces).  Tile
 // t + 2 is requested when tile t starts: 80 KiB of X are in flight while a tile is multiplied.
 // Residual: it seeds the accumulators, as in w_seed (fp16 -> fp32 is exact; the sum is ((r + x w) + bias), the 288-row tile's).  It comes
@@ -34,7 +34,7 @@
 // Bits.  Per output element: the accumulator seeded with the residual, k steps of 32 in ascending K with the operands in wgemm_kernel's
 // order, then alpha, bias, one rounding — the 288-row tile's sum exactly, so which of the two runs a problem changes no bit
 // (tests/test_gemm_stream_gpu.py).  GroupNorm partials are not produced: problems with `stats` stay on the 288-row tile.
-#include "gemm_shared.h"
+#include "tile_shared.h"
 
 #if MUDG_PLANES == 1
 namespace {
@@ -56,21 +56,6 @@ static_assert(X_DMA == 10 && STORES == 10 && R_DMA == 10, "S_WAIT_FIRST / S_WAIT
 #define S_WAIT_FIRST() asm volatile("s_waitcnt vmcnt(10)" ::: "memory")
 #define S_WAIT_TILE() asm volatile("s_waitcnt vmcnt(20)" ::: "memory")
 #define S_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define S_BARRIER()                            \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
-
-__device__ __forceinline__ f32x4 s_mfma(h16x8 a, h16x8 b, f32x4 c) {
-#ifdef MUDG_OPERAND_FP16
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-#else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-#endif
-}
-
 // HASR: a residual; RF16 / YF16: it / the result is the fp16 stream (else operand storage) — constants, so that no piece branches on a kind
 template <bool HASR, bool RF16, bool YF16>
 __global__ __launch_bounds__(256, 1) void sgemm_kernel(const MudgGemmDesc p, const int ntiles, const int nslices) {
@@ -91,13 +76,11 @@ __global__ __launch_bounds__(256, 1) void sgemm_kernel(const MudgGemmDesc p, con
     const int cpair = n0 + 64 * wave + 8 * q4;            // first channel of the lane's piece of pair 0 (pair 1: + 32)
     const int csingle = n0 + 256 + 16 * wave;             // the wave's unpaired fragment
 
-    // ---- X pieces: lane l writes byte 16 l of a subtile and fetches the element whose swizzled position that is (wgemm.hip)
-    const int pos = lane * 16;
-    const int sbyte = pos ^ (((pos >> 9) & 1) << 5);
-    const int srow = sbyte >> 6, schunk = (sbyte >> 4) & 3;
+    // ---- X pieces: subtiles with the lane geometry of tile_shared.h
+    const DmaLane dl(lane);
     const h16* X = reinterpret_cast<const h16*>(p.X);
-    const unsigned vx = (unsigned)(srow * p.ldx) * 2u + (unsigned)schunk * 16u;
-    const int xrow = 16 * wave + srow;                    // the tile row this lane stages
+    const unsigned vx = dl.x_off(p.ldx);
+    const int xrow = 16 * wave + dl.srow();               // the tile row this lane stages
     const int xsoff = 16 * wave * p.ldx * 2;
     char* const xdst = smem + wave * S_KS * 1024;
     auto issue_x = [&](const int t, const int slot) {
@@ -171,9 +154,7 @@ __global__ __launch_bounds__(256, 1) void sgemm_kernel(const MudgGemmDesc p, con
         }
     };
 
-    // fragment reads: lane l holds row l % 16, 16-byte k chunk l / 16 of a subtile
-    const int fbyte0 = px * 64 + q4 * 16;
-    const int fbyte = fbyte0 ^ (((fbyte0 >> 9) & 1) << 5);
+    const int fbyte = DmaLane::frag_byte(lane);
     const float alpha = p.alpha;
     h16* Y = reinterpret_cast<h16*>(p.Y);
     const unsigned vyp = (unsigned)(px * p.ldy + cpair) * 2u, vys = (unsigned)(hrow * p.ldy + hcol) * 2u;
@@ -213,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void sgemm_kernel(const MudgGemmDesc p, con
     int slot = 0;
     for (int t = t0; t < t1; ++t) {
         if (t == t0) S_WAIT_FIRST(); else S_WAIT_TILE();
-        S_BARRIER();
+        W_BARRIER();
         f32x4 acc[S_RB][S_NB];
         if constexpr (HASR) {
             seed(acc);
@@ -234,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void sgemm_kernel(const MudgGemmDesc p, con
             for (int s = 0; s < S_KS; ++s) {
                 const h16x8 xf = *reinterpret_cast<const h16x8*>(xs + (i * S_KS + s) * 1024);
 #pragma unroll
-                for (int j = 0; j < S_NB; ++j) acc[i][j] = s_mfma(wf[j][s], xf, acc[i][j]);      // operands as in wgemm_kernel
+                for (int j = 0; j < S_NB; ++j) acc[i][j] = mfma16(wf[j][s], xf, acc[i][j]);      // operands as in wgemm_kernel
             }
 
         // ---- epilogue: alpha acc + bias, one rounding, 16-byte stores

@@ -3,6 +3,10 @@
 // Plain GEMM, same-size 3x3 conv and temporal 3-tap conv (descriptor loader, 16-bit builds).  MudgGemmDesc semantics: mudg_hip.h.
 // Also in this file: the persistent form of the tile (wgemm_pkernel), the two-workgroup 144 x 256 GEGLU kernel (hgeglu_kernel, round 6: a
 // measured negative, rule "never") and the 160 x 320 tile for frames of whole 160-row tiles (wq_kernel, round 6) — each under its own header.
+// What the four kernels (and sgemm.hip's) must do alike is written once in tile_shared.h and called from here: the tile order (tile_order.h), the
+// DMA lane geometry and fragment offset of the st_16x32 subtile (DmaLane), the permuted-W-row rule of a piece (w_piece_row0), the tap masks
+// (tap_mask), the K-tile order (k_advance), the source of an X piece (x_source), the Phi pairs (phi_pairs_to_lds) and the six-phase K-tile
+// itself (Frag288, ktile_six).  A kernel here is its loop skeleton, its staging function and its counted waits.
 //
 // Why this tile.  (1) One workgroup per CU wants the tile count to be a multiple of the 256 CUs, and 288 rows make it one at
 // every level of the benchmarked resolution: a frame is 9216 / 2304 / 576 pixels = 32 / 8 / 2 x 288, so a guidance batch of
@@ -58,8 +62,7 @@
 // MFMAs (the 16-bit loop's shape, w0 x1 | w0 x0 | w1 x0 per row third) 398-444 TFLOP/s on the 3x3 convs, six phases (30 30 30 15 15 15)
 // 422-468, these three 468-521 (= 1400-1560 TFLOP/s of MFMA work; the 128 x 128 fused-piece kernels: 345-415): what a barrier slot
 // costs beside its MFMAs (~140 cycles) is amortised over three times as many of them.
-#include "gemm_shared.h"
-#include <type_traits>
+#include "tile_shared.h"
 
 #if MUDG_PLANES <= 2
 namespace {
@@ -77,12 +80,6 @@ template <int NREP> struct WGeo {
     static constexpr int SMEM = LOOP + (NREP == 4 ? W_TAIL_GEGLU : W_TAIL);
 };
 
-#define W_BARRIER()                            \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
 #define W_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 // Debug-variants build only: s_memtime stamps of wave 0 of every workgroup at the phase boundaries of the GEGLU kernels (tools/exp_stamps.py).
 #ifdef MUDG_DEBUG_VARIANTS
@@ -93,13 +90,6 @@ template <int NREP> struct WGeo {
 #endif
 #define H_LGKM0() __builtin_amdgcn_s_waitcnt(0xC07F)        /* s_waitcnt lgkmcnt(0) (vmcnt, expcnt untouched) as the compiler-visible builtin */
 
-__device__ __forceinline__ f32x4 mfma16(h16x8 a, h16x8 b, f32x4 c) {
-#ifdef MUDG_OPERAND_FP16
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-#else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-#endif
-}
 // The same instruction with the accumulator tied to its result register: in the bf16x3 loop (224 live accumulator and fragment
 // registers under branches) the register allocator otherwise splits accumulator live ranges — copies at every phase, then spills.
 __device__ __forceinline__ void mfma16_inplace(h16x8 a, h16x8 b, f32x4& c) {
@@ -123,12 +113,6 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
-// Which columns of a tile a wave column owns.  A wave's NREP fragments are NREP / 2 PAIRS (32 channels: a lane's 2 x 4 accumulator
-// registers are 8 consecutive ones, a 16-byte piece of a 16-bit result row) and, on the 320-wide tile, one unpaired fragment (16
-// channels, 8-byte pieces).  The pairs of all four wave columns come first, 32 channels each — so every 16-byte-per-lane store (four
-// lanes = 64 contiguous bytes) starts on a 64-byte boundary of the row and the two pairs of a wave fill one 128-byte line; the four
-// unpaired fragments follow at channel 256.  (A wave column as 80 CONSECUTIVE channels put the pieces of the odd wave columns across
-// sector boundaries: the epilogue ran at half the store / residual-fetch rate.)  Free: which W rows a wave's fragments fetch.
 // GEGLU's gate through the Phi table of gemm_shared.h held as PAIRS (Phi_i, Phi_{i+1} - Phi_i): one 8-byte LDS read per value instead of two
 // 4-byte ones, v_fract instead of a conversion back and a subtraction — 8 instead of 11 vector instructions, the same bits as gelu_lut
 // (the step is the same fp32 difference, taken once when the workgroup copies the table).
@@ -155,8 +139,6 @@ __device__ __forceinline__ float gelu_hermite(float x, const f32x2* __restrict__
     r = fmaf(t, r, n0[0]);
     return x * r;
 }
-template <int NREP> __device__ __forceinline__ int wave_pair_col(int wc, int pair) { return 32 * ((NREP / 2) * wc + pair); }
-template <int NREP> __device__ __forceinline__ int wave_single_col(int wc) { return 32 * (NREP / 2) * 4 + 16 * wc; }
 
 // A residual as the accumulators' INITIAL VALUE (alpha = 1, host-checked): its 27 pieces per lane are requested when the tile starts — no
 // accumulator is live yet, so all of them are in flight at once, next to the first K-tiles' DMA — instead of three dependent rounds of nine
@@ -260,7 +242,6 @@ __device__ __forceinline__ void w_epilogue(const MudgGemmDesc& p, f32x4 (&acc)[N
                                            const int lane, const int tid, float* tail, const float* __restrict__ phi,
                                            const u32x4 (*sraw)[2] = nullptr, const u32x2* srs = nullptr) {
     constexpr int WBN = 64 * NREP, NPAIR = NREP / 2;
-    using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>;
     const int px = lane & 15, q4 = lane >> 4;
     const float alpha = p.alpha;
     const int OK = p.out_fp32;
@@ -410,8 +391,6 @@ __device__ __forceinline__ void w_epilogue(const MudgGemmDesc& p, f32x4 (&acc)[N
     }
 }
 
-struct KPos { int kt, tap, c; };                         // a K-tile: its index along W's K axis, its tap and first input channel
-
 // NREP = 5: 288 x 320 (every channel count of the UNet is a multiple of 320); NREP = 4 + GEGLU: 288 x 256, a wave's four fragments are
 // one [32 value | 32 gate] block of the packed GEGLU weights.
 template <int MODE, int NREP, bool GEGLU>
@@ -426,47 +405,20 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
 #else
     constexpr bool SIX = PLANES == 1;
 #endif
-    constexpr int NPAIR = NREP / 2;                      // fragment pairs whose 2 x 4 accumulator registers are 8 consecutive channels
     static_assert(!GEGLU || (MODE == 0 && NREP == 4), "GEGLU: plain GEMM on the 256-wide tile");
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;             // waves wc and wc + 4 share a SIMD: the two M halves
     float* tail = reinterpret_cast<float*>(smem + G::LOOP);
-    if (GEGLU && phi) {                                  // visible after the K loop's barriers
-        for (int t = tid; t <= PHI_N; t += 512) {         // entry PHI_N exists (x = 8); its step is never used (u < 1024)
-            const float a = phi[t], b = phi[t < PHI_N ? t + 1 : t];
-            if constexpr (PLANES == 2) {                 // (value, slope x node distance): gelu_hermite
-                const float xt = -8.0f + (float)t * (1.0f / 64.0f);
-                *reinterpret_cast<f32x2*>(&tail[2 * t]) = f32x2{a, expf(-0.5f * xt * xt) * (0.3989422804014327f / 64.0f)};
-            } else *reinterpret_cast<f32x2*>(&tail[2 * t]) = f32x2{a, b - a};
-        }
-    }
+    if (GEGLU && phi) phi_pairs_to_lds<512>(tail, phi, tid);
 
-    // XCD-aware tile numbering (gemm.hip): every XCD a contiguous tile range, walked in 8-row groups column by column
     const int ntn = p.N / WBN, ntm = (p.M + WBM - 1) / WBM;
-    int tile;
-    {
-        const int total = gridDim.x, q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
-    int tm, tn;
-    {
-        const int per = 8 * ntn, g = tile / per, first = g * 8;
-        const int gsz = (ntm - first) < 8 ? (ntm - first) : 8;
-        const int r = tile - g * per;
-        tn = r / gsz;
-        tm = first + (r - tn * gsz);
-    }
+    const TileMN tl = group8_tile(xcd_work_item(gridDim.x), ntm, ntn);
+    const int tm = tl.tm, tn = tl.tn;
     const int m0 = tm * WBM, n0 = tn * WBN;
-    constexpr int ntaps = MODE == 0 ? 1 : (MODE == 1 ? 9 : 3);
 
-    // DMA lane geometry: lane l writes byte 16 l of a subtile (lane-linear) and therefore fetches the element whose swizzled position
-    // that is: row srow, 16-byte chunk schunk of the 16 x 32 subtile
-    const int pos = lane * 16;
-    const int sbyte = pos ^ (((pos >> 9) & 1) << 5);
-    const int srow = sbyte >> 6, schunk = (sbyte >> 4) & 3;
+    const DmaLane dl(lane);
     const h16* X = reinterpret_cast<const h16*>(p.X);
     const h16* X2 = p.X2 ? reinterpret_cast<const h16*>(p.X2) : nullptr;
     const h16* W = reinterpret_cast<const h16*>(p.W);
@@ -476,14 +428,8 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
     const __amdgpu_buffer_rsrc_t rX2 = X2 ? make_rsrc(X2 + ((int64_t)m0 + shift) * p.ldx2) : rX;
     const __amdgpu_buffer_rsrc_t rW = make_rsrc(W + (int64_t)n0 * p.ldw);
     const int ldx2e = X2 ? p.ldx2 : p.ldx;
-    const unsigned va1 = (unsigned)(srow * p.ldx) * 2u + (unsigned)schunk * 16u;
-    const unsigned va2 = (unsigned)(srow * ldx2e) * 2u + (unsigned)schunk * 16u;
-    // W rows are fetched PERMUTED, so that the epilogue can leave the accumulators in 16-byte pieces: subtile j of a wave column
-    // (j = 2 p + odd) holds in its row r = 4 q + e the channel 32 p + 8 q + 4 odd + e of the wave's 16 NREP columns — lane (pixel, q) of
-    // the MFMA result then owns, over the fragment pair p, the 8 CONSECUTIVE channels 32 p + 8 q .. + 7.  The fifth fragment of the
-    // 320-wide tile has no partner and keeps its rows (4 consecutive channels per lane).  Free: a row permutation of the source.
-    const unsigned vw_pair = (unsigned)((8 * (srow >> 2) + (srow & 3)) * p.ldw) * 2u + (unsigned)schunk * 16u;
-    const unsigned vw_single = (unsigned)(srow * p.ldw) * 2u + (unsigned)schunk * 16u;
+    const unsigned va1 = dl.x_off(p.ldx), va2 = dl.x_off(ldx2e);
+    const unsigned vw_pair = dl.w_off_pair(p.ldw), vw_single = dl.w_off_single(p.ldw);      // (permuted W rows: tile_shared.h)
     // this wave's pieces per k half.  W (4 NREP subtiles per piece) over the eight waves as 2 3 3 2 | 2 3 3 2 (NREP 5) or two each
     // (NREP 4).  X: a row third (3 subtiles) per staging point over the waves wc = 0, 1, 2 (slot q of amask = third q); the six-phase
     // loop (SIX, kept for A/B measurements) — the X half wr (9 subtiles) over its four waves as 3 2 2 2
@@ -495,36 +441,9 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
     unsigned amask[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        const int m = m0 + (wr * 9 + a_first + q * a_step) * 16 + srow;
-        unsigned mask = 0;
-        if (q < a_cnt && m < p.M) {
-            if (MODE == 0) mask = 1;
-            else if (MODE == 1) {
-                const int hw = p.Hout * p.Wout;
-                const int f = m / hw, r = m - f * hw;
-                const int oy = r / p.Wout, ox = r - oy * p.Wout;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int iy = oy - 1 + t / 3, ix = ox - 1 + t % 3;
-                    if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) mask |= 1u << t;
-                }
-            } else {
-                const int fr = (m / p.HW) % p.T;
-#pragma unroll
-                for (int t = 0; t < 3; ++t) if (fr + t - 1 >= 0 && fr + t - 1 < p.T) mask |= 1u << t;
-            }
-        }
-        amask[q] = mask;
+        const int m = m0 + (wr * 9 + a_first + q * a_step) * 16 + dl.srow();
+        amask[q] = q < a_cnt ? tap_mask<MODE>(p, m) : 0u;
     }
-    auto advance = [&](KPos& k) {
-        k.kt += 1;
-        if (MODE == 0) { k.c += BK; return; }
-        const int t1 = k.tap + 1, c1 = k.c + BK;
-        const bool slab = p.korder != 0;
-        const bool wrap = slab ? (t1 == ntaps) : (c1 == p.Cin);
-        k.tap = slab ? (wrap ? 0 : t1) : (wrap ? t1 : k.tap);
-        k.c = slab ? (wrap ? c1 : k.c) : (wrap ? 0 : c1);
-    };
     W_STAMP(0);
     f32x4 acc[9][NREP];
     if (!GEGLU && p.R) w_seed<NREP, 9>(p, acc, m0, n0, wr, wc, lane);
@@ -534,25 +453,19 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
 #pragma unroll
             for (int j = 0; j < NREP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    // fragment reads: a 16 x 32 fragment is one subtile; lane l holds row l % 16, 16-byte k chunk l / 16
-    const int fbyte0 = (lane & 15) * 64 + (lane >> 4) * 16;
-    const int fbyte = fbyte0 ^ (((fbyte0 >> 9) & 1) << 5);
+    const int fbyte = DmaLane::frag_byte(lane);
     const char* a_base = smem + (wr * 9) * 1024 + fbyte;
     const char* b_base = smem + (WNA + wc * NREP) * 1024 + fbyte;
 
-    using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>; using T2 = std::integral_constant<int, 2>;
     const int nk = p.K / BK;
     if constexpr (SIX) {
         // part: 0 = all of this wave's pieces of k half ks of K-tile k, 1 = its X pieces, 2 = its W pieces
         auto stage = [&](const KPos& k, int ks, int buf, int part) {
             char* base = smem + buf * W_BUF + ks * W_KS;
             if (part != 2) {
-                const bool s2 = k.c >= p.csplit;
-                const int cc = s2 ? k.c - p.csplit : k.c;
-                const int ld = s2 ? ldx2e : p.ldx;
-                int soff = (cc + ks * 32) * 2;
-                if (MODE == 1) { const int dy = k.tap / 3, dx = k.tap - 3 * dy; soff += (dy * p.Win + dx) * ld * 2; }
-                if (MODE == 2) soff += k.tap * p.HW * ld * 2;
+                const XSource xs = x_source<MODE>(p, ldx2e, k.c, k.tap, ks);
+                const bool s2 = xs.s2;
+                const int ld = xs.ld, soff = xs.soff;
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
                     if (q < a_cnt) {
@@ -567,34 +480,17 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
                     if (q < b_cnt) {
-                        const int st = b_first + q, wcol = st / NREP, j = st - wcol * NREP;
-                        const bool single = j >= 2 * NPAIR;
-                        const int row0 = single ? wave_single_col<NREP>(wcol) : wave_pair_col<NREP>(wcol, j >> 1) + 4 * (j & 1);       // first channel of the piece
+                        const int st = b_first + q;
+                        const WPiece wp = w_piece_row0<NREP>(st);
+                        const int row0 = wp.row0;
+                        const bool single = wp.single;
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lptr_t)(base + (WNA + st) * 1024), 16, (int)(single ? vw_single : vw_pair),
                                                                  soffw + row0 * p.ldw * 2, 0, 0);
                     }
             }
         };
 
-        h16x8 af[3], bf[NREP];
-        auto read_a = [&](int buf, int ks, int third) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) af[i] = *reinterpret_cast<const h16x8*>(a_base + buf * W_BUF + ks * W_KS + (third * 3 + i) * 1024);
-        };
-        auto read_b = [&](int buf, int ks) {
-#pragma unroll
-            for (int j = 0; j < NREP; ++j) bf[j] = *reinterpret_cast<const h16x8*>(b_base + buf * W_BUF + ks * W_KS + j * 1024);
-        };
-        auto mma = [&](auto third_tag) {
-            constexpr int third = decltype(third_tag)::value;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);              // (register-only MFMAs may otherwise be hoisted above the wait)
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < NREP; ++j)              // operands swapped: a lane ends up with 4 consecutive (permuted) channels of one pixel
-                    acc[third * 3 + i][j] = mfma16(bf[j], af[i], acc[third * 3 + i][j]);
-        };
+        Frag288<NREP> fr;
         // "everything but the pieces issued after the k half that is about to be read": that half's successor (a_cnt + b_cnt pieces) plus
         // the W pieces of the one after (b_cnt, issued in this phase): 7 | 8 | 6 (NREP 5: wc 0 | 1, 2 | 3), 7 | 6 (NREP 4: wc 0 | others)
         auto wait_half = [&](bool more) {
@@ -607,10 +503,10 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
         KPos kA{0, 0, 0};
         stage(kA, 0, 0, 0);
         stage(kA, 1, 0, 0);
-        advance(kA);                                         // kA = K-tile t + 1, kB = K-tile t + 2 at the top of iteration t
+        k_advance<MODE>(p, kA);                                         // kA = K-tile t + 1, kB = K-tile t + 2 at the top of iteration t
         if (nk > 1) stage(kA, 0, 1, 0);
         KPos kB = kA;
-        advance(kB);
+        k_advance<MODE>(p, kB);
         if (nk <= 1) W_VMCNT(0); else if (a_cnt + b_cnt == 5) W_VMCNT(10); else W_VMCNT(8);      // ks 0 of tile 0 has landed
         W_BARRIER();
         W_STAMP(1);
@@ -619,46 +515,9 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
         for (int t = 0; t < nk; ++t) {
             const int buf = t & 1;
             const bool n1 = t + 1 < nk, n2 = t + 2 < nk;
-            // phase 0
-            read_b(buf, 0);
-            read_a(buf, 0, 0);
-            W_BARRIER();
-            mma(T0{});
-            W_BARRIER();
-            // phase 1
-            read_a(buf, 0, 1);
-            if (n1) stage(kA, 1, buf ^ 1, 2);
-            W_BARRIER();
-            mma(T1{});
-            wait_half(n1);                                   // ks 1 of tile t
-            W_BARRIER();
-            // phase 2
-            read_a(buf, 0, 2);
-            if (n1) stage(kA, 1, buf ^ 1, 1);
-            W_BARRIER();
-            mma(T2{});
-            W_BARRIER();
-            // phase 3
-            read_b(buf, 1);
-            read_a(buf, 1, 0);
-            W_BARRIER();
-            mma(T0{});
-            W_BARRIER();
-            // phase 4
-            read_a(buf, 1, 1);
-            if (n2) stage(kB, 0, buf, 2);
-            W_BARRIER();
-            mma(T1{});
-            wait_half(n2);                                   // ks 0 of tile t + 1
-            W_BARRIER();
-            // phase 5
-            read_a(buf, 1, 2);
-            if (n2) stage(kB, 0, buf, 1);
-            W_BARRIER();
-            mma(T2{});
-            W_BARRIER();
+            ktile_six<W_KS>(fr, acc, a_base + buf * W_BUF, b_base + buf * W_BUF, buf, n1, n2, stage, kA, kB, wait_half);
             kA = kB;
-            advance(kB);
+            k_advance<MODE>(p, kB);
         }
     } else {
         // ---------------------------------------------------------------- the three-phase loop (header): a UNIT is what one ring slot holds — a
@@ -669,7 +528,7 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
         // row | permuted W row << 8 | 16-byte chunk offset << 16, maskpk = the three row thirds' tap masks, 9 bits each; the byte offsets
         // are rebuilt per piece (two extractions + one multiply-add).  opaque(): without it every staging point's offset is hoisted out
         // of the loop as one more live register, they spill, and a reload between two DMA issues drains the ring.
-        const unsigned lanepk = (unsigned)srow | ((unsigned)(8 * (srow >> 2) + (srow & 3)) << 8) | ((unsigned)(schunk * 16) << 16);
+        const unsigned lanepk = dl.lanepk();
         const unsigned maskpk = amask[0] | (amask[1] << 9) | (amask[2] << 18);
         auto lane_off = [&](int rowshift, int ld2) -> unsigned {           // rowshift 0: the X / unpaired-W row, 8: the permuted W row
             const unsigned lp = opaque(lanepk);
@@ -682,12 +541,9 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
             if (wc >= 3) return;
             const int ks = PLANES == 2 ? kh : pc, plane = PLANES == 2 ? pc : 0;
             char* base = smem + slot * W_SLOT + pc * W_PL;
-            const bool s2 = k.c >= p.csplit;
-            const int cc = s2 ? k.c - p.csplit : k.c;
-            const int ld = s2 ? ldx2e : p.ldx;
-            int soff = (cc + ks * 32) * 2 + plane * ld;          // bf16 piece 1 of a row: ld / 2 elements further
-            if (MODE == 1) { const int dy = k.tap / 3, dx = k.tap - 3 * dy; soff += (dy * p.Win + dx) * ld * 2; }
-            if (MODE == 2) soff += k.tap * p.HW * ld * 2;
+            const XSource xs = x_source<MODE>(p, ldx2e, k.c, k.tap, ks, plane);
+            const bool s2 = xs.s2;
+            const int ld = xs.ld, soff = xs.soff;
             const int st = wr * 9 + 3 * third + wc;
             const unsigned v = ((opaque(maskpk) >> (9 * third + k.tap)) & 1u) ? lane_off(0, ld * 2) : OOB;
             if (s2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rX2, (lptr_t)(base + st * 1024), 16, (int)v, soff + st * 16 * ld * 2, 0, 0);
@@ -700,9 +556,10 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
 #pragma unroll
             for (int q = 0; q < 3; ++q)
                 if (q < b_cnt) {
-                    const int st = b_first + q, wcol = st / NREP, j = st - wcol * NREP;
-                    const bool single = j >= 2 * NPAIR;
-                    const int row0 = single ? wave_single_col<NREP>(wcol) : wave_pair_col<NREP>(wcol, j >> 1) + 4 * (j & 1);
+                    const int st = b_first + q;
+                    const WPiece wp = w_piece_row0<NREP>(st);
+                    const int row0 = wp.row0;
+                    const bool single = wp.single;
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lptr_t)(base + (WNA + st) * 1024), 16, (int)lane_off(single ? 0 : 8, p.ldw * 2),
                                                              soffw + row0 * p.ldw * 2, 0, 0);
                 }
@@ -753,7 +610,7 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
 
         const int NU = PLANES * nk;                          // units
         KPos kC{0, 0, 0}, kN{0, 0, 0};                       // bf16x3: the K-tile of unit u and the next one; 16-bit: the K-tiles of units u + 1 and u + 2
-        if constexpr (PLANES == 2) { advance(kN); } else { advance(kC); kN = kC; advance(kN); }
+        if constexpr (PLANES == 2) { k_advance<MODE>(p, kN); } else { k_advance<MODE>(p, kC); kN = kC; k_advance<MODE>(p, kN); }
         {   // units 0 and 1, in the order the loop would have issued them (the counted waits rely on it)
             const KPos k0{0, 0, 0};
             stage_w2(k0, 0, 0); stage_x2(k0, 0, 0, T0{});
@@ -778,7 +635,7 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(const MudgGemmDesc p, con
             reads(sb, 2, false);
             if (n2) { stage_w2(kN, slot, slot); stage_x2(kN, slot, slot, T0{}); }
             W_BARRIER(); multiply(T2{}); wait3(0, n2); W_BARRIER();
-            if (PLANES == 1 || slot) { kC = kN; advance(kN); }
+            if (PLANES == 1 || slot) { kC = kN; k_advance<MODE>(p, kN); }
         }
         // the MFMAs above are inline assembly: the compiler does not know that the epilogue's first reads depend on matrix results
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -810,29 +667,22 @@ __device__ __forceinline__ void w_vmcnt_runtime(int n) {          // n: wave-uni
     }
 }
 
+struct KSel { int sel, kt; };                          // a K-tile of the stream: of the current (sel 0) or the next (sel 1) tile, its index
 template <int NREP, bool GEGLU>
 __global__ __launch_bounds__(512, 2) void wgemm_pkernel(const MudgGemmDesc p, const int vflags, const float* __restrict__ phi, const int ntiles) {
     using G = WGeo<NREP>;
-    constexpr int WBN = G::BN, W_KS = G::KS, W_BUF = G::BUF, NPAIR = NREP / 2;
+    constexpr int WBN = G::BN, W_KS = G::KS, W_BUF = G::BUF;
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     float* tail = reinterpret_cast<float*>(smem + G::LOOP);
-    if (GEGLU && phi) {
-        for (int t = tid; t <= PHI_N; t += 512) {         // entry PHI_N exists (x = 8); its step is never used (u < 1024)
-            const float a = phi[t], b = phi[t < PHI_N ? t + 1 : t];
-            if constexpr (PLANES == 2) {                 // (value, slope x node distance): gelu_hermite
-                const float xt = -8.0f + (float)t * (1.0f / 64.0f);
-                *reinterpret_cast<f32x2*>(&tail[2 * t]) = f32x2{a, expf(-0.5f * xt * xt) * (0.3989422804014327f / 64.0f)};
-            } else *reinterpret_cast<f32x2*>(&tail[2 * t]) = f32x2{a, b - a};
-        }
-    }
+    if (GEGLU && phi) phi_pairs_to_lds<512>(tail, phi, tid);
     // this workgroup's tiles: the XCD's contiguous range of the one-tile kernel's numbering, every (gridDim / 8)-th tile of it
     const int ntn = p.N / WBN, ntm = p.M / WBM;
-    const int xcd = blockIdx.x & 7, stride = gridDim.x >> 3;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8, count = q8 + (xcd < r8 ? 1 : 0);
+    const int stride = gridDim.x >> 3;
+    const XcdRange rng = xcd_range(ntiles, blockIdx.x & 7);
+    const int first = rng.first, count = rng.count;
     int li = blockIdx.x >> 3;                              // (host: ntiles >= gridDim, so every workgroup has a tile)
     const h16* X = reinterpret_cast<const h16*>(p.X);
     const h16* X2 = p.X2 ? reinterpret_cast<const h16*>(p.X2) : nullptr;
@@ -842,35 +692,26 @@ __global__ __launch_bounds__(512, 2) void wgemm_pkernel(const MudgGemmDesc p, co
     const __amdgpu_buffer_rsrc_t rX = make_rsrc(X), rX2 = X2 ? make_rsrc(X2) : rX, rW = make_rsrc(W);
     struct Tile { int m0, n0, tm; };
     auto locate = [&](int local) {
-        const int tile = first + local;
-        const int per = 8 * ntn, g = tile / per, f8 = g * 8;
-        const int gsz = (ntm - f8) < 8 ? (ntm - f8) : 8;
-        const int r = tile - g * per;
-        const int tn = r / gsz, tm = f8 + (r - tn * gsz);
-        return Tile{tm * WBM, tn * WBN, tm};
+        const TileMN t = group8_tile(first + local, ntm, ntn);
+        return Tile{t.tm * WBM, t.tn * WBN, t.tm};
     };
     Tile cur = locate(li), nxt = cur;
     if (li + stride < count) nxt = locate(li + stride);
 
-    const int pos = lane * 16;
-    const int sbyte = pos ^ (((pos >> 9) & 1) << 5);
-    const int srow = sbyte >> 6, schunk = (sbyte >> 4) & 3;
-    const unsigned va1 = (unsigned)(srow * p.ldx) * 2u + (unsigned)schunk * 16u;
-    const unsigned va2 = (unsigned)(srow * ldx2e) * 2u + (unsigned)schunk * 16u;
-    const unsigned vw_pair = (unsigned)((8 * (srow >> 2) + (srow & 3)) * p.ldw) * 2u + (unsigned)schunk * 16u;
-    const unsigned vw_single = (unsigned)(srow * p.ldw) * 2u + (unsigned)schunk * 16u;
+    const DmaLane dl(lane);
+    const unsigned va1 = dl.x_off(p.ldx), va2 = dl.x_off(ldx2e);
+    const unsigned vw_pair = dl.w_off_pair(p.ldw), vw_single = dl.w_off_single(p.ldw);
     const int a_first = wc == 0 ? 0 : 1 + 2 * wc, a_cnt = wc == 0 ? 3 : 2;
     const int b_cnt = NREP == 5 ? ((wc == 0 || wc == 3) ? 2 : 3) : 2;
     const int b_first = NREP == 5 ? wr * 10 + (wc == 0 ? 0 : (wc == 1 ? 2 : (wc == 2 ? 5 : 8))) : wave * 2;
     // pieces of k half ks of K-tile kt of the current (sel 0) or the next (sel 1) tile -> ring buffer buf; part as in the one-tile kernel
-    auto stage = [&](int sel, int kt, int ks, int buf, int part) {
+    auto stage = [&](const KSel& k, int ks, int buf, int part) {
+        const int sel = k.sel, kt = k.kt;
         char* base = smem + buf * W_BUF + ks * W_KS;
         if (part != 2) {
-            const int c = kt * BK;
-            const bool s2 = c >= p.csplit;
-            const int cc = s2 ? c - p.csplit : c;
-            const int ld = s2 ? ldx2e : p.ldx;
-            const int soff = (cc + ks * 32) * 2 + (sel ? nxt.m0 : cur.m0) * ld * 2;
+            const XSource xs = x_source<0>(p, ldx2e, kt * BK, 0, ks);
+            const bool s2 = xs.s2;
+            const int ld = xs.ld, soff = xs.soff + (sel ? nxt.m0 : cur.m0) * ld * 2;
 #pragma unroll
             for (int q = 0; q < 3; ++q)
                 if (q < a_cnt) {
@@ -884,54 +725,37 @@ __global__ __launch_bounds__(512, 2) void wgemm_pkernel(const MudgGemmDesc p, co
 #pragma unroll
             for (int q = 0; q < 3; ++q)
                 if (q < b_cnt) {
-                    const int st = b_first + q, wcol = st / NREP, j = st - wcol * NREP;
-                    const bool single = j >= 2 * NPAIR;
-                    const int row0 = single ? wave_single_col<NREP>(wcol) : wave_pair_col<NREP>(wcol, j >> 1) + 4 * (j & 1);
+                    const int st = b_first + q;
+                    const WPiece wp = w_piece_row0<NREP>(st);
+                    const int row0 = wp.row0;
+                    const bool single = wp.single;
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lptr_t)(base + (WNA + st) * 1024), 16, (int)(single ? vw_single : vw_pair),
                                                              soffw + row0 * p.ldw * 2, 0, 0);
                 }
         }
     };
-    const int fbyte0 = (lane & 15) * 64 + (lane >> 4) * 16;
-    const int fbyte = fbyte0 ^ (((fbyte0 >> 9) & 1) << 5);
+    const int fbyte = DmaLane::frag_byte(lane);
     const char* a_base = smem + (wr * 9) * 1024 + fbyte;
     const char* b_base = smem + (WNA + wc * NREP) * 1024 + fbyte;
     f32x4 acc[9][NREP];
-    h16x8 af[3], bf[NREP];
-    auto read_a = [&](int buf, int ks, int third) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) af[i] = *reinterpret_cast<const h16x8*>(a_base + buf * W_BUF + ks * W_KS + (third * 3 + i) * 1024);
-    };
-    auto read_b = [&](int buf, int ks) {
-#pragma unroll
-        for (int j = 0; j < NREP; ++j) bf[j] = *reinterpret_cast<const h16x8*>(b_base + buf * W_BUF + ks * W_KS + j * 1024);
-    };
-    auto mma = [&](auto third_tag) {
-        constexpr int third = decltype(third_tag)::value;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < NREP; ++j) acc[third * 3 + i][j] = mfma16(bf[j], af[i], acc[third * 3 + i][j]);
-    };
+    Frag288<NREP> fr;
     const int base_cnt = a_cnt + 2 * b_cnt;                // the one-tile kernel's wait_half count: 7 | 8 | 6
     const int nst = GEGLU ? (p.out_fp32 == KIND_F32 ? 18 : 9) : (p.out_fp32 == KIND_F32 ? 45 : 27);       // epilogue stores per lane
-    auto wait_half = [&](bool more, bool fresh) {
+    bool first_kt = false;                                 // the K-tile that follows an epilogue: set per iteration
+    auto wait_half = [&](bool more) {
         if (!more) W_VMCNT(0);
-        else if (fresh) w_vmcnt_runtime(base_cnt + nst);
+        else if (first_kt) w_vmcnt_runtime(base_cnt + nst);
         else if (base_cnt == 8) W_VMCNT(8);
         else if (base_cnt == 7) W_VMCNT(7);
         else W_VMCNT(6);
     };
-    using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>; using T2 = std::integral_constant<int, 2>;
     const int nk = p.K / BK;                               // >= 2 (host)
 
     W_STAMP(0);
     [[maybe_unused]] int stamp_tile = 0;
-    stage(0, 0, 0, 0, 0);
-    stage(0, 0, 1, 0, 0);
-    stage(0, 1, 0, 1, 0);
+    stage(KSel{0, 0}, 0, 0, 0);
+    stage(KSel{0, 0}, 1, 0, 0);
+    stage(KSel{0, 1}, 0, 1, 0);
     if (a_cnt + b_cnt == 5) W_VMCNT(10); else W_VMCNT(8);  // ks 0 of the first K-tile has landed
     W_BARRIER();
     if (wr == 1) W_BARRIER();                              // the stagger: M-half 1 runs one barrier behind M-half 0
@@ -949,39 +773,8 @@ __global__ __launch_bounds__(512, 2) void wgemm_pkernel(const MudgGemmDesc p, co
             const bool n1 = in1 || has_next, n2 = in2 || has_next;
             const int sel1 = in1 ? 0 : 1, kt1 = in1 ? t + 1 : 0;
             const int sel2 = in2 ? 0 : 1, kt2 = in2 ? t + 2 : t + 2 - nk;
-            const bool fr = fresh && t == 0;
-            read_b(buf, 0);
-            read_a(buf, 0, 0);
-            W_BARRIER();
-            mma(T0{});
-            W_BARRIER();
-            read_a(buf, 0, 1);
-            if (n1) stage(sel1, kt1, 1, buf ^ 1, 2);
-            W_BARRIER();
-            mma(T1{});
-            wait_half(n1, fr);
-            W_BARRIER();
-            read_a(buf, 0, 2);
-            if (n1) stage(sel1, kt1, 1, buf ^ 1, 1);
-            W_BARRIER();
-            mma(T2{});
-            W_BARRIER();
-            read_b(buf, 1);
-            read_a(buf, 1, 0);
-            W_BARRIER();
-            mma(T0{});
-            W_BARRIER();
-            read_a(buf, 1, 1);
-            if (n2) stage(sel2, kt2, 0, buf, 2);
-            W_BARRIER();
-            mma(T1{});
-            wait_half(n2, fr);
-            W_BARRIER();
-            read_a(buf, 1, 2);
-            if (n2) stage(sel2, kt2, 0, buf, 1);
-            W_BARRIER();
-            mma(T2{});
-            W_BARRIER();
+            first_kt = fresh && t == 0;
+            ktile_six<W_KS>(fr, acc, a_base + buf * W_BUF, b_base + buf * W_BUF, buf, n1, n2, stage, KSel{sel1, kt1}, KSel{sel2, kt2}, wait_half);
         }
         if (wr == 0) W_BARRIER();                          // evens out the stagger
         __builtin_amdgcn_sched_barrier(0);
@@ -1042,27 +835,12 @@ __global__ __launch_bounds__(256, 2) void hgeglu_kernel(const MudgGemmDesc p, co
     float* tail = reinterpret_cast<float*>(smem + H_RING);
     if (phi) for (int t = tid; t <= PHI_N; t += 256) tail[t] = phi[t];        // visible after the K loop's barriers
 
-    // XCD-aware tile numbering (as wgemm_kernel): every XCD a contiguous tile range, walked in 8-row groups column by column
     const int ntn = p.N / HBN, ntm = (p.M + HBM_ - 1) / HBM_;
-    int tile;
-    {
-        const int total = gridDim.x, q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
-    int tm, tn;
-    {
-        const int per = 8 * ntn, g = tile / per, first = g * 8;
-        const int gsz = (ntm - first) < 8 ? (ntm - first) : 8;
-        const int r = tile - g * per;
-        tn = r / gsz;
-        tm = first + (r - tn * gsz);
-    }
+    const TileMN tl = group8_tile(xcd_work_item(gridDim.x), ntm, ntn);
+    const int tm = tl.tm, tn = tl.tn;
     const int m0 = tm * HBM_, n0 = tn * HBN;
 
-    const int pos = lane * 16;
-    const int sbyte = pos ^ (((pos >> 9) & 1) << 5);
-    const int srow = sbyte >> 6, schunk = (sbyte >> 4) & 3;
+    const DmaLane dl(lane);
     const h16* X = reinterpret_cast<const h16*>(p.X);
     const h16* X2 = p.X2 ? reinterpret_cast<const h16*>(p.X2) : nullptr;
     const h16* W = reinterpret_cast<const h16*>(p.W);
@@ -1070,22 +848,19 @@ __global__ __launch_bounds__(256, 2) void hgeglu_kernel(const MudgGemmDesc p, co
     const __amdgpu_buffer_rsrc_t rX2 = X2 ? make_rsrc(X2 + (int64_t)m0 * p.ldx2) : rX;
     const __amdgpu_buffer_rsrc_t rW = make_rsrc(W + (int64_t)n0 * p.ldw);
     const int ldx2e = X2 ? p.ldx2 : p.ldx;
-    const unsigned va1 = (unsigned)(srow * p.ldx) * 2u + (unsigned)schunk * 16u;
-    const unsigned va2 = (unsigned)(srow * ldx2e) * 2u + (unsigned)schunk * 16u;
-    const unsigned vw_pair = (unsigned)((8 * (srow >> 2) + (srow & 3)) * p.ldw) * 2u + (unsigned)schunk * 16u;     // (permuted W rows: wgemm_kernel)
+    const unsigned va1 = dl.x_off(p.ldx), va2 = dl.x_off(ldx2e);
+    const unsigned vw_pair = dl.w_off_pair(p.ldw);
     // this wave's pieces per k half: its own 4 W subtiles; of the 9 X subtiles 3 | 2 | 2 | 2
     const int a_first = wc == 0 ? 0 : 1 + 2 * wc, a_cnt = wc == 0 ? 3 : 2;
     unsigned alive = 0;                                   // bit q: the lane's source row of X piece q exists
 #pragma unroll
     for (int q = 0; q < 3; ++q)
-        if (q < a_cnt && m0 + (a_first + q) * 16 + srow < p.M) alive |= 1u << q;
+        if (q < a_cnt && m0 + (a_first + q) * 16 + dl.srow() < p.M) alive |= 1u << q;
     auto stage = [&](int h, int slot) {
         char* base = smem + slot * H_KS;
-        const int c = (h >> 1) * BK;
-        const bool s2 = c >= p.csplit;
-        const int cc = s2 ? c - p.csplit : c;
-        const int ld = s2 ? ldx2e : p.ldx;
-        const int soff = (cc + (h & 1) * 32) * 2;
+        const XSource xs = x_source<0>(p, ldx2e, (h >> 1) * BK, 0, h & 1);
+        const bool s2 = xs.s2;
+        const int ld = xs.ld, soff = xs.soff;
 #pragma unroll
         for (int q = 0; q < 3; ++q)
             if (q < a_cnt) {
@@ -1097,7 +872,7 @@ __global__ __launch_bounds__(256, 2) void hgeglu_kernel(const MudgGemmDesc p, co
         const int soffw = h * 64;                          // k half h of W's K axis: 32 elements each
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int row0 = wave_pair_col<4>(wc, j >> 1) + 4 * (j & 1);
+            const int row0 = w_frag_row0<4>(wc, j).row0;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lptr_t)(base + (H_NA + wc * 4 + j) * 1024), 16, (int)vw_pair, soffw + row0 * p.ldw * 2, 0, 0);
         }
     };
@@ -1107,8 +882,7 @@ __global__ __launch_bounds__(256, 2) void hgeglu_kernel(const MudgGemmDesc p, co
     for (int i = 0; i < 9; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int fbyte0 = (lane & 15) * 64 + (lane >> 4) * 16;
-    const int fbyte = fbyte0 ^ (((fbyte0 >> 9) & 1) << 5);
+    const int fbyte = DmaLane::frag_byte(lane);
     const char* a_base = smem + fbyte;
     const char* b_base = smem + (H_NA + wc * 4) * 1024 + fbyte;
 
@@ -1142,7 +916,6 @@ __global__ __launch_bounds__(256, 2) void hgeglu_kernel(const MudgGemmDesc p, co
 #pragma unroll
         for (int i = 0; i < 3; ++i) dst[i] = *reinterpret_cast<const h16x8*>(a_base + sl * H_KS + (third * 3 + i) * 1024);
     };
-    using T0 = std::integral_constant<int, 0>; using T1 = std::integral_constant<int, 1>; using T2 = std::integral_constant<int, 2>;
     // The K loop runs at raised priority: when both workgroups of a CU have an instruction ready, the one that feeds the matrix pipe goes
     // first and the other one's epilogue arithmetic fills the slots in between (GEMM_H144PRIO = 0 in the variant build: off).
     if ((delay >> 20) == 0) __builtin_amdgcn_s_setprio(3);
@@ -1304,7 +1077,7 @@ __device__ __forceinline__ void w_pin(u32x2& r) { asm volatile("" : "+v"(r)); }
 template <int MODE, int NREP, bool GEGLU, int RS, int NI>          // RS: 0 = no residual, 1 = it seeds the accumulators, 2 = deferred (below)
 __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const int vflags, const float* __restrict__ phi) {
     using G = QGeo<NREP, NI>;
-    constexpr int WBN = G::BN, KS = G::KS, R = G::R, NPAIR = NREP / 2, BMq = G::BM, NA = G::NA, PW = G::PW;
+    constexpr int WBN = G::BN, KS = G::KS, R = G::R, BMq = G::BM, NA = G::NA, PW = G::PW;
     static_assert(!GEGLU || (MODE == 0 && NREP == 4), "GEGLU: plain GEMM on the 256-wide tile");
     static_assert(PW == 4 || PW == 5, "pieces per wave");
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -1312,34 +1085,13 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6) & 7;
     const int wr = wave >> 2, wc = wave & 3;             // waves wc and wc + 4 share a SIMD: the two M halves
     float* tail = reinterpret_cast<float*>(smem + G::LOOP);
-    if (GEGLU && phi) {                                  // (value, step) pairs: gelu_lut2; visible after the K loop's barriers
-        for (int t = tid; t <= PHI_N; t += 512) {
-            const float a = phi[t], b = phi[t < PHI_N ? t + 1 : t];
-            *reinterpret_cast<f32x2*>(&tail[2 * t]) = f32x2{a, b - a};
-        }
-    }
-    // XCD-aware tile numbering (as wgemm_kernel)
+    if (GEGLU && phi) phi_pairs_to_lds<512>(tail, phi, tid);
     const int ntn = p.N / WBN, ntm = (p.M + BMq - 1) / BMq;
-    int tile;
-    {
-        const int total = gridDim.x, q8 = total >> 3, r8 = total & 7;
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
-    int tm, tn;
-    {
-        const int per = 8 * ntn, g = tile / per, first = g * 8;
-        const int gsz = (ntm - first) < 8 ? (ntm - first) : 8;
-        const int r = tile - g * per;
-        tn = r / gsz;
-        tm = first + (r - tn * gsz);
-    }
+    const TileMN tl = group8_tile(xcd_work_item(gridDim.x), ntm, ntn);
+    const int tm = tl.tm, tn = tl.tn;
     const int m0 = tm * BMq, n0 = tn * WBN;
-    constexpr int ntaps = MODE == 0 ? 1 : (MODE == 1 ? 9 : 3);
 
-    const int pos = lane * 16;
-    const int sbyte = pos ^ (((pos >> 9) & 1) << 5);
-    const int srow = sbyte >> 6, schunk = (sbyte >> 4) & 3;
+    const DmaLane dl(lane);
     const h16* X = reinterpret_cast<const h16*>(p.X);
     const h16* X2 = p.X2 ? reinterpret_cast<const h16*>(p.X2) : nullptr;
     const h16* W = reinterpret_cast<const h16*>(p.W);
@@ -1348,10 +1100,8 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
     const __amdgpu_buffer_rsrc_t rX2 = X2 ? make_rsrc(X2 + ((int64_t)m0 + shift) * p.ldx2) : rX;
     const __amdgpu_buffer_rsrc_t rW = make_rsrc(W + (int64_t)n0 * p.ldw);
     const int ldx2e = X2 ? p.ldx2 : p.ldx;
-    const unsigned va1 = (unsigned)(srow * p.ldx) * 2u + (unsigned)schunk * 16u;
-    const unsigned va2 = (unsigned)(srow * ldx2e) * 2u + (unsigned)schunk * 16u;
-    const unsigned vw_pair = (unsigned)((8 * (srow >> 2) + (srow & 3)) * p.ldw) * 2u + (unsigned)schunk * 16u;     // (permuted W rows: wgemm_kernel)
-    const unsigned vw_single = (unsigned)(srow * p.ldw) * 2u + (unsigned)schunk * 16u;
+    const unsigned va1 = dl.x_off(p.ldx), va2 = dl.x_off(ldx2e);
+    const unsigned vw_pair = dl.w_off_pair(p.ldw), vw_single = dl.w_off_single(p.ldw);
     // This wave's pieces of a k half: piece indices wave + 8 q (q = 0 .. PW - 1); a piece below NA is an X subtile, below NP the W subtile
     // piece - NA, and beyond NP (the last pieces of some waves) a DUMMY: the same instruction with every lane out of range, zero-filling a
     // spare KiB behind the tail — every wave issues exactly PW operations per k half, so the counted waits are the same for all.
@@ -1366,9 +1116,9 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
     for (int q = XQ; q < PW; ++q) {
         const int pc = wave + 8 * q;
         const bool live = pc >= NA && pc < G::NP;
-        const int st = live ? pc - NA : 0, wcol = st / NREP, j = st - wcol * NREP;
-        const bool single = j >= 2 * NPAIR;
-        const int row0 = single ? wave_single_col<NREP>(wcol) : wave_pair_col<NREP>(wcol, j >> 1) + 4 * (j & 1);       // first channel of the piece
+        const WPiece wp = w_piece_row0<NREP>(live ? pc - NA : 0);
+        const int row0 = wp.row0;
+        const bool single = wp.single;
         wso[q] = row0 * p.ldw * 2;
         wv[q] = live ? (single ? vw_single : vw_pair) : OOB;
     }
@@ -1377,37 +1127,10 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
 #pragma unroll
     for (int q = 0; q < XMAX; ++q) {
         const int st = wave + 8 * q;
-        const int m = m0 + st * 16 + srow;
-        unsigned mask = 0;
-        if (st < NA && m < p.M) {
-            if (MODE == 0) mask = 1;
-            else if (MODE == 1) {
-                const int hw = p.Hout * p.Wout;
-                const int f = m / hw, r = m - f * hw;
-                const int oy = r / p.Wout, ox = r - oy * p.Wout;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int iy = oy - 1 + t / 3, ix = ox - 1 + t % 3;
-                    if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) mask |= 1u << t;
-                }
-            } else {
-                const int fr = (m / p.HW) % p.T;
-#pragma unroll
-                for (int t = 0; t < 3; ++t) if (fr + t - 1 >= 0 && fr + t - 1 < p.T) mask |= 1u << t;
-            }
-        }
-        amask[q] = mask;
+        const int m = m0 + st * 16 + dl.srow();
+        amask[q] = st < NA ? tap_mask<MODE>(p, m) : 0u;
     }
     const int NH = 2 * (p.K / BK);                        // k halves (>= 2, even)
-    auto advance = [&](KPos& k) {
-        k.kt += 1;
-        if (MODE == 0) { k.c += BK; return; }
-        const int t1 = k.tap + 1, c1 = k.c + BK;
-        const bool slab = p.korder != 0;
-        const bool wrap = slab ? (t1 == ntaps) : (c1 == p.Cin);
-        k.tap = slab ? (wrap ? 0 : t1) : (wrap ? t1 : k.tap);
-        k.c = slab ? (wrap ? c1 : k.c) : (wrap ? 0 : c1);
-    };
     auto stage = [&](const KPos& k, int ks, int slot) {
         char* base = smem + slot * KS;
         const bool s2 = k.c >= p.csplit;
@@ -1446,7 +1169,7 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
         stage(kS, hs & 1, sslot);
         ++hs;
         sslot = sslot == R - 1 ? 0 : sslot + 1;
-        if (!(hs & 1)) advance(kS);
+        if (!(hs & 1)) k_advance<MODE>(p, kS);
     };
     // RS (a residual seeds the accumulators) is a template parameter: as a run-time branch its merge point carried a vmcnt(0) — every tile
     // waited for all the prefetched k halves before its first MFMA, residual or not.
@@ -1499,8 +1222,7 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
             }
         }
     }
-    const int fbyte0 = (lane & 15) * 64 + (lane >> 4) * 16;
-    const int fbyte = fbyte0 ^ (((fbyte0 >> 9) & 1) << 5);
+    const int fbyte = DmaLane::frag_byte(lane);
     const char* a_base = smem + (wr * NI) * 1024 + fbyte;
     const char* b_base = smem + (NA + wc * NREP) * 1024 + fbyte;
     auto frag_a = [&](int slot, int i) { return *reinterpret_cast<const h16x8*>(a_base + slot * KS + i * 1024); };
@@ -1569,7 +1291,7 @@ __global__ __launch_bounds__(512, 2) void wq_kernel(const MudgGemmDesc p, const 
         W_BARRIER();
         stage(kS, ks, sslot);
         sslot = sslot == R - 1 ? 0 : sslot + 1;
-        if (ks) advance(kS);
+        if (ks) k_advance<MODE>(p, kS);
         multiply(cur_tag, nslot);
         slot = nslot;
     };

@@ -64,7 +64,6 @@ struct Walker {
     }
 };
 
-typedef __attribute__((address_space(3))) void* lptr_t;
 // The transposing reads are issued as inline assembly: behind the builtin the compiler cannot tell them from the LDS-DMA writes
 // of the OTHER stage and drains vmcnt before every group of reads, which serialises fetch and multiply.  In assembly the only
 // waits are the ones written here: lgkmcnt before a fragment is used (tr_wait ties the fragment registers to the wait), vmcnt(0)
@@ -94,11 +93,6 @@ __device__ __forceinline__ unsigned tr_offset(int kbase, int cbase, int lane) {
     const int piece = (kbase >> 2) + 2 * (g >> 1);
     const int pair = (cbase >> 4) + (g & 1), r = q >> 2;
     return (unsigned)(2 * (piece * 512 + r * 128 + (((pair ^ (2 * r)) * 2 + ((q & 3) >> 1)) * 8) + (q & 1) * 4));
-}
-
-constexpr unsigned OOB = 0x80000000u;            // a voffset at num_records: the buffer load returns 0 into the LDS
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const h16* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<h16*>(base), 0, (int)0x80000000u, 0x00020000);
 }
 
 constexpr int IMG = WK * WT;                     // h16 per operand image (16 KiB)
