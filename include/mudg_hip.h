@@ -746,6 +746,46 @@ int mudg_gauss_loss_bwd(const float* rgb, const float* targets, const float* map
                         const float* totals, const float* upstream, int V, int H, int W, float ssim_weight, float depth_weight, float* d_rgb,
                         float* d_depth, void* stream);
 
+/* ------------------------------------------------------------------ semantic Gaussians (csrc/gaussians_feat.hip)
+ * Every Gaussian carries feat (n, F) fp32, row-major and unpadded, 1 <= F <= 32: class scores blended with the colours in the same walk.
+ * colours: (n, 3) with colour_views = 0, (V, n, 3) with colour_views = 1, fp32 in byte units.  fp32 throughout, every operation a single
+ * rounded one in the order §29 states, E(p) §23's polynomial exponential; plain stores, no atomics; a repeat run gives the same bits.
+ * blend_feat: mudg_gauss_blend_train (colour_views = 1: mudg_gauss_blend_train_views) with one more line per blended entry,
+ *   Fk = Fk + feat[g][k] w for k < F.  rgb, depth_out, alpha and state (V, 5, H, W; NULL for inference) are that call's bits on the same
+ *   inputs; feat_out (V, F, H, W) = Fk, unrounded and undivided.  A sorted value outside 0 .. n - 1 is an entry of opacity 0 and reads
+ *   no feature row.
+ * blend_bwd_feat: mudg_gauss_blend_bwd's walk with the forward recomputed bit for bit.  Per pixel gF_k = d_feat[k] (d_feat (V, F, H, W)),
+ *   Stot = sum_k gF_k feat_out[k], P = +0.  Per blended entry s = sum_k gF_k feat[g][k], P = P + s w, own = (§24's own) + s,
+ *   behind = (§24's behind) + (Stot - P), the ten sums from own and behind as §24 computes them, and q_k = gF_k w.  Sums over k run
+ *   ascending from +0.  The ten sums go to partial (E, 10) and q to partial_feat (E, F) at row order[e], reduced over the tile's pixels
+ *   in §24's order; both buffers are zeroed by the call.  With d_feat = 0 partial has mudg_gauss_blend_bwd's values.
+ * feat_bwd: d_feat_g (n, F): per Gaussian and channel, per view (ascending) the count[view][g] rows of partial_feat from
+ *   offsets[view][g] added in ascending order from +0 (nothing where count <= 0 or the offset lies outside [0, E - count]), the views'
+ *   sums added in view order from +0.
+ * class_loss: x (V, F, H, W) fp32, labels (V, H, W) uint8; a pixel is labelled iff label < F.  Labelled: m = max_k x_k (fmaxf, ascending),
+ *   p_k = fmaxf(x_k - m, -80), e_k = E(p_k), S = sum_k e_k, maps[k] = e_k / S - [k == label], l = L(S) - p_label with L §29's polynomial
+ *   logarithm on [1, 32]; unlabelled: maps = +0, l = +0.  maps (V, F, H, W); partial (V NT, 2): each 16 x 16 tile's sum of l in the
+ *   tile's fixed order and its labelled count (an int32 in the second word).
+ * class_loss_finish: adds the tiles in a fixed order (fp64, the count in int64) into totals (4): sum l, the count as int32
+ *   (saturated), float(max(count, 1)), and the loss weight (sum l / max(count, 1)).
+ * class_loss_bwd: d_x (V, F, H, W) = ((up weight) / totals[2]) maps; up (1) is the loss's gradient, on the device.
+ * Refused before any launch: what mudg_gauss_blend_train / mudg_gauss_blend_bwd / mudg_gauss_loss refuse, and F outside 1 .. 32,
+ *   colour_views outside {0, 1}, null feat / feat_out / d_feat / partial_feat, E F >= 2^31, a negative or non-finite weight. */
+int mudg_gauss_blend_feat(const float* colours, int colour_views, const float* feat, int F, const float* uv, const float* conic,
+                          const float* depth, const int32_t* values_sorted, const int32_t* ranges, int64_t n, int64_t E, int V, int H, int W,
+                          float* rgb, float* depth_out, float* alpha, float* feat_out, float* state, void* stream);
+int mudg_gauss_blend_bwd_feat(const float* colours, int colour_views, const float* feat, int F, const float* uv, const float* conic,
+                              const float* depth, const int32_t* values_sorted, const int64_t* order, const int32_t* ranges, int64_t n,
+                              int64_t E, int V, int H, int W, const float* state, const float* feat_out, const float* d_rgb,
+                              const float* d_depth, const float* d_alpha, const float* d_feat, float* partial, float* partial_feat,
+                              void* stream);
+int mudg_gauss_feat_bwd(const int32_t* count, const int64_t* offsets, const float* partial_feat, int64_t E, int64_t n, int V, int F,
+                        float* d_feat_g, void* stream);
+int mudg_gauss_class_loss(const float* x, const uint8_t* labels, int V, int F, int H, int W, float* maps, float* partial, void* stream);
+int mudg_gauss_class_loss_finish(const float* partial, int V, int H, int W, float weight, float* totals, void* stream);
+int mudg_gauss_class_loss_bwd(const float* maps, const float* totals, const float* up, float weight, int V, int F, int H, int W, float* d_x,
+                              void* stream);
+
 /* ------------------------------------------------------------------ the image tower (csrc/towers.hip)
  * Reference: lvdm/modules/encoders/condition.py:295-372 (FrozenOpenCLIPImageEmbedderV2): a pre-LN ViT whose GEMMs run on mudg_gemm;
  * these entries are what it needs besides.

@@ -21,7 +21,7 @@ OUT_X3 = os.path.join(HERE, "libmudg_hip_x3.so")
 OUT_X6 = os.path.join(HERE, "libmudg_hip_x6.so")
 OUT_X3_DBG = os.path.join(HERE, "libmudg_hip_x3_dbg.so")  # bf16x3 + kernel-variant switches (same use)
 OUT_DBG = os.path.join(HERE, "libmudg_hip_dbg.so")      # bf16 + kernel-variant switches (tests / tools only; hip.py loads it under MUDG_DEBUG_VARIANTS=1)
-SOURCES = ["capi.hip", "gemm.hip", "pgemm.hip", "wgemm.hip", "sgemm.hip", "attention.hip", "norm.hip", "misc.hip", "post.hip", "train.hip", "optim.hip", "attention_bwd.hip", "wgrad.hip", "batch_input.hip", "splat.hip", "cloud.hip", "depth.hip", "metrics.hip", "frames.hip", "towers.hip", "normals.hip", "lidar_depth.hip", "consistency.hip", "neighbours.hip", "gaussians.hip", "gaussians_bwd.hip", "gaussians_density.hip", "gaussians_loss.hip", "gaussians_sh.hip", "gaussians_pose.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "pgemm.hip", "wgemm.hip", "sgemm.hip", "attention.hip", "norm.hip", "misc.hip", "post.hip", "train.hip", "optim.hip", "attention_bwd.hip", "wgrad.hip", "batch_input.hip", "splat.hip", "cloud.hip", "depth.hip", "metrics.hip", "frames.hip", "towers.hip", "normals.hip", "lidar_depth.hip", "consistency.hip", "neighbours.hip", "gaussians.hip", "gaussians_bwd.hip", "gaussians_density.hip", "gaussians_loss.hip", "gaussians_sh.hip", "gaussians_pose.hip", "gaussians_feat.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off", *os.environ.get("MUDG_EXTRA_HIPCC_FLAGS", "").split()]      # extra flags: kernel experiments only
 

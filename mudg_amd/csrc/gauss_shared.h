@@ -1,7 +1,7 @@
 // gauss_shared.h — every step that more than one kernel of the Gaussian splat renderer computes (gaussians.hip, DESIGN.md §23;
-// gaussians_bwd.hip, §24; gaussians_density.hip, §25; gaussians_loss.hip, §26; gaussians_sh.hip, §27), written once: the constants of the rule, the single
+// gaussians_bwd.hip, §24; gaussians_density.hip, §25; gaussians_loss.hip, §26; gaussians_sh.hip, §27; gaussians_feat.hip, §29), written once: the constants of the rule, the single
 // rounded operations, the polynomial exponential, a Gaussian's load and its projection into a view, a tile's prologue, the staging of an
-// entry, the blend step and the forward blend loop, the walk over a Gaussian's partials, the fixed-order tile reduction, and the checks
+// entry, the blend step and the forward blend loop, a pixel's state and the blend's backward at a pixel, the walk over a Gaussian's partials, the fixed-order tile reduction, and the checks
 // the entry points share, the chain rule of one (view, Gaussian) (§24) and the fixed-order reduction over all Gaussians of a (view, matrix)
 // (§28).  One copy, so that the backward recomputes the forward's values bit for bit.
 #pragma once
@@ -257,6 +257,73 @@ __device__ __forceinline__ void store_images(const GaussTile& tile, int H, int W
     out[2 * plane] = dvd(acc.c2, 255.0f);
     depth_out[tile.view * plane + pix] = acc.D;
     alpha_out[tile.view * plane + pix] = sub(1.0f, acc.T);
+}
+
+// The raw accumulators (C0, C1, C2, D, T) of a pixel that the image has, into state (V, 5, H, W): what a backward needs unrounded.
+__device__ __forceinline__ void store_state(const GaussTile& tile, int H, int W, const GaussPixel& acc, float* __restrict__ state) {
+    const int64_t plane = (int64_t)H * W;
+    float* st = state + tile.view * 5 * plane + (int64_t)tile.j * W + tile.i;
+    st[0] = acc.c0;
+    st[plane] = acc.c1;
+    st[2 * plane] = acc.c2;
+    st[3 * plane] = acc.D;
+    st[4 * plane] = acc.T;
+}
+
+// ------------------------------------------------------------------------------------------------ the blend's backward at a pixel (§24)
+// What a pixel of the backward holds before its walk: the upstream gradients of the raw accumulators (colour over 255), gA T_final, and
+// the forward's final accumulators; zeros for a lane the image does not have.
+struct GaussUpstream {
+    float gC0 = 0.0f, gC1 = 0.0f, gC2 = 0.0f, gD = 0.0f, gAT = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sD = 0.0f;
+};
+
+__device__ __forceinline__ GaussUpstream load_upstream(const GaussTile& tile, int H, int W, const float* __restrict__ state,
+                                                       const float* __restrict__ d_rgb, const float* __restrict__ d_depth,
+                                                       const float* __restrict__ d_alpha) {
+    GaussUpstream u;
+    if (tile.inside) {
+        const int64_t plane = (int64_t)H * W, pix = (int64_t)tile.j * W + tile.i;
+        const float* g = d_rgb + tile.view * 3 * plane + pix;
+        u.gC0 = dvd(g[0], 255.0f);
+        u.gC1 = dvd(g[plane], 255.0f);
+        u.gC2 = dvd(g[2 * plane], 255.0f);
+        u.gD = d_depth[tile.view * plane + pix];
+        const float* st = state + tile.view * 5 * plane + pix;
+        u.s0 = st[0]; u.s1 = st[plane]; u.s2 = st[2 * plane]; u.sD = st[3 * plane];
+        u.gAT = mul(d_alpha[tile.view * plane + pix], st[4 * plane]);      // gA T_final
+    }
+    return u;
+}
+
+// A blended entry's four sums that need no alpha gradient: the colour's and the depth's.
+__device__ __forceinline__ void blend_bwd_direct(const GaussUpstream& u, const GaussBlend& s, float (&r)[GAUSS_SUMS]) {
+    r[SUM_COLOUR] = mul(u.gC0, s.w);
+    r[SUM_COLOUR + 1] = mul(u.gC1, s.w);
+    r[SUM_COLOUR + 2] = mul(u.gC2, s.w);
+    r[SUM_ZC] = mul(u.gD, s.w);
+}
+
+// own: what the entry itself adds to the loss per unit of w; behind: what everything behind it adds.  acc: after the entry was added.
+__device__ __forceinline__ float blend_bwd_own(const GaussUpstream& u, const f32x4& c, float zc) {
+    return add(add(add(mul(u.gC0, c.x), mul(u.gC1, c.y)), mul(u.gC2, c.z)), mul(u.gD, zc));
+}
+
+__device__ __forceinline__ float blend_bwd_behind(const GaussUpstream& u, const GaussPixel& acc) {
+    return add(add(add(mul(u.gC0, sub(u.s0, acc.c0)), mul(u.gC1, sub(u.s1, acc.c1))), mul(u.gC2, sub(u.s2, acc.c2))),
+               mul(u.gD, sub(u.sD, acc.D)));
+}
+
+// The six sums through alpha, for an entry whose alpha the cap did not take: a, b the staged entry, T the transmittance before it.
+__device__ __forceinline__ void blend_bwd_alpha(const GaussUpstream& u, const f32x4& a, const f32x4& b, const GaussBlend& s, float T, float own,
+                                                float behind, float (&r)[GAUSS_SUMS]) {
+    const float dal = add(sub(mul(T, own), dvd(behind, s.om)), dvd(u.gAT, s.om));
+    r[SUM_OPACITY] = mul(dal, s.ge);
+    const float dp = mul(mul(dal, b.y), s.ge);
+    r[SUM_A] = mul(dp, mul(-0.5f, mul(s.dx, s.dx)));
+    r[SUM_B] = mul(dp, -mul(s.dx, s.dy));
+    r[SUM_C] = mul(dp, mul(-0.5f, mul(s.dy, s.dy)));
+    r[SUM_U] = mul(dp, -add(mul(a.z, s.dx), mul(a.w, s.dy)));
+    r[SUM_V] = mul(dp, -add(mul(b.x, s.dy), mul(a.w, s.dx)));
 }
 
 // ------------------------------------------------------------------------------------------------ partials and reductions (§24)

@@ -32,14 +32,7 @@ __global__ __launch_bounds__(256) void gauss_blend_train_kernel(const float* __r
     blend_forward(uv, conic, depth, values, n, tile, FloatColour{colour + tile.view * per_view, tint}, geom, look, acc);
     if (tile.inside) {
         store_images(tile, H, W, acc, rgb, depth_out, alpha_out);
-        if (!state) return;                                                 // inference: the images only
-        const int64_t plane = (int64_t)H * W;
-        float* st = state + tile.view * 5 * plane + (int64_t)tile.j * W + tile.i;
-        st[0] = acc.c0;
-        st[plane] = acc.c1;
-        st[2 * plane] = acc.c2;
-        st[3 * plane] = acc.D;
-        st[4 * plane] = acc.T;
+        if (state) store_state(tile, H, W, acc, state);                    // NULL: inference, the images only
     }
 }
 
@@ -59,18 +52,7 @@ __global__ __launch_bounds__(256) void gauss_blend_bwd_kernel(const float* __res
     const GaussTile tile = gauss_tile(blockIdx.x, ranges, E, TX, NT, H, W);
     const FloatColour tints = {colour + tile.view * per_view, tint};
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float gC0 = 0.0f, gC1 = 0.0f, gC2 = 0.0f, gD = 0.0f, gAT = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sD = 0.0f;
-    if (tile.inside) {
-        const int64_t plane = (int64_t)H * W, pix = (int64_t)tile.j * W + tile.i;
-        const float* g = d_rgb + tile.view * 3 * plane + pix;
-        gC0 = dvd(g[0], 255.0f);
-        gC1 = dvd(g[plane], 255.0f);
-        gC2 = dvd(g[2 * plane], 255.0f);
-        gD = d_depth[tile.view * plane + pix];
-        const float* st = state + tile.view * 5 * plane + pix;
-        s0 = st[0]; s1 = st[plane]; s2 = st[2 * plane]; sD = st[3 * plane];
-        gAT = mul(d_alpha[tile.view * plane + pix], st[4 * plane]);        // gA T_final
-    }
+    const GaussUpstream up = load_upstream(tile, H, W, state, d_rgb, d_depth, d_alpha);
     GaussPixel acc;
     int done = tile.inside ? 0 : 1;
     for (int64_t base = tile.start; base < tile.end; base += BATCH) {
@@ -87,22 +69,9 @@ __global__ __launch_bounds__(256) void gauss_blend_bwd_kernel(const float* __res
                     const f32x4 c = tints.at(k, b);
                     const float T = acc.T, zc = b.w;
                     accumulate(acc, c, zc, s);
-                    r[SUM_COLOUR] = mul(gC0, s.w);
-                    r[SUM_COLOUR + 1] = mul(gC1, s.w);
-                    r[SUM_COLOUR + 2] = mul(gC2, s.w);
-                    r[SUM_ZC] = mul(gD, s.w);
+                    blend_bwd_direct(up, s, r);
                     if (s.raw > MAX_ALPHA) return;                          // the cap passes no gradient
-                    const float own = add(add(add(mul(gC0, c.x), mul(gC1, c.y)), mul(gC2, c.z)), mul(gD, zc));
-                    const float behind = add(add(add(mul(gC0, sub(s0, acc.c0)), mul(gC1, sub(s1, acc.c1))), mul(gC2, sub(s2, acc.c2))),
-                                             mul(gD, sub(sD, acc.D)));
-                    const float dal = add(sub(mul(T, own), dvd(behind, s.om)), dvd(gAT, s.om));
-                    r[SUM_OPACITY] = mul(dal, s.ge);
-                    const float dp = mul(mul(dal, b.y), s.ge);
-                    r[SUM_A] = mul(dp, mul(-0.5f, mul(s.dx, s.dx)));
-                    r[SUM_B] = mul(dp, -mul(s.dx, s.dy));
-                    r[SUM_C] = mul(dp, mul(-0.5f, mul(s.dy, s.dy)));
-                    r[SUM_U] = mul(dp, -add(mul(a.z, s.dx), mul(a.w, s.dy)));
-                    r[SUM_V] = mul(dp, -add(mul(b.x, s.dy), mul(a.w, s.dx)));
+                    blend_bwd_alpha(up, a, b, s, T, blend_bwd_own(up, c, zc), blend_bwd_behind(up, acc), r);
                 });
             }
             float* out = wsum + ((size_t)wave * BATCH + k) * GAUSS_SUMS;

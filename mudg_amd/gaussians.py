@@ -61,11 +61,13 @@ class Gaussians:
     background, the object's frame for an object), `opacity` (n,) fp32 in [0, 1] and `ids` (n,) int32 or None: the matrix a point goes
     through, 0 for the background and 1 + object for an object.  `sh` (n, K - 1, 3) fp32 in byte units or None: the coefficients of the
     real spherical harmonics of degrees 1 .. L, K = (L + 1)^2, L = 1, 2 or 3; with them `colour` (n, 3) fp32 in byte units
-    is the direction-independent term (default: the cloud's bytes), and render draws max(0, colour + sum B_k(d) sh[k - 1]) per view."""
-    sh = colour = None
+    is the direction-independent term (default: the cloud's bytes), and render draws max(0, colour + sum B_k(d) sh[k - 1]) per view.
+    `features` (n, F) fp32 or None, 1 <= F <= ops.GAUSS_FEAT_MAX: a row of class scores per Gaussian; with them render
+    also returns the blended scores and a label image."""
+    sh = colour = features = None
 
     def __init__(self, cloud: PointCloud, cov: torch.Tensor, opacity: torch.Tensor, ids: Optional[torch.Tensor] = None,
-                 sh: Optional[torch.Tensor] = None, colour: Optional[torch.Tensor] = None):
+                 sh: Optional[torch.Tensor] = None, colour: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None):
         if not isinstance(cloud, PointCloud) or not cloud.points.is_cuda:
             raise hip.MudgError("Gaussians: the cloud is a PointCloud on the GPU (there is no CPU path)")
         n = len(cloud)
@@ -79,6 +81,7 @@ class Gaussians:
             self.colour = _byte_colours(cloud.points) if colour is None else _on_gpu("Gaussians: colour", colour, torch.float32, (n, 3))
         elif colour is not None:
             raise hip.MudgError("Gaussians: colour comes with sh; without harmonics the colour is the cloud's bytes")
+        self.features = None if features is None else _on_gpu("Gaussians: features", features, torch.float32, (n, _feature_width_of("Gaussians", features)))
 
     def __len__(self):
         return len(self.cloud)
@@ -136,6 +139,24 @@ def _sh_rows_of(name, sh):
     return rows
 
 
+def _feature_width_of(name, features):
+    """F of features (n, F), refused in `name`'s words unless 1 <= F <= ops.GAUSS_FEAT_MAX."""
+    width = features.shape[1] if torch.is_tensor(features) and features.dim() == 2 else -1
+    if not 1 <= width <= ops.GAUSS_FEAT_MAX:
+        got = tuple(features.shape) if torch.is_tensor(features) else type(features).__name__
+        raise hip.MudgError(f"{name}: features is an (n, F) fp32 tensor on the GPU with 1 <= F <= {ops.GAUSS_FEAT_MAX}, got {got}")
+    return width
+
+
+def label_image(features, alpha, label_alpha=0.5):
+    """Blended scores (..., F, H, W) and alpha (..., H, W) -> uint8 labels (..., H, W): the argmax over the F scores, the lowest index
+    on ties, and 255 (unlabelled) where alpha <= label_alpha."""
+    best = features.max(dim=-3, keepdim=True).values
+    index = torch.arange(features.shape[-3], device=features.device).reshape(-1, 1, 1)
+    first = torch.where(features == best, index, features.shape[-3]).amin(dim=-3)      # scores that are not numbers: unlabelled
+    return torch.where((alpha > label_alpha) & (first < features.shape[-3]), first, 255).to(torch.uint8)
+
+
 def _sh_degree_of(sh):
     return {ops.gauss_sh_rows(d): d for d in range(1, ops.GAUSS_SH_MAX_DEGREE + 1)}[sh.shape[1]]
 
@@ -173,7 +194,7 @@ def _blank(views, h, w, device):
             torch.zeros((views, h, w), dtype=torch.float32, device=device))
 
 
-def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, stats=None):
+def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, stats=None, label_alpha=0.5):
     """Draw `g` into V views.  mats: (V, nmat, 12) fp32 on the GPU, row-major 3 x 4 matrices, mats[v][0] the world-to-camera matrix of
     view v and mats[v][1 + o] that matrix times object o's transform (zero for an object the view does not show); cams: (fx, fy, cx, cy)
     shared by the views; hw: (H, W).  Returns {"rgb": (V, 3, H, W) in [0, 1] on black, "depth": (V, H, W) alpha-weighted metres, "alpha":
@@ -181,7 +202,10 @@ def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=
     "rect", "values" (sorted) and "ranges"; a (V NT,) int32 tensor put under "walked" beforehand is filled with the entries each tile's
     workgroup staged (tools; not with harmonics).  With g.sh the colours of every (view, Gaussian) are evaluated first
     and the blend reads those; without, nothing changes.  One host synchronisation reads E (a second one, for the longest tile, only with stats); more than
-    max_entries (or 2^31 - 1) entries are refused."""
+    max_entries (or 2^31 - 1) entries are refused.  With g.features the blend is the one that also sums the scores: the
+    dict gains "features" (V, F, H, W) fp32, the blended scores sum_entries feat[g] w (not divided by alpha), and "labels" (V, H, W)
+    uint8 = label_image(features, alpha, label_alpha); rgb, depth and alpha keep their values up to the rounding of a colour byte to
+    fp32, which is exact.  Without features the call, its launches and its dict are what they were."""
     if not isinstance(g, Gaussians):
         raise hip.MudgError("render: expected Gaussians")
     if not torch.is_tensor(mats) or not mats.is_cuda or mats.dtype != torch.float32 or mats.dim() != 3 or mats.shape[2] != 12:
@@ -199,8 +223,21 @@ def render(g: Gaussians, mats, cams, hw, *, znear=ZNEAR, zfar=ZFAR, max_entries=
     if stats is not None:
         stats.update(entries=b.entries, longest_tile=0, count=b.count, rect=b.rect, values=None, ranges=None)
     if b.entries == 0:
-        return dict(zip(("rgb", "depth", "alpha"), _blank(views, h, w, dev)))
+        out = dict(zip(("rgb", "depth", "alpha"), _blank(views, h, w, dev)))
+        if g.features is not None:
+            out["features"] = torch.zeros((views, g.features.shape[1], h, w), dtype=torch.float32, device=dev)
+            out["labels"] = label_image(out["features"], out["alpha"], label_alpha)
+        return out
     walked = stats.get("walked") if stats is not None else None
+    if g.features is not None:                                              # §29: the blend that also sums the scores
+        if walked is not None:
+            raise hip.MudgError("render: the blend that sums features does not count the entries it walked")
+        colours = _byte_colours(pts) if g.sh is None else ops.gauss_sh_colour(pts, mats.contiguous(), b.count, g.colour, g.sh, ids=g.ids)
+        rgb, out_depth, alpha, features, _ = ops.gauss_blend_feat(colours, g.features, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w),
+                                                                  with_state=False)
+        if stats is not None:
+            stats.update(longest_tile=int((b.ranges[:, 1] - b.ranges[:, 0]).max().item()), values=b.values, ranges=b.ranges)
+        return {"rgb": rgb, "depth": out_depth, "alpha": alpha, "features": features, "labels": label_image(features, alpha, label_alpha)}
     if g.sh is not None:
         if walked is not None:
             raise hip.MudgError("render: the blend that reads per-view colours does not count the entries it walked")
@@ -223,12 +260,13 @@ def scene_matrices(objects: Optional[ObjectSet], w2c, frame):
 
 
 def render_scene(g: Gaussians, objects: Optional[ObjectSet], intr, c2w_frames, hw_native, hw_out, poses=None, *, frame_ids=None, shift=2.0,
-                 znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, stats=None):
+                 znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, stats=None, label_alpha=0.5):
     """Render T frames at P poses, with render_conditions' argument conventions: intr (3, 3) or (T, 3, 3) at hw_native, c2w_frames
     (T, 4, 4), poses None (the original pose and virtual_poses(c2w, shift): P = 3) or (T, P, 4, 4), frame_ids the scene's frame numbers
     for the objects' transforms.  `g` is Gaussians.from_scene's set (ids 0 and 1 + object): background and objects go through one sort
     and occlude one another per pixel.  Returns {"rgb": (P, T, 3, H, W), "depth", "alpha": (P, T, H, W)} fp32 and "rgb_u8": (P, T, H, W, 3)
-    uint8 = floor(rgb 255 + 0.5) clamped.  stats: a list that receives one dict per frame."""
+    uint8 = floor(rgb 255 + 0.5) clamped.  stats: a list that receives one dict per frame.  With g.features also "features" (P, T, F, H, W)
+    and "labels" (P, T, H, W) uint8, as render gives them."""
     if not isinstance(g, Gaussians) or (objects is not None and not isinstance(objects, ObjectSet)):
         raise hip.MudgError("render_scene: expected Gaussians and an ObjectSet (or None)")
     c2w_frames = np.asarray(c2w_frames, dtype=np.float64)
@@ -247,10 +285,10 @@ def render_scene(g: Gaussians, objects: Optional[ObjectSet], intr, c2w_frames, h
     for t in range(T):
         st = {} if stats is not None else None
         frames.append(render(g, mats[t], scaled_intrinsics(intr[t], hw_native, hw_out).astype(np.float32), hw_out, znear=znear, zfar=zfar,
-                             max_entries=max_entries, stats=st))
+                             max_entries=max_entries, stats=st, label_alpha=label_alpha))
         if stats is not None:
             stats.append(st)
-    out = {k: torch.stack([f[k] for f in frames], dim=1) for k in ("rgb", "depth", "alpha")}
+    out = {k: torch.stack([f[k] for f in frames], dim=1) for k in frames[0]}
     out["rgb_u8"] = torch.floor(out["rgb"] * 255.0 + 0.5).clamp_(0.0, 255.0).to(torch.uint8).permute(0, 1, 3, 4, 2).contiguous()
     return out
 
@@ -263,8 +301,13 @@ def _pack_xyz(xyz):
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density=None, sh=None, sh_degree=None):
+    def forward(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density=None, sh=None, sh_degree=None,
+                features=None):
+        if features is not None:                                            # §29: its own forward; backward tells by ctx.features
+            return _Render._forward_features(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density, sh,
+                                             sh_degree, features)
         h, w = hw
+        ctx.features = False
         ctx.density = density
         ctx.sh_degree = sh_degree if sh is not None else None
         pts = _pack_xyz(xyz)
@@ -287,7 +330,68 @@ class _Render(torch.autograd.Function):
         return rgb, out_depth, alpha
 
     @staticmethod
-    def backward(ctx, d_rgb, d_depth, d_alpha):
+    def _forward_features(ctx, xyz, colour, cov, opacity, mats, cams, hw, ids, znear, zfar, max_entries, density, sh, sh_degree, features):
+        """forward with features (n, F): the same projection, binning and harmonics, then the blend that also sums the
+        scores.  Returns (rgb, depth, alpha, feat)."""
+        h, w = hw
+        ctx.features = True
+        ctx.density = density
+        ctx.sh_degree = sh_degree if sh is not None else None
+        pts = _pack_xyz(xyz)
+        cov, opacity, colour = cov.detach().contiguous(), opacity.detach().contiguous(), colour.detach().contiguous()
+        features = features.detach().contiguous()
+        b = _bin("render_differentiable", pts, cov, opacity, mats, cams, (h, w), ids, znear, zfar, max_entries)
+        ctx.meta = (cams, (h, w), ids, znear, zfar, b.entries)
+        ctx.shapes = (tuple(mats.shape), tuple(features.shape), None if sh is None else tuple(sh.shape))
+        if b.entries == 0:
+            ctx.save_for_backward(xyz)
+            return _blank(mats.shape[0], h, w, xyz.device) + (torch.zeros((mats.shape[0], features.shape[1], h, w), dtype=torch.float32,
+                                                                          device=xyz.device),)
+        colours = colour
+        if sh is not None:                                                  # §27: one colour per (view, Gaussian)
+            sh = sh.detach().contiguous()
+            colours = ops.gauss_sh_colour(pts, mats, b.count, colour, sh, ids=ids, active=sh_degree)
+        rgb, out_depth, alpha, feat, state = ops.gauss_blend_feat(colours, features, b.uv, b.conic, b.depth, b.values, b.ranges, (h, w))
+        ctx.save_for_backward(pts, colour, cov, mats, b.uv, b.conic, b.depth, b.values, b.order, b.offsets, b.count, b.ranges, state, features,
+                              feat, *(() if sh is None else (sh, colours)))
+        return rgb, out_depth, alpha, feat
+
+    @staticmethod
+    def _backward_features(ctx, d_rgb, d_depth, d_alpha, d_feat):
+        """backward of _forward_features: blend_bwd_feat, then project_bwd (and the harmonics', the matrices' and density's passes) on
+        `partial` exactly as without features, and feat_bwd on `partial_feat`.  One gradient per argument of forward."""
+        cams, hw, ids, znear, zfar, entries = ctx.meta
+        mats_shape, feat_shape, sh_shape = ctx.shapes
+        if entries == 0:                                                    # nothing was drawn: no launch
+            n, dev = ctx.saved_tensors[0].shape[0], ctx.saved_tensors[0].device
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            return (z(n, 3), z(n, 3), z(n, 6), z(n), z(*mats_shape) if ctx.needs_input_grad[4] else None) + (None,) * 7 + (
+                None if sh_shape is None else z(*sh_shape), None, z(*feat_shape))
+        pts, colour, cov, mats, uv, conic, depth, values, order, offsets, count, ranges, state, features, feat = ctx.saved_tensors[:15]
+        sh, colours = ctx.saved_tensors[15:] if len(ctx.saved_tensors) > 15 else (None, colour)
+        views, (h, w) = mats.shape[0], hw
+        grad = lambda g, shape: torch.zeros(shape, dtype=torch.float32, device=pts.device) if g is None else g.to(torch.float32).contiguous()
+        ups = (grad(d_rgb, (views, 3, h, w)), grad(d_depth, (views, h, w)), grad(d_alpha, (views, h, w)), grad(d_feat, tuple(feat.shape)))
+        partial, partial_feat = ops.gauss_blend_bwd_feat(colours, features, uv, conic, depth, values, order, ranges, hw, state, feat, *ups)
+        d_xyz, d_cov, d_opacity, d_colour = ops.gauss_project_bwd(pts, cov, mats, cams, hw, count, offsets, partial, ids=ids, znear=znear,
+                                                                  zfar=zfar)
+        d_features = ops.gauss_feat_bwd(count, offsets, partial_feat)
+        d_mats = d_sh = None
+        if ctx.needs_input_grad[4]:
+            d_mats = ops.gauss_pose_bwd(pts, cov, mats, cams, hw, count, offsets, partial, ids=ids, znear=znear, zfar=zfar)
+        if sh is not None:
+            d_colour, d_sh, d_xyz_dir = ops.gauss_sh_bwd(pts, mats, count, offsets, partial, colour, sh, ids=ids, active=ctx.sh_degree)
+            d_xyz = d_xyz + d_xyz_dir
+            if d_mats is not None:
+                d_mats = d_mats + ops.gauss_sh_pose_bwd(pts, mats, count, offsets, partial, colour, sh, ids=ids, active=ctx.sh_degree)
+        if ctx.density is not None:
+            ops.gauss_density_accumulate(partial, count, offsets, hw, ctx.density.grad_sum, ctx.density.seen)
+        return (d_xyz, d_colour, d_cov, d_opacity, d_mats) + (None,) * 7 + (d_sh, None, d_features)
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_depth, d_alpha, d_feat=None):
+        if ctx.features:
+            return _Render._backward_features(ctx, d_rgb, d_depth, d_alpha, d_feat)
         cams, hw, ids, znear, zfar, entries = ctx.meta
         if entries == 0:                                                    # nothing was drawn: no launch
             n, dev = ctx.saved_tensors[0].shape[0], ctx.saved_tensors[0].device
@@ -322,7 +426,7 @@ class _Render(torch.autograd.Function):
 
 
 def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES,
-                          density=None, sh=None, sh_degree=None):
+                          density=None, sh=None, sh_degree=None, features=None):
     """`render` with gradients.  xyz (n, 3), colour (n, 3) in byte units (0 .. 255, not necessarily whole), cov (n, 6) and
     opacity (n,): fp32 on the GPU; mats, cams, hw and ids as `render` takes them.  Returns (rgb (V, 3, H, W), depth (V, H, W), alpha
     (V, H, W)); backward gives gradients for the first four arguments and, when `mats` requires one, for the matrices (DESIGN.md §28:
@@ -333,7 +437,13 @@ def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None
     coefficients in byte units of the harmonics of degrees 1 .. L, K = (L + 1)^2, L = 1, 2 or 3: `colour` is then the
     direction-independent term, every (view, Gaussian) gets max(0, colour + sum B_k(d) sh[k - 1]), backward also gives the gradient of sh
     and adds to xyz's what reaches it through the direction; sh_degree (default L) is the highest degree that takes part, and the
-    coefficients above it get a zero gradient.  With sh None nothing else happens: the same launches, the same bits."""
+    coefficients above it get a zero gradient.  With sh None nothing else happens: the same launches, the same bits.  features: (n, F)
+    fp32 class scores, 1 <= F <= ops.GAUSS_FEAT_MAX: the call then returns (rgb, depth, alpha, feat) with feat (V, F, H, W)
+    the blended scores sum feat[g] w, rgb, depth and alpha keep their bits, and backward also gives the gradient of features; the
+    gradients of everything else include what reaches them through feat.  With features None nothing else happens."""
+    if features is not None:
+        features = _on_gpu("render_differentiable: features", features, torch.float32,
+                           (xyz.shape[0] if torch.is_tensor(xyz) else -1, _feature_width_of("render_differentiable", features)))
     n = xyz.shape[0] if torch.is_tensor(xyz) and xyz.dim() == 2 else -1
     if density is not None and (not isinstance(density, DensityStats) or density.grad_sum.shape[0] != n):
         raise hip.MudgError(f"render_differentiable: density is a DensityStats of {n} Gaussians")
@@ -356,13 +466,13 @@ def render_differentiable(xyz, colour, cov, opacity, mats, cams, hw, *, ids=None
     if sh is None:
         if sh_degree is not None:
             raise hip.MudgError("render_differentiable: sh_degree comes with sh")
-        return _Render.apply(*args)
+        return _Render.apply(*args) if features is None else _Render.apply(*args, None, None, features)
     sh = _on_gpu("render_differentiable: sh", sh, torch.float32, (n, _sh_rows_of("render_differentiable", sh), 3))
     degree = _sh_degree_of(sh)
     active = degree if sh_degree is None else int(sh_degree)
     if not 0 <= active <= degree:
         raise hip.MudgError(f"render_differentiable: sh_degree {active} of coefficients of degree {degree}")
-    return _Render.apply(*args, sh, active)
+    return _Render.apply(*args, sh, active) if features is None else _Render.apply(*args, sh, active, features)
 
 
 # ------------------------------------------------------------------------------------------------ camera poses that move (§28)
@@ -449,8 +559,10 @@ class CameraPoses:
 PARAMETERS = ("xyz", "colour", "log_scale", "quat", "opacity_logit")
 LEARNING_RATES = {"xyz": 2e-3, "colour": 2.0, "log_scale": 5e-3, "quat": 1e-3, "opacity_logit": 5e-2}      # metres, bytes, log metres, -, logits
 LEARNING_RATES["sh"] = LEARNING_RATES["colour"] / 20       # bytes; 3DGS's ratio of the two rates, not tuned here
-POSE_LEARNING_RATE = 1e-3                                  # radians and metres of a CameraPoses twist; not tuned here.  Beside
+POSE_LEARNING_RATE = 1e-3                                 # radians and metres of a CameraPoses twist; not tuned here.  Beside
 #                                                            LEARNING_RATES, not in it: that table is the model's leaves, and the twist is not one
+CLASS_LEARNING_RATE = 0.05                                 # logits of GaussianModel.class_logits, opacity_logit's rate; not tuned here (DESIGN.md
+#                                                            §29).  Beside LEARNING_RATES as the twist's rate is: the table's keys are pinned
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-15
 MAX_SEED_OPACITY = 0.999                       # a seed opacity of 1 would be an infinite logit
 
@@ -460,10 +572,12 @@ class GaussianModel:
     of the per-axis standard deviation), `quat` (n, 4) = (w, x, y, z), `opacity_logit` (n,), all fp32 leaves on the GPU that require
     gradients, and `ids` (n,) int32 or None as Gaussians has them.  Covariance R exp(log_scale)^2 R^T and opacity sigmoid(opacity_logit)
     are torch expressions, so autograd carries the kernels' gradients to the parameters.  `sh` (n, K - 1, 3) fp32 in byte units or None:
-    the coefficients of the harmonics of degrees 1 .. L, a sixth leaf when present; enable_sh(L) creates zeros."""
-    sh = None
+    the coefficients of the harmonics of degrees 1 .. L, a sixth leaf when present; enable_sh(L) creates zeros.
+    `class_logits` (n, F) fp32 or None: a row of class scores per Gaussian (DESIGN.md §29), one more leaf when present;
+    enable_classes(F) creates zeros."""
+    sh = class_logits = None
 
-    def __init__(self, xyz, colour, log_scale, quat, opacity_logit, ids=None, sh=None):
+    def __init__(self, xyz, colour, log_scale, quat, opacity_logit, ids=None, sh=None, class_logits=None):
         n = xyz.shape[0] if torch.is_tensor(xyz) and xyz.dim() == 2 else -1
         shapes = {"xyz": (n, 3), "colour": (n, 3), "log_scale": (n, 3), "quat": (n, 4), "opacity_logit": (n,)}
         for name, t in zip(PARAMETERS, (xyz, colour, log_scale, quat, opacity_logit)):
@@ -472,6 +586,10 @@ class GaussianModel:
         self.sh = None
         if sh is not None:
             self.sh = _on_gpu("GaussianModel: sh", sh, torch.float32, (n, _sh_rows_of("GaussianModel", sh), 3)).detach().clone().requires_grad_(True)
+        self.class_logits = None
+        if class_logits is not None:
+            width = _feature_width_of("GaussianModel", class_logits)
+            self.class_logits = _on_gpu("GaussianModel: class_logits", class_logits, torch.float32, (n, width)).detach().clone().requires_grad_(True)
 
     def __len__(self):
         return self.xyz.shape[0]
@@ -493,9 +611,22 @@ class GaussianModel:
             raise hip.MudgError(f"GaussianModel.enable_sh: the model has harmonics of degree {self.sh_degree}, not {degree}")
         return self
 
+    def enable_classes(self, classes):
+        """Give the model zero class scores for `classes` classes (1 .. ops.GAUSS_FEAT_MAX).  A model that has scores keeps them if the
+        number is theirs and refuses another."""
+        classes = int(classes)
+        if not 1 <= classes <= ops.GAUSS_FEAT_MAX:
+            raise hip.MudgError(f"GaussianModel.enable_classes: {classes} classes (1 .. {ops.GAUSS_FEAT_MAX})")
+        if self.class_logits is None:
+            self.class_logits = torch.zeros((len(self), classes), dtype=torch.float32, device=self.xyz.device).requires_grad_(True)
+        elif self.class_logits.shape[1] != classes:
+            raise hip.MudgError(f"GaussianModel.enable_classes: the model has {self.class_logits.shape[1]} classes, not {classes}")
+        return self
+
     def parameters(self):
-        """The leaves by name: PARAMETERS, and "sh" when the model has harmonics."""
-        return {name: getattr(self, name) for name in PARAMETERS + (("sh",) if self.sh is not None else ())}
+        """The leaves by name: PARAMETERS, "sh" when the model has harmonics and "class_logits" when it has class scores."""
+        more = (("sh",) if self.sh is not None else ()) + (("class_logits",) if self.class_logits is not None else ())
+        return {name: getattr(self, name) for name in PARAMETERS + more}
 
     def covariance(self):
         return covariance_from_scales_rotations(torch.exp(self.log_scale), self.quat)
@@ -535,10 +666,11 @@ class GaussianModel:
             byte = torch.floor(self.colour + 0.5).clamp_(0.0, 255.0).to(torch.int32)
             word = byte[:, 0] | (byte[:, 1] << 8) | (byte[:, 2] << 16)
             pts = torch.cat([self.xyz.contiguous().view(torch.int32), word[:, None]], dim=1).contiguous()
+            features = None if self.class_logits is None else self.class_logits.detach().clone()      # §29: the scores, as fitted
             if self.sh is None:
-                return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids)
+                return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids, features=features)
             return Gaussians(PointCloud(pts), self.covariance().contiguous(), self.opacity().contiguous(), self.ids,
-                             sh=self.sh.detach().clone(), colour=self.colour.detach().clone())
+                             sh=self.sh.detach().clone(), colour=self.colour.detach().clone(), features=features)
 
 
 # ------------------------------------------------------------------------------------------------ growing and pruning while fitting (§25)
@@ -654,6 +786,13 @@ def densify_and_prune(model: GaussianModel, stats: DensityStats, moments: dict, 
             p = model.sh.detach()
             m, v = moments["sh"] if "sh" in moments else (torch.zeros_like(p), torch.zeros_like(p))
             sh, sh_m, sh_v = density_rows(action, rows, p, m, v)
+        if model.class_logits is not None:                                  # §29: and so do the class scores
+            p = model.class_logits.detach()
+            m, v = moments["class_logits"] if "class_logits" in moments else (torch.zeros_like(p), torch.zeros_like(p))
+            logits, logits_m, logits_v = density_rows(action, rows, p, m, v)
+    if model.class_logits is not None:
+        model.class_logits = logits.contiguous().requires_grad_(True)
+        moments["class_logits"] = (logits_m.contiguous(), logits_v.contiguous())
     if model.sh is not None:
         model.sh = sh.contiguous().requires_grad_(True)
         moments["sh"] = (sh_m.contiguous(), sh_v.contiguous())
@@ -738,9 +877,68 @@ def _image_loss_terms(rgb, targets, depth=None, depth_targets=None, *, ssim_weig
 image_loss.terms = _image_loss_terms
 
 
+# ------------------------------------------------------------------------------------------------ the class loss (§29)
+UNLABELLED = 255                 # a label image's "no class here"; any label >= F is unlabelled
+
+
+class _ClassLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, labels, weight):
+        maps, partial = ops.gauss_class_loss(feat, labels)
+        totals = ops.gauss_class_loss_finish(partial, feat.shape[0], feat.shape[2:], weight=weight)
+        ctx.weight = weight
+        ctx.save_for_backward(maps, totals)
+        ctx.mark_non_differentiable(totals)
+        return totals[3].clone(), totals
+
+    @staticmethod
+    def backward(ctx, up, _):
+        maps, totals = ctx.saved_tensors
+        up = up.to(torch.float32).reshape(1).contiguous()                   # stays on the device: the kernel reads it
+        return ops.gauss_class_loss_bwd(maps, totals, up, weight=ctx.weight), None, None
+
+
+def _class_labels(name, labels, shape):
+    """uint8 labels as they are; int64 labels converted, values outside 0 .. 254 becoming UNLABELLED."""
+    if torch.is_tensor(labels) and labels.dtype == torch.int64:
+        labels = torch.where((labels >= 0) & (labels < UNLABELLED), labels, UNLABELLED).to(torch.uint8)
+    return _on_gpu(f"{name}: labels", labels, torch.uint8, shape)
+
+
+def class_loss(feat, labels, *, weight=1.0):
+    """weight times the mean over the labelled pixels of the softmax cross-entropy of feat (V, F, H, W) fp32, the blended class scores of
+    render_differentiable(..., features=), against labels (V, H, W) uint8 (or int64, converted): a pixel is labelled iff its label is
+    below F, so UNLABELLED = 255 marks sky and holes; with no labelled pixel the loss and its gradient are zero.  Three launches of
+    csrc/gaussians_feat.hip, no host synchronisation on either side.  Returns a 0-d fp32 loss whose backward gives the
+    gradient of feat.  class_loss.terms gives the sum and the count."""
+    return _ClassLoss.apply(*_class_loss_args(feat, labels, weight))[0]
+
+
+def _class_loss_args(feat, labels, weight):
+    if not torch.is_tensor(feat) or feat.dim() != 4 or feat.numel() == 0 or not 1 <= feat.shape[1] <= ops.GAUSS_FEAT_MAX:
+        got = tuple(feat.shape) if torch.is_tensor(feat) else type(feat).__name__
+        raise hip.MudgError(f"class_loss: feat is a (V, 1 .. {ops.GAUSS_FEAT_MAX}, H, W) fp32 tensor on the GPU (there is no CPU path), got {got}")
+    v, f, h, w = feat.shape
+    weight = float(weight)
+    if not 0.0 <= weight < float("inf"):
+        raise hip.MudgError(f"class_loss: weight {weight} is finite and not negative")
+    return _on_gpu("class_loss: feat", feat, torch.float32, (v, f, h, w)), _class_labels("class_loss", labels, (v, h, w)), weight
+
+
+def _class_loss_terms(feat, labels, *, weight=1.0):
+    """The parts of class_loss as 0-d tensors on the GPU, without gradients: loss, sum (of the labelled pixels' losses) and count (int32)."""
+    feat, labels, weight = _class_loss_args(feat, labels, weight)
+    with torch.no_grad():
+        totals = ops.gauss_class_loss_finish(ops.gauss_class_loss(feat.detach(), labels)[1], feat.shape[0], feat.shape[2:], weight=weight)
+    return dict(loss=totals[3], sum=totals[0], count=totals.view(torch.int32)[1])
+
+
+class_loss.terms = _class_loss_terms
+
+
 def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_per_step=None, depth_targets=None, depth_weight=0.0,
         trainable=PARAMETERS, znear=ZNEAR, zfar=ZFAR, max_entries=MAX_ENTRIES, density=None, ssim_weight=0.0, sh_degree=0, sh_raise_every=None,
-        poses=None):
+        poses=None, label_targets=None, class_weight=0.0, classes=None):
     """Optimise `model` in place against targets (V, 3, H, W) fp32 in [0, 1] seen through mats (V, nmat, 12) and cams.
     Iteration i renders the views_per_step (default: all) views (i views_per_step + k) mod V, takes the mean absolute difference of rgb,
     adds depth_weight times the mean absolute depth difference over the pixels where depth_targets (V, H, W) is positive, and takes one
@@ -760,7 +958,12 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
     bit for bit, and a model that has harmonics is refused.  poses: a CameraPoses of V views or None.  With one, every
     iteration renders through poses.apply(mats[pick], pick), the matrices' gradient reaches poses.twist, and the twist is one more tensor
     of the Adam step at POSE_LEARNING_RATE (lr may name "pose"; the rate is not tuned); trainable=() is then allowed and is pure
-    registration against fixed Gaussians; density control does not touch the twist.  With None nothing changes, bit for bit.  Returns the
+    registration against fixed Gaussians; density control does not touch the twist.  With None nothing changes, bit for bit.
+    label_targets: (V, H, W) uint8 (or int64) label images, 255 or any value >= classes unlabelled, with class_weight > 0:
+    the model gets zero class scores for `classes` classes (default: metrics.CLASSES) if it has none, every iteration renders them
+    with the colours and adds class_loss(feat, label_targets[pick], weight=class_weight), "class_logits" moves at
+    CLASS_LEARNING_RATE (lr may name it), density control carries its rows and moments as it carries sh's, and
+    model.gaussians() hands the scores to render.  With label_targets None or class_weight 0 nothing changes, bit for bit.  Returns the
     loss of every iteration."""
     from .train import kernels as K
     if not isinstance(model, GaussianModel):
@@ -784,14 +987,24 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
         raise hip.MudgError(f"fit: sh_degree {sh_degree} for a model with harmonics of degree {model.sh_degree}")
     if poses is not None and (not isinstance(poses, CameraPoses) or len(poses) != views or poses.twist.device != mats.device):
         raise hip.MudgError(f"fit: poses is a CameraPoses of {views} views on the matrices' device, or None")
-    known = PARAMETERS + ("sh", "pose")
-    rates = {**LEARNING_RATES, "pose": POSE_LEARNING_RATE, **(lr or {})}
+    class_weight = float(class_weight)
+    if not 0.0 <= class_weight < float("inf"):
+        raise hip.MudgError(f"fit: class_weight {class_weight} is finite and not negative")
+    with_classes = label_targets is not None and class_weight > 0.0
+    if with_classes:
+        from .metrics import CLASSES
+        label_targets = _class_labels("fit", label_targets, (views, h, w))
+        model.enable_classes(CLASSES if classes is None else classes)
+    known = PARAMETERS + ("sh", "pose", "class_logits")
+    rates = {**LEARNING_RATES, "pose": POSE_LEARNING_RATE, "class_logits": CLASS_LEARNING_RATE, **(lr or {})}
     names = [n for n in PARAMETERS if n in tuple(trainable)]
     if (not names and poses is None) or "pose" in tuple(trainable) or set(trainable) - set(known) or set(rates) - set(known) or int(iters) < 0:
         raise hip.MudgError(f"fit: trainable and lr name parameters among {PARAMETERS}, got {tuple(trainable)} and {tuple(rates)}")
     if sh_degree:
         model.enable_sh(sh_degree)
         names.append("sh")
+    if with_classes:
+        names.append("class_logits")
     if poses is not None:
         names.append("pose")
     leaf = lambda n: poses.twist if n == "pose" else getattr(model, n)
@@ -824,10 +1037,12 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
         harmonics = {}
         if sh_degree:                                                       # §27: the active degree rises by one every sh_raise_every
             harmonics = dict(sh=model.sh, sh_degree=sh_degree if sh_raise_every is None else min(sh_degree, it // int(sh_raise_every)))
-        rgb, depth, _ = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(),
-                                              mats[pick] if poses is None else poses.apply(mats[pick], pick), cams, (h, w),
-                                              ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries,
-                                              density=stats if gathers else None, **harmonics)
+        if with_classes:                                                    # §29: the scores ride the same walk
+            harmonics["features"] = model.class_logits
+        rgb, depth, _, *scores = render_differentiable(model.xyz, model.colour, model.covariance(), model.opacity(),
+                                                       mats[pick] if poses is None else poses.apply(mats[pick], pick), cams, (h, w),
+                                                       ids=model.ids, znear=znear, zfar=zfar, max_entries=max_entries,
+                                                       density=stats if gathers else None, **harmonics)
         with_depth = depth_targets is not None and bool(depth_weight)
         if ssim_weight:                                                     # §26: the loss and its backward in csrc/gaussians_loss.hip
             loss = image_loss(rgb, targets[pick], depth if with_depth else None, depth_targets[pick] if with_depth else None,
@@ -838,6 +1053,8 @@ def fit(model: GaussianModel, targets, mats, cams, hw, *, iters, lr=None, views_
                 want = depth_targets[pick]
                 seen = want > 0
                 loss = loss + float(depth_weight) * ((depth - want).abs() * seen).sum() / seen.sum().clamp(min=1)
+        if with_classes:
+            loss = loss + class_loss(scores[0], label_targets[pick], weight=class_weight)
         for g, d in zip(grads, torch.autograd.grad(loss, params, allow_unused=True)):
             g.zero_() if d is None else g.copy_(d)
         for rate, (table, chunks) in tables.items():

@@ -210,6 +210,12 @@ SIGNATURES = {
     "mudg_gauss_loss": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "mudg_gauss_loss_finish": (_I, [_P, _I, _I, _I, _F, _F, _P, _P]),
     "mudg_gauss_loss_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P]),
+    "mudg_gauss_blend_feat": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mudg_gauss_blend_bwd_feat": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mudg_gauss_feat_bwd": (_I, [_P, _P, _P, _L, _L, _I, _I, _P, _P]),
+    "mudg_gauss_class_loss": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "mudg_gauss_class_loss_finish": (_I, [_P, _I, _I, _I, _F, _P, _P]),
+    "mudg_gauss_class_loss_bwd": (_I, [_P, _P, _P, _F, _I, _I, _I, _I, _P, _P]),
     "mudg_short_attention_ok": (_I, [C.POINTER(ShortAttnDesc)]),
     "mudg_short_attention": (_I, [C.POINTER(ShortAttnDesc), _P]),
     "mudg_layernorm_f32": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _F, _P]),

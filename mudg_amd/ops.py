@@ -1355,6 +1355,126 @@ def gauss_loss_bwd(rgb, targets, maps, totals, upstream, depth=None, depth_targe
     return d_rgb, d_depth
 
 
+GAUSS_FEAT_MAX = 32                                                 # feature values (class scores) a Gaussian may carry
+GAUSS_CLASS_COLS, GAUSS_CLASS_TOTALS = 2, 4                         # a tile's partial row; the finish buffer
+
+
+def _gauss_entries_feat(name, colours, feat, uv, conic, depth, values_sorted, ranges, hw):
+    """The operands of the two blends with features: colours (n, 3) or (V, n, 3) and feat (n, F) -> (colour_views, F, V, n, h, w)."""
+    per_view = torch.is_tensor(colours) and colours.dim() == 3
+    shared = _gauss_entries_views if per_view else (lambda nm, c, *rest: _gauss_entries(nm, c, _GAUSS_COLOURS, *rest))
+    v, n, h, w, _ = shared(name, colours, uv, conic, depth, values_sorted, ranges, hw)
+    _splat_tensor(f"{name}: feat", feat, torch.float32)
+    if feat.dim() != 2 or feat.shape[0] != n or not 1 <= feat.shape[1] <= GAUSS_FEAT_MAX:
+        raise hip.MudgError(f"{name}: expected features ({n}, 1 .. {GAUSS_FEAT_MAX}), got {tuple(feat.shape)}")
+    return int(per_view), feat.shape[1], v, n, h, w
+
+
+def gauss_blend_feat(colours, feat, uv, conic, depth, values_sorted, ranges, hw, *, with_state=True):
+    """gauss_blend_train (colours (n, 3)) or gauss_blend_train_views (colours (V, n, 3)) that also blends feat (n, F) fp32, 1 <= F <= 32
+    (DESIGN.md §29).  Returns rgb, depth, alpha and state with that call's bits (state None with with_state false: inference) and
+    feat_out (V, F, H, W) fp32, the raw sums of feat[g][k] w, which are their own state."""
+    views, f, v, n, h, w = _gauss_entries_feat("gauss_blend_feat", colours, feat, uv, conic, depth, values_sorted, ranges, hw)
+    dev = feat.device
+    rgb, out_depth, alpha = _gauss_images(v, h, w, dev)
+    feat_out = torch.empty((v, f, h, w), dtype=torch.float32, device=dev)
+    state = torch.empty((v, 5, h, w), dtype=torch.float32, device=dev) if with_state else None
+    hip.check(hip.lib().mudg_gauss_blend_feat(colours.data_ptr(), views, feat.data_ptr(), f, uv.data_ptr(), conic.data_ptr(), depth.data_ptr(),
+                                              values_sorted.data_ptr(), ranges.data_ptr(), n, values_sorted.numel(), v, h, w, rgb.data_ptr(),
+                                              out_depth.data_ptr(), alpha.data_ptr(), feat_out.data_ptr(), _ptr(state), _stream()),
+              "mudg_gauss_blend_feat")
+    return rgb, out_depth, alpha, feat_out, state
+
+
+def gauss_blend_bwd_feat(colours, feat, uv, conic, depth, values_sorted, order, ranges, hw, state, feat_out, d_rgb, d_depth, d_alpha, d_feat):
+    """gauss_blend_bwd (or _views) with the features' share: partial (E, 10) as that call returns it, and partial_feat (E, F) fp32, the
+    sums over the tile's pixels of d_feat[k] w at the entry's unsorted position, in the same fixed order."""
+    views, f, v, n, h, w = _gauss_entries_feat("gauss_blend_bwd_feat", colours, feat, uv, conic, depth, values_sorted, ranges, hw)
+    e = values_sorted.numel()
+    if e * f >= 2 ** 31:
+        raise hip.MudgError(f"gauss_blend_bwd_feat: {e} entries of {f} features (E F < 2^31)")
+    _splat_tensor("gauss_blend_bwd_feat: order", order, torch.int64, (e,))
+    _splat_tensor("gauss_blend_bwd_feat: state", state, torch.float32, (v, 5, h, w))
+    _splat_tensor("gauss_blend_bwd_feat: feat_out", feat_out, torch.float32, (v, f, h, w))
+    _splat_tensor("gauss_blend_bwd_feat: d_rgb", d_rgb, torch.float32, (v, 3, h, w))
+    _splat_tensor("gauss_blend_bwd_feat: d_depth", d_depth, torch.float32, (v, h, w))
+    _splat_tensor("gauss_blend_bwd_feat: d_alpha", d_alpha, torch.float32, (v, h, w))
+    _splat_tensor("gauss_blend_bwd_feat: d_feat", d_feat, torch.float32, (v, f, h, w))
+    partial = torch.empty((e, GAUSS_SUMS), dtype=torch.float32, device=feat.device)
+    partial_feat = torch.empty((e, f), dtype=torch.float32, device=feat.device)
+    hip.check(hip.lib().mudg_gauss_blend_bwd_feat(colours.data_ptr(), views, feat.data_ptr(), f, uv.data_ptr(), conic.data_ptr(), depth.data_ptr(),
+                                                  values_sorted.data_ptr(), order.data_ptr(), ranges.data_ptr(), n, e, v, h, w, state.data_ptr(),
+                                                  feat_out.data_ptr(), d_rgb.data_ptr(), d_depth.data_ptr(), d_alpha.data_ptr(),
+                                                  d_feat.data_ptr(), partial.data_ptr(), partial_feat.data_ptr(), _stream()),
+              "mudg_gauss_blend_bwd_feat")
+    return partial, partial_feat
+
+
+def gauss_feat_bwd(count, offsets, partial_feat):
+    """Every Gaussian's rows of partial_feat (E, F) gathered per view in ascending order, the views added in order: d_feat (n, F) fp32.
+    count (V, n) int32 and offsets (V, n) int64 are gauss_project_bwd's, with its guards."""
+    _splat_tensor("gauss_feat_bwd: count", count, torch.int32)
+    if count.dim() != 2 or count.numel() == 0:
+        raise hip.MudgError(f"gauss_feat_bwd: expected counts (V > 0, n > 0), got {tuple(count.shape)}")
+    v, n = count.shape
+    _splat_tensor("gauss_feat_bwd: offsets", offsets, torch.int64, (v, n))
+    _splat_tensor("gauss_feat_bwd: partial_feat", partial_feat, torch.float32)
+    if partial_feat.dim() != 2 or partial_feat.shape[0] == 0 or not 1 <= partial_feat.shape[1] <= GAUSS_FEAT_MAX:
+        raise hip.MudgError(f"gauss_feat_bwd: expected partials (E > 0, 1 .. {GAUSS_FEAT_MAX}), got {tuple(partial_feat.shape)}")
+    e, f = partial_feat.shape
+    d_feat = torch.empty((n, f), dtype=torch.float32, device=count.device)
+    hip.check(hip.lib().mudg_gauss_feat_bwd(count.data_ptr(), offsets.data_ptr(), partial_feat.data_ptr(), e, n, v, f, d_feat.data_ptr(),
+                                            _stream()), "mudg_gauss_feat_bwd")
+    return d_feat
+
+
+def _gauss_scores(name, x):
+    _splat_tensor(f"{name}: x", x, torch.float32)
+    if x.dim() != 4 or x.numel() == 0 or not 1 <= x.shape[1] <= GAUSS_FEAT_MAX:
+        raise hip.MudgError(f"{name}: expected (V > 0, 1 .. {GAUSS_FEAT_MAX}, H > 0, W > 0) scores, got {tuple(x.shape)}")
+    return tuple(x.shape)
+
+
+def gauss_class_loss(x, labels):
+    """The forward of the class loss.  x (V, F, H, W) fp32 blended scores, labels (V, H, W) uint8; a pixel is labelled iff
+    its label is below F.  Returns maps (V, F, H, W) = softmax(x) - onehot(label) (+0 where unlabelled) and partial (V NT, 2): each
+    16 x 16 tile's sum of log S - p_label and its labelled count (int32 bits)."""
+    v, f, h, w = _gauss_scores("gauss_class_loss", x)
+    _splat_tensor("gauss_class_loss: labels", labels, torch.uint8, (v, h, w))
+    tx, ty = gauss_tiles(h, w)
+    maps = torch.empty((v, f, h, w), dtype=torch.float32, device=x.device)
+    partial = torch.empty((v * tx * ty, GAUSS_CLASS_COLS), dtype=torch.float32, device=x.device)
+    hip.check(hip.lib().mudg_gauss_class_loss(x.data_ptr(), labels.data_ptr(), v, f, h, w, maps.data_ptr(), partial.data_ptr(), _stream()),
+              "mudg_gauss_class_loss")
+    return maps, partial
+
+
+def gauss_class_loss_finish(partial, views, hw, *, weight=1.0):
+    """gauss_class_loss's partials of `views` (H, W) images -> totals (4,) fp32: the sum of the pixels' losses, the labelled count as int32
+    bits, float(max(count, 1)) and the loss weight sum / max(count, 1).  One workgroup, one fixed order, no host synchronisation."""
+    h, w = (int(s) for s in hw)
+    tx, ty = gauss_tiles(h, w)
+    _splat_tensor("gauss_class_loss_finish: partial", partial, torch.float32, (int(views) * tx * ty, GAUSS_CLASS_COLS))
+    totals = torch.empty((GAUSS_CLASS_TOTALS,), dtype=torch.float32, device=partial.device)
+    hip.check(hip.lib().mudg_gauss_class_loss_finish(partial.data_ptr(), int(views), h, w, float(weight), totals.data_ptr(), _stream()),
+              "mudg_gauss_class_loss_finish")
+    return totals
+
+
+def gauss_class_loss_bwd(maps, totals, upstream, *, weight=1.0):
+    """The backward of the class loss: d_x (V, F, H, W) = ((upstream weight) / totals[2]) maps.  upstream is the loss's gradient, one
+    fp32 on the GPU, read by the kernel."""
+    v, f, h, w = _gauss_scores("gauss_class_loss_bwd", maps)
+    _splat_tensor("gauss_class_loss_bwd: totals", totals, torch.float32, (GAUSS_CLASS_TOTALS,))
+    _splat_tensor("gauss_class_loss_bwd: upstream", upstream, torch.float32)
+    if upstream.numel() != 1:
+        raise hip.MudgError(f"gauss_class_loss_bwd: the upstream gradient is one number, got {tuple(upstream.shape)}")
+    d_x = torch.empty_like(maps)
+    hip.check(hip.lib().mudg_gauss_class_loss_bwd(maps.data_ptr(), totals.data_ptr(), upstream.data_ptr(), float(weight), v, f, h, w,
+                                                  d_x.data_ptr(), _stream()), "mudg_gauss_class_loss_bwd")
+    return d_x
+
+
 # ------------------------------------------------------------------------------------------------ metric depth and lifted views
 def _depth_frames(name, frames):
     _splat_tensor(f"{name}: frames", frames, torch.uint8)

@@ -206,7 +206,7 @@ def fuse_window_outputs(outputs_by_pose, scene, frame_ids, poses, **rule):
     return cloud, scores
 
 
-def render_cloud_views(cloud, scene, frame_ids, pose, hw_out, scale, **kw):
+def render_cloud_views(cloud, scene, frame_ids, pose, hw_out, scale, *, fitted=None, **kw):
     """A cloud drawn as isotropic 3D Gaussians at a pose (mudg_amd/gaussians.py): what a fused cloud looks like in pixels.
 
     cloud: fuse_window_outputs' cloud, or any mudg_amd.render.PointCloud in world coordinates (the moving objects are whatever the cloud
@@ -214,7 +214,10 @@ def render_cloud_views(cloud, scene, frame_ids, pose, hw_out, scale, **kw):
     cameras; pose: as render_windows takes it, 0 / 1 / 2 or a (4, 4) camera-from-virtual-camera matrix; hw_out: the size rendered at;
     scale: the Gaussians' standard deviation in metres, a number or one per point (for a cloud thinned at voxel_size a multiple of it).
     **kw: opacity (default 1) and mudg_amd.gaussians.render_scene's keywords (znear, zfar, max_entries, stats).  Returns (frames (t, h,
-    w, 3) uint8, alpha (t, h, w) fp32): the frames on black, ready for mudg_amd.metrics.psnr_ssim against the scene's own frames."""
+    w, 3) uint8, alpha (t, h, w) fp32): the frames on black, ready for mudg_amd.metrics.psnr_ssim against the scene's own frames.
+    fitted: fit_cloud_views' mudg_amd.gaussians.Gaussians, drawn in place of the seeded cloud (cloud, scale and opacity are then unused and
+    cloud may be None).  If they carry class scores the call returns (frames, alpha, labels (t, h, w) int64): the argmax
+    of the blended scores, 255 where alpha <= label_alpha (a keyword, default 0.5), ready for mudg_amd.metrics.segmentation_scores."""
     import numpy as np
     from mudg_amd import gaussians, render
     frame_ids = [int(f) for f in frame_ids]
@@ -226,12 +229,16 @@ def render_cloud_views(cloud, scene, frame_ids, pose, hw_out, scale, **kw):
         cams = np.stack([render.virtual_poses(c, with_ori_pose=True)[int(pose)] for c in c2w])
     else:
         cams = c2w @ np.asarray(pose, dtype=np.float64)
-    g = gaussians.Gaussians.from_cloud(cloud, scale, kw.pop("opacity", 1.0))
+    if fitted is not None and not isinstance(fitted, gaussians.Gaussians):
+        raise ValueError("render_cloud_views: fitted is fit_cloud_views' Gaussians")
+    g = gaussians.Gaussians.from_cloud(cloud, scale, kw.pop("opacity", 1.0)) if fitted is None else fitted
     out = gaussians.render_scene(g, None, intr, c2w, scene.hw_native, hw_out, poses=cams[:, None], frame_ids=frame_ids, **kw)
+    if "labels" in out:
+        return out["rgb_u8"][0], out["alpha"][0], out["labels"][0].to(torch.int64)
     return out["rgb_u8"][0], out["alpha"][0]
 
 
-def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, **kw):
+def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, *, labels=None, **kw):
     """The companion of render_cloud_views: a cloud seeded as isotropic Gaussians and optimised against a window's frames
     (mudg_amd.gaussians.fit).
 
@@ -246,7 +253,11 @@ def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, **k
     of t views, one per frame, whose twist the fit then moves with the Gaussians, DESIGN.md §28, because a scenario's camera poses and
     tracked boxes carry calibration and tracking error; its world_to_camera gives the corrected cameras afterwards).  Returns the fitted
     mudg_amd.gaussians.Gaussians, which render, render_scene and the renderer of render_cloud_views draw; one fitted with harmonics
-    carries them, and its colour then depends on the pose it is drawn at."""
+    carries them, and its colour then depends on the pose it is drawn at.  labels: (t, h, w) int64 or uint8 label images at hw_out, such
+    as window_outputs' "semantic_labels", with the keyword class_weight > 0 (and classes, default mudg_amd.metrics.CLASSES): every
+    Gaussian then also learns a row of class scores by softmax cross-entropy, values outside 0 .. classes - 1 are
+    unlabelled, and the returned Gaussians carry the scores, which render_cloud_views(..., fitted=) draws as a label image at any pose.
+    The scores start at zero: they are not seeded from lifted labels."""
     import numpy as np
     import torch
     from mudg_amd import gaussians, hip, render
@@ -270,6 +281,8 @@ def fit_cloud_views(cloud, scene, frame_ids, frames_u8, pose, hw_out, scale, **k
     history = kw.pop("history", None)
     kw.setdefault("iters", 200)
     targets = frames_u8.permute(0, 3, 1, 2).to(torch.float32).div_(255.0).contiguous()
+    if labels is not None:
+        kw["label_targets"] = labels
     losses = gaussians.fit(model, targets, mats, k, (h, w), **kw)
     if history is not None:
         history.extend(losses)
